@@ -16,9 +16,15 @@ and the MAX-over-ranks time / SUM-over-ranks counts ("scaling": "weak").
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
         bench.py --gpus 8 --steps 20 --warmup 3             # what the driver runs: same ranks, launched from outside
 
+A plain run sets up, warms up, times the --steps steps back to back and prints the headline line (value, ms_per_step, ...).  `--full`
+synchronises inside the timed loop to sample the kernel times (its value / ms_per_step include those waits) and adds everything else
+this file measures: the per-launch kernel times and the rooflines, and at N = 1 the CPU baseline (all granted host
+cores + one core), the batch-size sweep, the single-window latency, the PCIe-inclusive streaming rate and the replay figures.
+`--dump-outputs DIR` writes what the timed path computed in its last step (states, costs, a fixed sample of the priors) as
+DIR/<name>.npy; the inputs depend on the arguments only, so two builds can be compared output for output.
+
 Modes (`--mode`):
-    solve   (default) the headline above; at N = 1 the line also carries the CPU baseline (all granted host cores + one core),
-            the single-window latency and the PCIe-inclusive streaming rate as extra keys;
+    solve   (default) the headline above;
     replay  BASELINE configs[4]: `--streams` (default 8) EuRoC-trajectory streams, stream s on rank s mod N, every rank advances
             its streams in lock step through the native estimator (include/tcv_estimator.h): value = optimised windows per second;
             a step is one frame of every stream;
@@ -212,6 +218,66 @@ def build_batches(tcv, synth, first_id: int, B: int):
     dropsm = [tcv.margin_old_drops(Wm[k], MWm[k]) for k in range(B)]
     batch = tcv.Batch(Wm, Mm, dropsm)
     return batch, wins, (Wm, Mm, dropsm, pdev)
+
+
+DUMP_STATE_WINDOWS = 8192        # --dump-outputs: states and costs of every window up to this many, else of a fixed sample
+DUMP_PRIOR_WINDOWS = 256         # --dump-outputs: priors of a fixed sample of this many windows
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _padded(arrays):
+    """one float64 array from per-window arrays, zero-padded to the largest shape (the windows of this file all have one shape)"""
+    arrays = [np.asarray(a, dtype=np.float64) for a in arrays]
+    shape = tuple(max(s) for s in zip(*[a.shape for a in arrays])) if arrays else ()
+    out = np.zeros((len(arrays),) + shape)
+    for i, a in enumerate(arrays):
+        out[(i,) + tuple(slice(0, s) for s in a.shape)] = a
+    return out
+
+
+def dump_outputs(path, batch, keep, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as <path>/<name>.npy (float64, 25 MB at 1024 windows):
+    the solved, gauge-fixed states written back into the caller's parameter blocks (tcv_batch_download_states), the initial / final cost,
+    iteration count and termination of every window (of a fixed sample above DUMP_STATE_WINDOWS), and for a fixed sample of
+    DUMP_PRIOR_WINDOWS windows the marginalisation prior the next frame takes (J0, r0, linearisation point x0) with its A', b'.  The samples
+    depend on the batch size only (seed 0); `window` / `prior_window` name the windows.  At N > 1 every rank writes its own shard
+    (rank<r>_<name>.npy).  The caller's parameter blocks hold their initial states again on return: the --full figures build new batches
+    from them (a batch of solved windows rejects its steps and skips most linearisations)."""
+    Wm = keep[0]
+    B = len(Wm)
+    rng = np.random.default_rng(0)
+    ws = np.arange(B) if B <= DUMP_STATE_WINDOWS else np.sort(rng.choice(B, DUMP_STATE_WINDOWS, replace=False))
+    ps = np.arange(B) if B <= DUMP_PRIOR_WINDOWS else np.sort(rng.choice(B, DUMP_PRIOR_WINDOWS, replace=False))
+    blocks = [[a for a in (w.pose, w.sb, w.ex, w.lam, w.td) if a is not None] for w in Wm]      # (the marginalisation windows share them)
+    initial = [[a.copy() for a in bl] for bl in blocks]
+    try:
+        batch.synchronize(); batch.download_states(); batch.download_priors()
+        s = batch.summaries()
+        out = {"window": ws, "pose": _padded([Wm[k].pose for k in ws]), "speedbias": _padded([Wm[k].sb for k in ws]),
+               "ex_pose": _padded([Wm[k].ex for k in ws]), "inv_depth": _padded([Wm[k].lam for k in ws]),
+               "initial_cost": [s[k].initial_cost for k in ws], "final_cost": [s[k].final_cost for k in ws],
+               "num_iterations": [s[k].num_iterations for k in ws], "termination": [s[k].termination for k in ws]}
+        if Wm[0].td is not None:
+            out["td"] = _padded([Wm[k].td for k in ws])
+    finally:
+        for bl, ini in zip(blocks, initial):
+            for a, a0 in zip(bl, ini):
+                np.copyto(a, a0)
+    J0, r0, x0, A, b, dims = [], [], [], [], [], []
+    for k in ps:
+        P = batch.prior(int(k))
+        d = P.export()
+        As, bs = P.schur()
+        J0.append(d["J0"]); r0.append(d["r0"]); x0.append(np.concatenate([np.atleast_1d(x) for x in d["x0"]]) if d["x0"] else np.zeros(0))
+        A.append(As); b.append(bs); dims.append((d["m"], d["n"]))
+    out.update(prior_window=ps, prior_dims=dims, prior_J0=_padded(J0), prior_r0=_padded(r0), prior_x0=_padded(x0), prior_A=_padded(A), prior_b=_padded(b))
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte bound")
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, (k if world == 1 else f"rank{rank}_{k}") + ".npy"), v)
 
 
 # ---- CPU baseline (the ONLY part of this file that touches oracle/) -------------------------------------------------------
@@ -524,7 +590,7 @@ def sweep_figures(tcv, keep, opts):
 # ---- modes ----------------------------------------------------------------------------------------------------------------
 def run_solve(args, rank, world, local, dist):
     pool = nproc = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not DRY:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not DRY:
         pool, nproc = cpu_pool()                     # forked before the first GPU call
     B = args.windows
     if DRY:
@@ -566,10 +632,13 @@ def run_solve(args, rank, world, local, dist):
     sync()
     solve_ms, marg_ms = [], []
     t0 = time.perf_counter()
-    sample_every = max(1, (args.steps + 63) // 64)      # HIP-event duration of the launches (events recorded on the launch stream): at most 64 samples
+    # --full: HIP-event duration of the launches (events recorded on the launch stream), at most 64 samples, each behind a synchronise
+    # that is inside the timed region (every step up to 64 steps) -- the --full line's value / ms_per_step include those waits; a plain
+    # run enqueues its steps back to back, so the two lines' headlines are not measured the same way
+    sample_every = max(1, (args.steps + 63) // 64) if args.full else 0
     for k in range(args.steps):
         step()
-        if not DRY and k % sample_every == 0:
+        if not DRY and sample_every and k % sample_every == 0:
             batch.synchronize()
             st = batch.stats(); solve_ms.append(st["solve_ms"]); marg_ms.append(st["marg_ms"])
     sync()
@@ -581,6 +650,8 @@ def run_solve(args, rank, world, local, dist):
         # parity of what was just timed is the job of tests/ and smoke(); here only sanity of the results
         s = batch.summaries(min(4, B))
         assert all(np.isfinite(s[k].final_cost) and s[k].final_cost < s[k].initial_cost for k in range(min(4, B)))
+        if args.dump_outputs:      # (the caller's blocks keep their initial states: the --full figures below solve them again)
+            dump_outputs(args.dump_outputs, batch, keep, rank, world)
 
     if rank != 0:
         return
@@ -608,6 +679,9 @@ def run_solve(args, rank, world, local, dist):
     if DRY:
         out["dry_run"] = True
         out["data"] = "dry run: no device work (launch / reduction logic only)"
+        print(json.dumps(out))
+        return
+    if not args.full:
         print(json.dumps(out))
         return
     w0 = wins[0]
@@ -795,7 +869,7 @@ def run_replay(args, rank, world, local, dist):
     if args.host_threads <= 0:
         args.host_threads = 4 if len(mine) >= 96 else 2
     pool = nproc = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not DRY:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not DRY:
         pool, nproc = cpu_pool()                     # forked before the first GPU call
     if DRY:
         dev = None
@@ -911,7 +985,7 @@ def run_replay(args, rank, world, local, dist):
 
 
 def replay_figures(tcv, local, streams=8, groups=2, steps=60, warmup=10):
-    """the replay number of the default line (one GPU): optimised windows per second of `streams` EuRoC-trajectory streams"""
+    """the replay number of the --full line (one GPU): optimised windows per second of `streams` EuRoC-trajectory streams"""
     import replay
     eng = ReplayEngine(tcv, replay, list(range(streams)), replay.WINDOW_SIZE + 1 + warmup + steps, 60, 8, groups, local)
     import torch
@@ -972,8 +1046,12 @@ def main():
     ap.add_argument("--windows", type=int, default=1024, help="independent windows per GPU per step")
     ap.add_argument("--threads", type=int, default=256)
     ap.add_argument("--variant", type=int, default=0, help="0: chain layout (default), 1: dense 171-dim layout (cross-check)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the PCIe-inclusive / single-window figures")
+    ap.add_argument("--full", action="store_true", help="also every figure beyond the headline line: kernel times and rooflines, CPU baselines, "
+                    "batch-size sweep, PCIe-inclusive / single-window / replay figures (a plain run prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="--mode solve: write what the timed path computed in its last step "
+                    "as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the batch sweep and the PCIe-inclusive / single-window / replay figures")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--streams", type=int, default=8, help="replay mode: number of EuRoC-trajectory streams of the whole job")
     ap.add_argument("--features", type=int, default=60)
@@ -983,6 +1061,8 @@ def main():
     args = ap.parse_args()
     if args.mode == "stream" and args.gpus > 1:
         raise SystemExit("--mode stream measures one GPU (host threads x HIP streams of one device): use --gpus 1")
+    if args.dump_outputs and args.mode != "solve":
+        raise SystemExit("--dump-outputs writes the outputs of --mode solve (the headline's timed path)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))       # nothing above touched the GPU

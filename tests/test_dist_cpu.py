@@ -89,14 +89,16 @@ def test_replay_shards_an_odd_stream_count_over_two_ranks():
 
 
 def test_default_line_key_set():
-    """the keys the default line promises beyond the contract's: present in the source of the line and, for the ones the dry
-    run can produce, on the dry line"""
-    rc, out, err = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--windows", "16"], {})
-    assert rc == 0, err[-3000:]
-    d = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
-    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
-              "ranks_seen", "per_rank_solves_per_s"):
-        assert k in d, k
+    """the keys the --full line promises beyond the contract's: present in the source of the line and, for the ones the dry
+    run can produce, on the dry line -- the plain one and the --full one"""
+    for extra in ([], ["--full"]):
+        rc, out, err = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--windows", "16"] + extra, {})
+        assert rc == 0, err[-3000:]
+        d = json.loads([l for l in out.splitlines() if l.startswith("{")][0])
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+                  "ranks_seen", "per_rank_solves_per_s"):
+            assert k in d, k
+        assert d["steps"] == 2
     src = open(os.path.join(ROOT, "bench.py")).read()
     for k in ("roofline_fp64", "batch_sweep", "run_to_convergence", "mfma_busy", "valu_active", "replay_cpu_baseline", "cpu_baseline", "traffic_commit",
               # round 6: the roofline on SURVEY 8(d)'s unit (iteration) with the per-linearisation figure beside it, executed flops from the counters,

@@ -188,7 +188,7 @@ def test_bench_cpu_leg_of_the_replay_mode_runs_the_same_streams():
     import bench
     n, t = bench._cpu_replay_worker((1, replay.WINDOW_SIZE + 1 + 10 + 100, 60, 8, 3.0))      # the default replay line: warm-up 10 + 100 steps
     assert n >= 3 and 0.0 < t < 3.5
-    # the default line's replay figure (10 + 60 frames) and a stream of the second lap over the sequences (start offset 3 s)
+    # the --full line's replay figure (10 + 60 frames) and a stream of the second lap over the sequences (start offset 3 s)
     n2, t2 = bench._cpu_replay_worker((6, replay.WINDOW_SIZE + 1 + 10 + 60, 60, 8, 1.0))
     assert n2 >= 1 and t2 > 0.0
 

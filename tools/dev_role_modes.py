@@ -23,7 +23,7 @@ subprocess.call([sys.executable, __file__, str(B), "--hist"], env=env)
 for rep in range(2):
     for mode in (0, 1, 2, 3, 4, 5, 6):
         env["TCV_ROLE_MODE"] = str(mode)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True)
         try:
             d = json.loads(r.stdout.strip().splitlines()[-1])
             print("TCV_ROLE_MODE=%d  solve %.3f ms  marg %.3f ms  %.1f K solves/s" % (mode, d["kernel_ms"]["solve"], d["kernel_ms"]["marginalize"], d["value"] / 1e3), flush=True)

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err
 rocprofv3 --kernel-trace --stats -d $O/stats -o st --output-format csv -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/stats.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch -o f --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/write -o w --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/write.log 2>&1
@@ -41,15 +41,15 @@ python3 tools/dev_small_batch.py 60 12 > $O/small_batch.txt 2>&1
 if [ -f tc-viml_amd/libtcv_hip_prof.so ]; then
   TCV_DEBUG=1 TCV_LIB=tc-viml_amd/libtcv_hip_prof.so python3 tools/dev_small_batch.py 60 3 > $O/small_batch_prof.txt 2>&1
 fi
-python3 bench.py --mode replay --steps 150 --warmup 10 > $O/bench_replay.json 2> /dev/null
-python3 bench.py --mode replay --steps 150 --warmup 10 --host-threads 1 > $O/bench_replay_1thread.json 2> /dev/null
+python3 bench.py --full --mode replay --steps 150 --warmup 10 > $O/bench_replay.json 2> /dev/null
+python3 bench.py --full --mode replay --steps 150 --warmup 10 --host-threads 1 > $O/bench_replay_1thread.json 2> /dev/null
 python3 bench.py --mode stream --windows 2048 > $O/bench_stream_2048.json 2> /dev/null
 python3 tools/replay_euroc.py --native --profile --frames 340 --out $O/euroc > $O/replay_euroc_native.json 2> /dev/null
 # round 3: A/B of the round's kernel changes on the final build (developer switches), the experiments of DESIGN 6b
 for spec in "default:" "round-2 eigenvalue search:TCV_MARG_EIG_FLAGS=1" "reflector-by-reflector back-transformation:TCV_MARG_EIG_FLAGS=2" "both round-2 eigen paths:TCV_MARG_EIG_FLAGS=3" "prior with its zero rows:TCV_PRIOR_FULL=1"; do
   name="${spec%%:*}"; var="${spec#*:}"
   for rep in 1 2; do
-    env $var python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%-45s solve %.3f ms  marginalisation %.3f ms  %.1f K solves/s' % ('$name', d['kernel_ms']['solve'], d['kernel_ms']['marginalize'], d['value'] / 1e3))"
+    env $var python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%-45s solve %.3f ms  marginalisation %.3f ms  %.1f K solves/s' % ('$name', d['kernel_ms']['solve'], d['kernel_ms']['marginalize'], d['value'] / 1e3))"
   done
 done > $O/kernel_ab.txt 2>&1
 find $O -name "*_kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv
@@ -72,7 +72,7 @@ def merged(*ds):
     return m
 out["latency"] = merged(summarise("lat_VmemLatency"), summarise("lat_LdsLatency"), summarise("lat_SmemLatency"))
 json.dump(out, open(f"{O}/sq_counters.json", "w"), indent=1)
-# the figures bench.py copies onto its default line (profiles/counters.json), with the commit they were taken at
+# the figures bench.py --full copies onto its line (profiles/counters.json), with the commit they were taken at
 import os
 def pick(d, pat):
     for k, v in d.items():

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06i; mkdir -p $O; cd $R
 for rep in 1 2 3; do
   for spec in "fused:" "separate kernel:TCV_BENCH_SEPARATE_GAUGE=1"; do
     name="${spec%%:*}"; var="${spec#*:}"
-    env $var python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%-18s step %.4f ms  solve %.3f ms  marginalisation %.3f ms  %.1f K solves/s' % ('$name', d['ms_per_step'], d['kernel_ms']['solve'], d['kernel_ms']['marginalize'], d['value'] / 1e3))"
+    env $var python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%-18s step %.4f ms  solve %.3f ms  marginalisation %.3f ms  %.1f K solves/s' % ('$name', d['ms_per_step'], d['kernel_ms']['solve'], d['kernel_ms']['marginalize'], d['value'] / 1e3))"
   done
 done > $O/gauge_ab.txt 2>&1
 for rep in 1 2; do
