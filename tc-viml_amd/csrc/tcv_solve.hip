@@ -54,7 +54,7 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 // are garbage, every step is forced to be accepted so that the control flow stays the benchmark's); the time difference to skip = 0
 // is what the phase really costs under the real overlap conditions -- no instrumentation in the timed code
 // (-DTCV_ABLATE_CONST=mask, round 6: the same mask as a COMPILE-TIME constant -- the removed phases' code and registers are really gone, which is
-// what a phase-split pipeline's kernels would look like to the register allocator: tools/r06_phase_split_bound.sh)
+// what a phase-split pipeline's kernels would look like to the register allocator: tools/dev_phase_split.py)
 #if defined(TCV_ABLATE_CONST)
 #define TCV_ABLATE 1
 #define ABL(C, bit) (!((unsigned)(TCV_ABLATE_CONST) & (1u << (bit))))
@@ -1408,12 +1408,10 @@ __device__ __forceinline__ void panel_tile_mfma(lds_d *T, const lds_d *TK, const
     for (int i = 0; i < 4; i++) r[i] = at[i];                        // A' in the accumulator layout (rows row0 + 4 i of column col) IS the B operand just loaded
 #pragma unroll
     for (int kk = 0; kk < 4; kk++) y1 = __builtin_amdgcn_mfma_f64_16x16x4f64(li[kk], at[kk], y1, 0, 0, 0);
-#ifndef TCV_PANEL_NOREFINE      // (A/B build `build.py --norefine`: the product with the explicit inverse alone, as up to round 5)
 #pragma unroll
     for (int kk = 0; kk < 4; kk++) r = __builtin_amdgcn_mfma_f64_16x16x4f64(ll[kk], y1[kk], r, 0, 0, 0);
 #pragma unroll
     for (int kk = 0; kk < 4; kk++) y1 = __builtin_amdgcn_mfma_f64_16x16x4f64(li[kk], r[kk], y1, 0, 0, 0);
-#endif
 #pragma unroll
     for (int i = 0; i < 4; i++) T[sw(col, row0 + 4 * i)] = y1[i];    // X = Y'
 }
@@ -2339,53 +2337,19 @@ __device__ __noinline__ void gauge_epilogue(lds_d *xs_, cst_d *x_init_, cst_i *f
 }
 
 template <int NT, bool MFMA, bool CHAIN, bool COOP = false, bool TD = !CHAIN>
-// (-DTCV_CHAIN_OCC1, developer build libtcv_hip_occ1.so: the chain kernel compiled for ONE wavefront per SIMD -- 512 registers, no spills -- to
-// measure what the 156 spilled registers of the production kernel cost at equal occupancy, profiles/r03_spill_ab.txt)
-// (-DTCV_CHAIN_OCC3, libtcv_hip_occ3.so: THREE wavefronts per SIMD -- 168 registers -- for the occupancy experiment of tools/dev_occupancy3.py)
-#if defined(TCV_CHAIN_OCC)      // (round 6: any occupancy, -DTCV_CHAIN_OCC=4 -> 128 registers)
+// (-DTCV_CHAIN_OCC=N, developer builds `build.py --suffix=occN -DTCV_CHAIN_OCC=N`: the chain kernel compiled for N wavefronts per SIMD -- 1: 512
+// registers, no spills, what the spilled registers of the production kernel cost at equal occupancy (profiles/r03_spill_ab.txt); 3: 168 registers,
+// the occupancy experiment of tools/dev_occupancy3.py; 4: 128 registers)
+#if defined(TCV_CHAIN_OCC)
 #define TCV_CHAIN_WAVES TCV_CHAIN_OCC
-#elif defined(TCV_CHAIN_OCC1)
-#define TCV_CHAIN_WAVES 1
-#elif defined(TCV_CHAIN_OCC3)
-#define TCV_CHAIN_WAVES 3
 #else
 #define TCV_CHAIN_WAVES 2
 #endif
 __global__ void __launch_bounds__(NT) __attribute__((disable_tail_calls)) __attribute__((amdgpu_waves_per_eu((CHAIN && !COOP) ? TCV_CHAIN_WAVES : 1, COOP ? 1 : (CHAIN ? TCV_CHAIN_WAVES : 8)))) solve_kernel(SolveArgs A) {
     extern __shared__ __attribute__((aligned(16))) double lds_raw[];
     lds_d *lds = (lds_d *)lds_raw;
-    int tid = threadIdx.x;
+    const int tid = threadIdx.x;
     int slot = blockIdx.x, wstride = gridDim.x;      // scratch slot and first window of this workgroup; window stride
-    if (CHAIN && !COOP && NT == 256 && A.role_mode != 0) {
-        // Role placement experiment.  The phases give the wavefronts different roles (wave 3: T pipeline, waves 0-1: column owners and the
-        // point factors, ...); two workgroups that share a CU and run in step put the same role on the same SIMD.  HW_ID: wave slot
-        // [3:0], SIMD [5:4], CU [11:8].
-        const unsigned hw = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-        const int simd = (int)(hw >> 4) & 3, wslot = (int)hw & 15, pw = tid >> 6;
-        lds_i *ex = (lds_i *)lds;
-        if ((tid & 63) == 0) { ex[pw] = simd; ex[4 + pw] = wslot; }
-        __syncthreads();
-        const int s0 = ex[0], s1 = ex[1], s2 = ex[2], s3 = ex[3], w0 = ex[4];
-        __syncthreads();
-        const bool perm = ((1 << s0) | (1 << s1) | (1 << s2) | (1 << s3)) == 15;
-        const int mode = A.role_mode & 15;
-        int lw = pw;
-        if (mode == 1) lw = (pw + 2 * (w0 & 1)) & 3;
-        else if (mode == 2) lw = (pw + 2 * (((int)blockIdx.x >> 8) & 1)) & 3;
-        else if (mode == 3 && perm) lw = (simd + 2 * (w0 & 1)) & 3;
-        else if (mode == 4 && perm) lw = simd;
-        else if (mode == 5) lw = (pw + (w0 & 1)) & 3;
-        else if (mode == 6 && perm) lw = (simd + (w0 & 3)) & 3;
-        if ((A.role_mode & 16) && A.prof && (tid & 63) == 0) {
-            gbl_d *pr = (gbl_d *)A.prof + (size_t)blockIdx.x * 32;
-            pr[pw * 4 + simd] += 1.0;
-            if (pw == 0) { pr[16 + (w0 & 7)] += 1.0; pr[24 + (perm ? 1 : 0)] += 1.0; }
-        }
-        tid = (tid & 63) | (__builtin_amdgcn_readfirstlane(lw) << 6);      // the wave index stays provably uniform
-        // de-phasing experiment (role_mode bit 5, count in bits 8..): the second workgroup of a CU starts late, so that the two do not walk
-        // through the same phases (and memory bursts) at the same time
-        if ((A.role_mode & 32) && (w0 & 1)) { const int nsl = __builtin_amdgcn_readfirstlane(A.role_mode >> 8); for (int k = 0; k < nsl; k++) __builtin_amdgcn_s_sleep(127); }
-    }
     if (COOP) {
         const int G8 = 8 * (1 + A.coop_h);      // workgroups of a block of eight groups: contiguous in dispatch order, one group per XCD
         const int blk8 = (int)blockIdx.x / G8, r8 = (int)blockIdx.x - blk8 * G8;

@@ -7,10 +7,10 @@ speed-bias chain), every workgroup limited to 53 KB (TCV_CHAIN_LDS_DOUBLES).  Th
 switches are read once per process):
 
     A  production build (2 wavefronts / SIMD, 256 registers), 2 workgroups per CU (grid 512)
-    B  -DTCV_CHAIN_OCC3 build (3 wavefronts / SIMD, 168 registers: build.py --occ3), 2 workgroups per CU  -> what the register diet costs
+    B  -DTCV_CHAIN_OCC=3 build (3 wavefronts / SIMD, 168 registers: libtcv_hip_occ3.so), 2 workgroups per CU -> what the register diet costs
     C  the same build, 3 workgroups per CU (grid 768)                                                        -> what the third workgroup buys
 
-    python tc-viml_amd/build.py --occ3 && python tools/dev_occupancy3.py [--frames 6] [--windows 1536]
+    python tc-viml_amd/build.py --suffix=occ3 -DTCV_CHAIN_OCC=3 && python tools/dev_occupancy3.py [--frames 6] [--windows 1536]
 """
 import os
 import subprocess
@@ -55,7 +55,7 @@ def main():
     lds = os.environ.get("OCC3_LDS_DOUBLES", "6784")      # 53 KB
     prod = os.path.join(ROOT, "tc-viml_amd", "libtcv_hip.so"); occ3 = os.path.join(ROOT, "tc-viml_amd", "libtcv_hip_occ3.so")
     if not os.path.exists(occ3):
-        raise SystemExit("build the three-wavefront variant first: python tc-viml_amd/build.py --occ3")
+        raise SystemExit("build the three-wavefront variant first: python tc-viml_amd/build.py --suffix=occ3 -DTCV_CHAIN_OCC=3")
     rows = []
     for name, lib, grid in (("A: 2 waves/SIMD build (256 VGPRs), 2 workgroups per CU", prod, 512), ("B: 3 waves/SIMD build (168 VGPRs), 2 workgroups per CU", occ3, 512),
                             ("C: 3 waves/SIMD build (168 VGPRs), 3 workgroups per CU", occ3, 768), ("D: 2 waves/SIMD build, grid 768 (the third workgroup waits for a free slot)", prod, 768)):

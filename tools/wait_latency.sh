@@ -3,6 +3,8 @@
 # and L2 hit rates of the solve kernel -- for the production launch shape and for the four configurations of the occupancy-3
 # experiment (tools/dev_occupancy3.py; profiles/r04_occupancy3.txt: why does a third workgroup slow its neighbours 1.72 x?).
 #   bash tools/wait_latency.sh [tag]   ->  gpurun_out/lat_<tag>/table.txt
+# needs the developer builds libtcv_hip_occ3.so and libtcv_hip_occ1.so:
+#   python tc-viml_amd/build.py --suffix=occ3 -DTCV_CHAIN_OCC=3 && python tc-viml_amd/build.py --suffix=occ1 -DTCV_CHAIN_OCC=1
 TAG=${1:-r06}
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/lat_$TAG
