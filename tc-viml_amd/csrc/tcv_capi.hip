@@ -167,10 +167,10 @@ ThreadStreams &thread_streams() { thread_local ThreadStreams mine; return mine; 
 // The list is bounded: a thread that pre-integrates and never creates a batch (or whose frames keep failing before tcv_batch_create) would
 // otherwise pin host and device memory until it ends -- at DEFER_MAX parked commands the stream is drained and its buffers released.
 enum { DEFER_MAX = 32 };
-void flush_deferred(hipStream_t st);
+hipError_t stream_wait(hipStream_t st) { return st ? hipStreamSynchronize(st) : hipDeviceSynchronize(); }
 void defer_release(void *host_staging, void *dev_buf, hipStream_t st) {
     std::vector<Deferred> &v = thread_streams().deferred;
-    if (v.size() >= DEFER_MAX) { (void)(st ? hipStreamSynchronize(st) : hipDeviceSynchronize()); flush_deferred(st); }
+    if (v.size() >= DEFER_MAX) { (void)stream_wait(st); flush_deferred(st); }
     v.push_back(Deferred{host_staging, dev_buf, st});
 }
 void flush_deferred(hipStream_t st) {
@@ -217,7 +217,7 @@ hipStream_t take_parked_stream(int dev) {
         }
     }
     for (auto &d : drain) {      // what a stream's previous thread left in flight has long finished, as a rule: wait (here a HIP call is fine) and release
-        (void)(d.first ? hipStreamSynchronize(d.first) : hipDeviceSynchronize());
+        (void)stream_wait(d.first);
         for (auto &x : d.second) { host_staging_release(x.h); (void)dev_free(x.d); }
     }
     return st;
@@ -247,7 +247,6 @@ hipStream_t aux_stream() {
     return st;
 }
 namespace { thread_local int g_stream_slot = 0; }
-hipStream_t aux_stream();
 hipStream_t util_stream() {
     if (g_stream_slot == 1) { const int keep = g_stream_slot; g_stream_slot = 0; hipStream_t a = aux_stream(); g_stream_slot = keep; return a; }      // (aux_stream asks for the main one once, to learn whether this is the main thread)
     ThreadStreams &mine = thread_streams();
@@ -357,6 +356,11 @@ static int ensure_block(tcv_problem *p, double *addr, int size) {
     if (tcv_problem_add_parameter_block(p, addr, size, TCV_PARAM_EUCLIDEAN) != TCV_OK) return -1;
     return block_of(p, addr);
 }
+// the four parameter blocks of a factor (added when unknown); false: a NULL address or a block of another size
+static bool bind_blocks(tcv_problem *p, double *const a[4], const int sz[4], int b[4]) {
+    for (int k = 0; k < 4; k++) if ((b[k] = a[k] ? ensure_block(p, a[k], sz[k]) : -1) < 0) return false;
+    return true;
+}
 extern "C" int tcv_problem_add_imu_factor(tcv_problem *p, const tcv_imu_preintegration *pre, double *pose_i, double *sb_i,
                                           double *pose_j, double *sb_j) {
     if (!p || !pre) return TCV_ERR_INVALID;
@@ -364,10 +368,7 @@ extern "C" int tcv_problem_add_imu_factor(tcv_problem *p, const tcv_imu_preinteg
     f.pre = *pre;
     double *a[4] = {pose_i, sb_i, pose_j, sb_j};
     const int sz[4] = {7, 9, 7, 9};
-    for (int k = 0; k < 4; k++) {
-        f.b[k] = a[k] ? ensure_block(p, a[k], sz[k]) : -1;
-        if (f.b[k] < 0) { set_error("add_imu_factor: bad parameter block"); return TCV_ERR_INVALID; }
-    }
+    if (!bind_blocks(p, a, sz, f.b)) { set_error("add_imu_factor: bad parameter block"); return TCV_ERR_INVALID; }
     p->imu.push_back(f);
     return TCV_OK;
 }
@@ -379,10 +380,7 @@ extern "C" int tcv_problem_add_imu_factor_device(tcv_problem *p, const tcv_prein
     f.dev = pre;
     double *a[4] = {pose_i, sb_i, pose_j, sb_j};
     const int sz[4] = {7, 9, 7, 9};
-    for (int k = 0; k < 4; k++) {
-        f.b[k] = a[k] ? ensure_block(p, a[k], sz[k]) : -1;
-        if (f.b[k] < 0) { set_error("add_imu_factor_device: bad parameter block"); return TCV_ERR_INVALID; }
-    }
+    if (!bind_blocks(p, a, sz, f.b)) { set_error("add_imu_factor_device: bad parameter block"); return TCV_ERR_INVALID; }
     p->imu.push_back(f);
     return TCV_OK;
 }
@@ -395,10 +393,7 @@ extern "C" int tcv_problem_add_projection_factor(tcv_problem *p, const double pt
     f.sqrt_info = sqrt_info; f.loss_a = loss_a;
     double *a[4] = {pose_i, pose_j, ex_pose, inv_depth};
     const int sz[4] = {7, 7, 7, 1};
-    for (int k = 0; k < 4; k++) {
-        f.b[k] = a[k] ? ensure_block(p, a[k], sz[k]) : -1;
-        if (f.b[k] < 0) { set_error("add_projection_factor: bad parameter block"); return TCV_ERR_INVALID; }
-    }
+    if (!bind_blocks(p, a, sz, f.b)) { set_error("add_projection_factor: bad parameter block"); return TCV_ERR_INVALID; }
     for (int i = 0; i < 8; i++) f.aux[i] = 0.0;
     f.btd = -1;
     p->proj.push_back(f);
@@ -513,6 +508,18 @@ extern "C" int tcv_problem_plan_ints(const tcv_problem *p, int *out, int cap, in
     return TCV_OK;
 }
 extern "C" int tcv_set_packer_reference(int on) { tcv::set_pack_reference(on); return TCV_OK; }
+// first failing window of a parallel packing pass, with the message of the thread that packed it (the message is thread-local)
+struct PackErrors {
+    std::vector<int> rcs, who;
+    std::vector<std::string> msgs;
+    PackErrors(int n, int nth) : rcs(n, TCV_OK), who(n, 0), msgs(nth) {}
+    void note(int w, int t, int rc) { rcs[w] = rc; who[w] = t; if (rc != TCV_OK && msgs[t].empty()) msgs[t] = tcv_last_error(); }
+    int first() const {      // TCV_OK, or that window's status with its message as the calling thread's error
+        for (size_t w = 0; w < rcs.size(); w++)
+            if (rcs[w] != TCV_OK) { if (!msgs[who[w]].empty()) set_error(msgs[who[w]]); return rcs[w]; }
+        return TCV_OK;
+    }
+};
 // the packing pass of tcv_batch_create (plans + data sizes of n problems on `threads` host threads of the library's worker pool) without
 // a device: seconds of wall time in *seconds
 extern "C" int tcv_problems_pack_bench(tcv_problem *const *problems, int n, int threads, int coop_chunks, double *seconds) {
@@ -521,23 +528,20 @@ extern "C" int tcv_problems_pack_bench(tcv_problem *const *problems, int n, int 
     // the life cycle of a lock-step frame's batch (the int pools come back from the block pool) instead of n plans alive at once
     int frame = n;
     if (const char *e = getenv("TCV_PACK_BENCH_FRAME")) { const int v = atoi(e); if (v > 0) frame = std::min(n, v); }
-    std::vector<int> rcs(n, TCV_OK);
-    std::vector<std::string> msgs(n);
+    PackErrors err(n, n);      // (the text is per thread: a worker's is carried over to the caller below)
     const auto t0 = std::chrono::steady_clock::now();
     for (int b = 0; b < n; b += frame) {
         const int m = std::min(frame, n - b), nth = std::max(1, std::min(threads, m));
         std::vector<Packed> packed(m);
         auto one = [&](int w) {
-            rcs[b + w] = pack_problem(*problems[b + w], packed[w], nullptr, g_solver_variant, coop_chunks > 0 ? (int)LDS_DOUBLES : 0, true, coop_chunks);
-            if (rcs[b + w] != TCV_OK) msgs[b + w] = tcv_last_error();      // (the text is per thread: a worker's is carried over to the caller below)
+            err.note(b + w, b + w, pack_problem(*problems[b + w], packed[w], nullptr, g_solver_variant, coop_chunks > 0 ? (int)LDS_DOUBLES : 0, true, coop_chunks));
         };
         if (getenv("TCV_PACK_BENCH_STRIDED")) tcv::parallel_run(nth, [&](int t) { for (int w = t; w < m; w += nth) one(w); });      // (a fixed share per thread: up to round 5)
         else tcv::parallel_items(m, nth, [&](int w, int) { one(w); });
     }
     *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (getenv("TCV_DEBUG_PACK2")) tcv::pack_laps_print();
-    for (int w = 0; w < n; w++) if (rcs[w] != TCV_OK) { set_error(msgs[w]); return rcs[w]; }
-    return TCV_OK;
+    return err.first();
 }
 extern "C" int tcv_plan_cache_stats(long long *out4) {
     if (!out4) return TCV_ERR_INVALID;
@@ -793,7 +797,272 @@ void host_staging_release(void *p) {
     }
     if (to_free) { g_host_frees++; (void)hipHostFree(to_free); }
 }
+StagedTransfer::~StagedTransfer() { if (in_flight) (void)stream_wait(st); host_staging_release(host); (void)dev_free(dev); }
+hipError_t StagedTransfer::wait() { const hipError_t e = stream_wait(st); if (e == hipSuccess) in_flight = false; return e; }
+void StagedTransfer::park() { defer_release(host, dev, st); host = dev = nullptr; in_flight = false; }
+int staged_download(void *dst, const void *d_src, size_t bytes, const char *what) {
+    StagedTransfer dl(util_stream(), bytes);
+    if (!dl.host) { set_error("hipHostMalloc (download staging) failed"); return TCV_ERR_HIP; }
+    hipError_t e = bytes ? hipMemcpyAsync(dl.host, d_src, bytes, hipMemcpyDeviceToHost, dl.st) : hipSuccess;
+    if (e == hipSuccess) { dl.issued(); e = dl.wait(); }
+    if (e != hipSuccess) return hip_fail(e, what);
+    std::memcpy(dst, dl.host, bytes);
+    return TCV_OK;
+}
 }  // namespace tcv
+
+// ---- tcv_batch_create, phase by phase ----------------------------------------------------------------------------------------
+// Cooperative mode (tcv_packed.h COOP_*): a chain-layout batch that leaves most of the chip idle gives every window 1 + H workgroups.
+// H: one helper per ~96 point / line factors of the largest window (`fmax` of them), as many as the CUs allow.  TCV_COOP_H overrides (0: off).
+static int coop_helper_count(int n, size_t fmax, int n_cu) {
+    const bool automatic = g_coop_helpers < 0 && !getenv("TCV_COOP_H");
+    int want = g_coop_helpers;
+    if (const char *eh = getenv("TCV_COOP_H")) want = atoi(eh);
+    if (want < 0) want = fmax >= 96 ? std::min<int>(COOP_MAX_H, std::max<int>(2, (int)((fmax + 95) / 96))) : 0;
+    want = std::min(want, (int)COOP_MAX_H);
+    while (want > 0 && (long long)((n + 7) / 8) * (1 + want) > n_cu / 8) want--;      // the groups of a launch are dealt round-robin to the XCDs: per XCD ceil(n / 8) groups on n_cu / 8 CUs
+    // A large batch seldom has the device to itself -- a lock-step replay drives it from two host threads, and a launch that fills the chip with
+    // helpers makes the other thread's launch queue behind it (64 streams: 10.8 K windows/s with seven helpers per window against 12.1 K with
+    // two; 128 streams: 15.5 K with three against 17.7 K with two; profiles/r05_replay_coop_helpers.txt).  From 24 windows on a launch takes
+    // half the chip -- three quarters if that is what two helpers per window need; TCV_COOP_H / tcv_set_cooperative still decide otherwise.
+    if (n >= 24 && automatic) {
+        int w2 = want;
+        while (w2 > 0 && (long long)n * (1 + w2) > n_cu / 2) w2--;
+        if (w2 < 2 && want >= 2 && (long long)n * 3 <= (long long)n_cu * 3 / 4) w2 = 2;
+        want = std::min(want, w2);
+    }
+    if (want == 1 && automatic) want = 0;      // a single helper is not worth the hand-offs
+    return want;
+}
+// (a plan out of the cache carries the hash of its template, computed once by the thread that built it)
+static unsigned long long plan_hash_of(const Packed &pk) { return pk.tmpl ? pk.tmpl->hash : tcv::plan_content_hash(pk.hdr, pk.ints); }
+// The plan and the data size of every window under the batch's policy: chain or dense layout (b->chain), LDS doubles of a chain-layout
+// workgroup (b->chain_lds), cooperative helpers per window (b->coop_h).  A fall-back rewrites the policy and packs the batch again.
+// packing (symbolic elimination, gather programs, data layout) is independent per window: host threads share the work
+static int pack_plans(tcv_batch *b, const tcv::HostOp &host_op) {
+    auto pack_all = [&]() -> int {
+        const int mode = b->chain ? 0 : 1;
+        const int nth = host_op.threads(std::min(b->n, 16));
+        PackErrors err(b->n, nth);
+        tcv::parallel_items(b->n, nth, [&](int w, int t) {
+            const int rc = pack_problem(*b->problems[w], b->packed[w], nullptr, mode, b->chain_lds, true, b->coop_h);      // plan + data size
+            err.note(w, t, rc);
+            // hash of the plan for the structure de-duplication below (a plan out of the cache is de-duplicated by its template: hashed
+            // there, once per template, not once per window)
+            if (rc == TCV_OK && !b->packed[w].tmpl && !b->packed[w].key_hashed) b->packed[w].plan_hash = plan_hash_of(b->packed[w]);
+        });
+        return err.first();
+    };
+    int rc = pack_all();
+    // a window that does not fit half a CU's LDS (more than ~280 landmarks: its vectors over the unknowns and the chain's working set leave no
+    // pool for the visual chunks) gives the WHOLE batch one workgroup per CU with all 160 KiB -- up to 1024 landmarks / 4096 point factors --
+    // instead of failing; such a batch runs at 1 / 1.7 of the two-per-CU rate
+    if (rc == TCV_ERR_TOO_LARGE && b->chain && b->chain_lds < (int)LDS_DOUBLES && !getenv("TCV_CHAIN_LDS_DOUBLES")) {
+        b->chain_lds = (int)LDS_DOUBLES;
+        rc = pack_all();
+    }
+    if (rc == TCV_OK && b->coop_h > 0)
+        for (int w = 0; w < b->n; w++) {      // what the cooperative master assumes: the prior staged in one piece, one IMU chunk
+            const PlanHdr &H = b->packed[w].hdr;
+            if (!H.chain || H.n_imu_chunk > 1 || H.camw != (int)CAM_W || (H.prior_n > 0 && H.prior_n * H.prior_n + 2 * H.prior_n > H.c_stage_cap)) {      // (the export layout of the helpers holds CAM_W-wide vectors)
+                b->coop_h = 0;
+                rc = pack_all();
+                break;
+            }
+        }
+    if (rc == TCV_OK && b->chain)
+        for (int w = 0; w < b->n; w++)
+            if (!b->packed[w].hdr.chain) {      // a window is not chain-eligible: the whole batch uses the dense layout
+                b->chain = false; b->coop_h = 0;
+                rc = pack_all();
+                break;
+            }
+    return rc;
+}
+// the distinct plans of the batch and what the windows' sizes add up to
+struct PlanSet {
+    std::vector<std::pair<const int *, size_t>> src;      // per device plan: its ints on the host
+    size_t ipool_size = 0, dtotal = 0;
+};
+// structure de-duplication (b->plans, b->plan_base, WinHdr::plan), the windows' offsets in the data pool (WinHdr::dbase) and what the
+// largest window asks of the batch (strides, LDS, spill and coupling stores)
+static void dedup_plans(tcv_batch *b, PlanSet &ps) {
+    std::unordered_map<unsigned long long, std::vector<int>> plan_by_hash;
+    std::map<const PlanTemplate *, int> plan_of_tmpl;   // windows that share a cached plan template share the device plan
+    for (int w = 0; w < b->n; w++) {
+        Packed &pk = b->packed[w];
+        const PlanInts &pints = pk.tmpl ? pk.tmpl->ints : pk.ints;
+        int pid = -1;
+        if (pk.tmpl) { auto it = plan_of_tmpl.find(pk.tmpl.get()); if (it != plan_of_tmpl.end()) pid = it->second; }
+        if (pid < 0) {
+            // equal plans share one device copy: candidates by hash (computed with the packing, in parallel), confirmed by comparison -- the
+            // replay's windows are all different (200 KB of plan each), the benchmark's all equal
+            if (pk.tmpl) pk.plan_hash = plan_hash_of(pk);
+            std::vector<int> &cands = plan_by_hash[pk.plan_hash];
+            for (int c : cands)
+                if (ps.src[c].second == pints.size() && std::memcmp(&b->plans[c], &pk.hdr, sizeof(PlanHdr)) == 0 &&
+                    std::memcmp(ps.src[c].first, pints.data(), sizeof(int) * pints.size()) == 0) { pid = c; break; }
+            if (pid < 0) {
+                pid = (int)b->plans.size();
+                cands.push_back(pid);
+                b->plans.push_back(pk.hdr);
+                b->plan_base.push_back((long long)ps.ipool_size);
+                ps.src.push_back({pints.data(), pints.size()});      // (stays valid: pk.ints / the template live until the copy into the staging buffer)
+                ps.ipool_size += pints.size();
+            }
+            if (pk.tmpl) plan_of_tmpl[pk.tmpl.get()] = pid;
+        }
+        pk.win.plan = pid;
+        pk.win.dbase = (long long)ps.dtotal;
+        ps.dtotal += (size_t)pk.win.n_doubles;
+        b->state_stride = std::max(b->state_stride, (pk.hdr.nx + pk.hdr.nland + 1) & ~1);
+        b->delta_stride = std::max(b->delta_stride, (pk.hdr.nc + pk.hdr.nland + 1) & ~1);
+        const int nt = pk.hdr.nt;
+        const size_t lds = b->chain ? (size_t)b->chain_lds * 8
+                                    : (size_t)(nt * (nt + 1) / 2 * 256 + 2 * ((pk.hdr.nx + pk.hdr.nland + 1) & ~1) + (3 * pk.hdr.camw + 176) + 64 + pk.hdr.lds_area) * 8;
+        b->lds_bytes = std::max(b->lds_bytes, lds);
+        b->spill_stride = std::max(b->spill_stride, pk.hdr.c_spill);
+        b->hcl_cap = std::max(b->hcl_cap, (pk.hdr.hcl_total + 63) & ~63);
+        b->input_bytes += 8.0 * pk.win.n_doubles;
+    }
+    b->plan_bytes = 4.0 * ps.ipool_size;
+}
+// ONE pinned staging buffer and ONE device blob for everything the kernels read: [data pool | window headers | plan headers | plan
+// offsets | plan ints | splice jobs], one asynchronous copy on the calling thread's own stream (five synchronous copies through the default
+// stream used to cost a lock-step frame more than its packing)
+// device-resident priors (tcv_batch_get_priors_device): nothing of them is packed or uploaded.  Their J0 | r0 | x0 regions live in a
+// device-only tail behind the uploaded blob (WinHdr::d_prior is relative to the window's slice and simply points there), filled by one
+// splice job per window on the upload's stream
+struct BlobLayout {
+    size_t o_win, o_plans, o_pbase, o_ipool, o_jobs, in_bytes, dev_bytes;      // byte offsets; uploaded bytes; with the device-only tail
+    size_t n_jobs = 0;
+    std::vector<int> splice_win, splice_imu_win;      // windows with a device-resident prior / with device-resident IMU factors
+    std::vector<long long> tail_off, tail_imu;        // their regions in the tail (doubles)
+};
+static BlobLayout blob_layout(const tcv_batch *b, const PlanSet &ps) {
+    const int n = b->n;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    BlobLayout L;
+    L.o_win = up16(sizeof(double) * std::max<size_t>(1, ps.dtotal)); L.o_plans = up16(L.o_win + sizeof(WinHdr) * (size_t)n);
+    L.o_pbase = up16(L.o_plans + sizeof(PlanHdr) * b->plans.size()); L.o_ipool = up16(L.o_pbase + sizeof(long long) * b->plan_base.size());
+    L.tail_off.assign(n, -1); L.tail_imu.assign(n, -1);
+    size_t tail_doubles = 0;
+    for (int w = 0; w < n; w++) {
+        if (b->packed[w].dev_prior_doubles > 0) { L.splice_win.push_back(w); L.tail_off[w] = (long long)tail_doubles; tail_doubles += ((size_t)b->packed[w].dev_prior_doubles + 1) & ~(size_t)1; L.n_jobs++; }
+        if (b->packed[w].dev_imu_doubles > 0) { L.splice_imu_win.push_back(w); L.tail_imu[w] = (long long)tail_doubles; tail_doubles += ((size_t)b->packed[w].dev_imu_doubles + 1) & ~(size_t)1; L.n_jobs += b->problems[w]->imu.size(); }
+    }
+    L.o_jobs = up16(L.o_ipool + sizeof(int) * std::max<size_t>(1, ps.ipool_size));
+    L.in_bytes = up16(L.o_jobs + sizeof(PriorSplice) * L.n_jobs);
+    L.dev_bytes = L.in_bytes + sizeof(double) * tail_doubles;
+    return L;
+}
+// data half: every window written straight into the pinned upload buffer, in parallel, and the plans' ints beside them; then the window
+// headers of the batch (b->wins)
+static int pack_data(tcv_batch *b, const tcv::HostOp &host_op, const PlanSet &ps, const BlobLayout &L, double *h_dpool) {
+    const int n = b->n, n_plans = (int)ps.src.size();
+    const int nth = host_op.threads(std::min(n, 16));
+    PackErrors err(n, nth);
+    tcv::parallel_items(n + n_plans, nth, [&](int i, int t) {
+        if (i < n_plans) {      // the plans straight into the upload buffer (the larger items first)
+            std::memcpy((char *)h_dpool + L.o_ipool + sizeof(int) * (size_t)b->plan_base[i], ps.src[i].first, sizeof(int) * ps.src[i].second);
+            return;
+        }
+        const int w = i - n_plans;
+        err.note(w, t, pack_problem_data(*b->problems[w], b->packed[w], nullptr, h_dpool + b->packed[w].win.dbase));
+    });
+    for (int w = 0; w < n; w++) { b->packed[w].ints.clear(); b->packed[w].ints.shrink_to_fit(); }
+    if (int rc = err.first()) return rc;
+    const long long tail = (long long)(L.in_bytes / sizeof(double));
+    // the prior region of the window: in the tail, addressed relative to the window's own slice; likewise the constants of its (device-resident) IMU factors
+    for (int w : L.splice_win) b->packed[w].win.d_prior = (int)(tail + L.tail_off[w] - b->packed[w].win.dbase);
+    for (int w : L.splice_imu_win) b->packed[w].win.d_imu = (int)(tail + L.tail_imu[w] - b->packed[w].win.dbase);
+    for (int w = 0; w < n; w++) b->wins.push_back(b->packed[w].win);
+    return TCV_OK;
+}
+// the launch shape of the solve: one workgroup per window, or the cooperative groups with the whole LDS each
+static void set_launch_shape(tcv_batch *b, int n_cu) {
+    const int n = b->n;
+    b->grid = std::min(n, n_cu * ((b->chain && b->chain_lds < (int)LDS_DOUBLES) ? 2 : 1));      // (two workgroups per CU only when each takes half its LDS)
+    if (const char *eg = getenv("TCV_GRID")) { const int g = atoi(eg); if (g > 0) b->grid = std::min(n, g); }      // tuning experiments
+    b->slots = b->grid;
+    if (b->coop_h > 0) {
+        b->coop_groups = std::min(n, 8 * std::max(1, (n_cu / 8) / (1 + b->coop_h)));      // whole groups per XCD
+        b->slots = b->coop_groups;
+        b->grid = (1 + b->coop_h) * ((b->coop_groups + 7) & ~7);
+        b->lds_bytes = (size_t)LDS_DOUBLES * 8;
+        int te_max = 0;
+        for (auto &H : b->plans) { b->coop_exp_chunks = std::max(b->coop_exp_chunks, H.n_vis_chunk); te_max = std::max(te_max, (H.nt_c * (H.nt_c + 1) / 2) << 8); }
+        b->coop_exp_stride = 2 * te_max + COOP_EXP_VEC;
+    }
+}
+// window headers, plan headers, plan offsets and the splice jobs into the upload buffer `hb` (the data pool and the plan ints are there)
+static void write_headers_and_jobs(const tcv_batch *b, const BlobLayout &L, char *hb) {
+    const std::vector<tcv_problem *> &problems = b->problems;
+    std::memcpy(hb + L.o_win, b->wins.data(), sizeof(WinHdr) * (size_t)b->n);
+    std::memcpy(hb + L.o_plans, b->plans.data(), sizeof(PlanHdr) * b->plans.size());
+    std::memcpy(hb + L.o_pbase, b->plan_base.data(), sizeof(long long) * b->plan_base.size());
+    PriorSplice *hj = (PriorSplice *)(hb + L.o_jobs);
+    for (size_t q = 0; q < L.splice_win.size(); q++) {
+        const int w = L.splice_win[q];
+        const tcv_prior *pr = problems[w]->prior[0].prior;
+        PriorSplice &J = hj[q];
+        std::memset(&J, 0, sizeof J);
+        J.src = pr->d_block; J.dst = b->packed[w].win.dbase + b->packed[w].win.d_prior;
+        J.n = pr->n; J.k0 = b->packed[w].win.prior_k0; J.nblk = (int)pr->size.size();
+        J.k0_src = b->packed[w].prior_k0_deferred ? pr->d_k0 : nullptr; J.win = w;
+        for (int k = 0; k < J.nblk; k++) { J.goff[k] = pr->x_goff[k]; J.size[k] = pr->size[k]; }
+    }
+    size_t q = L.splice_win.size();
+    for (int w : L.splice_imu_win)
+        for (size_t f = 0; f < problems[w]->imu.size(); f++, q++) {
+            PriorSplice &J = hj[q];
+            std::memset(&J, 0, sizeof J);
+            J.kind = 1; J.src = problems[w]->imu[f].dev->d_out;
+            J.dst = b->packed[w].win.dbase + b->packed[w].win.d_imu + (long long)f * IMU_CONST;
+        }
+}
+// the device blob, its upload from `up.host` and, behind it on the same stream, the splice of the device-resident inputs
+static int upload_and_splice(tcv_batch *b, const BlobLayout &L, tcv::StagedTransfer &up) {
+    const std::vector<tcv_problem *> &problems = b->problems;
+    hipError_t e_ = up.dev_alloc(L.dev_bytes);
+    if (e_ == hipSuccess) e_ = hipMemcpyAsync(up.dev, up.host, L.in_bytes, hipMemcpyHostToDevice, up.st);
+    if (e_ != hipSuccess) return hip_fail(e_, "upload of the batch");
+    char *db = (char *)up.dev;
+    b->d_dpool = (double *)db; b->d_win = (WinHdr *)(db + L.o_win); b->d_plans = (PlanHdr *)(db + L.o_plans);
+    b->d_plan_base = (long long *)(db + L.o_pbase); b->d_ipool = (int *)(db + L.o_ipool);
+    // the splice jobs (if any) behind the upload on its stream; a source whose producer did not wait for its kernel carries an event
+    for (int w : L.splice_imu_win)
+        for (size_t f = 0; f < problems[w]->imu.size(); f++)
+            if (const int rcw = problems[w]->imu[f].dev->dev->wait_ready(up.st)) return rcw;
+    for (int w : L.splice_win)
+        if (const int rcw = problems[w]->prior[0].prior->dev->wait_ready(up.st)) return rcw;
+    return tcv::launch_prior_splice((const PriorSplice *)(db + L.o_jobs), (int)L.n_jobs, b->d_dpool, (void *)b->d_win, up.st);
+}
+// a pooled device buffer of cnt (at least one) T
+template <class T> static hipError_t dev_array(T *&dst, size_t cnt) { return tcv::dev_malloc((void **)&dst, sizeof(T) * std::max<size_t>(1, cnt)); }
+// the buffers the kernels write; *zero_bytes: size of the block that starts as zeros (b->d_zero)
+static hipError_t alloc_work_buffers(tcv_batch *b, size_t *zero_bytes) {
+    const int n = b->n, scr = tcv_solve_scratch_doubles() + b->hcl_cap;
+    hipError_t e_ = dev_array(b->d_state, (size_t)n * b->state_stride);
+    if (e_ != hipSuccess) return e_;
+    // the four buffers that start as zeros share ONE allocation and one memset: four fill kernels of 4 - 5 us with their launch gaps sat between
+    // the upload and the frame's solve (a lock-step frame's GPU timeline, tools/gpu_calls.md#r05_gpu_z43: ~50 us of a 2.1 ms frame)
+    auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_delta = 0, o_scr = up256(o_delta + sizeof(double) * std::max<size_t>(1, (size_t)n * b->delta_stride));
+    const size_t o_sum = up256(o_scr + sizeof(double) * std::max<size_t>(1, (size_t)b->slots * scr));
+    const size_t o_prof = up256(o_sum + sizeof(DevSummary) * std::max<size_t>(1, (size_t)n));
+    *zero_bytes = up256(o_prof + sizeof(double) * std::max<size_t>(1, (size_t)32 * b->slots));
+    if ((e_ = tcv::dev_malloc(&b->d_zero, *zero_bytes)) != hipSuccess) return e_;
+    char *z = (char *)b->d_zero;
+    b->d_delta = (double *)(z + o_delta); b->d_scratch = (double *)(z + o_scr); b->d_summary = (DevSummary *)(z + o_sum); b->d_prof = (double *)(z + o_prof);
+    const bool coop = b->coop_h > 0;
+    if (b->chain) e_ = dev_array(b->d_imublk, (size_t)b->slots * 16 * IMU_BLK);
+    if (b->chain && e_ == hipSuccess) e_ = dev_array(b->d_spill, (size_t)b->slots * b->spill_stride);
+    if (coop && e_ == hipSuccess) e_ = dev_array(b->d_coop_ctl, (size_t)b->coop_groups * COOP_CTL_INTS);
+    if (coop && e_ == hipSuccess) e_ = dev_array(b->d_coop_x, (size_t)b->coop_groups * COOP_X_DOUBLES);
+    if (coop && e_ == hipSuccess) e_ = dev_array(b->d_coop_exp, (size_t)b->coop_groups * b->coop_exp_chunks * b->coop_exp_stride);
+    return e_;
+}
 
 extern "C" int tcv_batch_create(tcv_batch **out, tcv_problem *const *problems, tcv_problem *const *marg_problems,
                                 double *const *const *marg_drop, const int *marg_num_drop, int n) {
@@ -805,324 +1074,76 @@ extern "C" int tcv_batch_create(tcv_batch **out, tcv_problem *const *problems, t
     tcv::prior_refresh_switch();
     const tcv::HostOp host_op;      // host threads of this call: the granted cores shared with the batch-level calls running beside it
     tcv_batch *b = new tcv_batch();
+    std::unique_ptr<tcv_batch, void (*)(tcv_batch *)> owner(b, batch_free);      // every error exit frees the batch -- behind the upload guard's wait below
     b->n = n;
     b->problems.assign(problems, problems + n);
     b->packed.resize(n);
     { int cur = -1; if (hipGetDevice(&cur) != hipSuccess) cur = -1; for (auto &pk : b->packed) pk.batch_dev = cur; }
-    std::unordered_map<unsigned long long, std::vector<int>> plan_by_hash;   // structure de-duplication
-    std::vector<std::pair<const int *, size_t>> plan_src;                    // per device plan: its ints on the host
-    size_t ipool_size = 0;
-    int max_state = 0, max_nl = 0;
-    size_t max_lds = 0;
     int dev = 0, n_cu = 0;
     hipError_t e0 = hipGetDevice(&dev);
     if (e0 == hipSuccess) e0 = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e0 != hipSuccess) { batch_free(b); return hip_fail(e0, "hipDeviceGetAttribute"); }
+    if (e0 != hipSuccess) return hip_fail(e0, "hipDeviceGetAttribute");
     if (n_cu <= 0) n_cu = 256;
-    // chain layout: two workgroups share a CU's LDS when the batch is larger than the chip; a batch that leaves CUs idle anyway gives
-    // every workgroup the whole 160 KiB (fewer chunk passes over the visual factors, the prior's J0 staged in one piece)
-    int chain_lds = (n <= n_cu && !getenv("TCV_CHAIN_LDS_DOUBLES")) ? (int)LDS_DOUBLES : chain_lds_doubles();
-    b->chain_lds = chain_lds;
-    int mode = g_solver_variant;
+    b->n_cu = n_cu; b->coop_dev = dev;
     // the chain layout is used only if every window of the batch allows it: the packing pass below starts over with the dense layout
     // at the first window that does not
-    b->chain = (mode == 0);
-    // packing (symbolic elimination, gather programs, data layout) is independent per window: host threads share the work
-    // Cooperative mode (tcv_packed.h COOP_*): a chain-layout batch that leaves most of the chip idle gives every window 1 + H workgroups.
-    // H: one helper per ~96 point / line factors of the largest window, as many as the CUs allow.  TCV_COOP_H overrides (0: off).
-    int coop_h = 0;
-    if (mode == 0) {
-        int want = g_coop_helpers;
-        if (const char *eh = getenv("TCV_COOP_H")) want = atoi(eh);
-        size_t fmax = 0;
-        for (int w = 0; w < n; w++) fmax = std::max(fmax, problems[w]->proj.size() + problems[w]->line.size());
-        if (want < 0) want = fmax >= 96 ? std::min<int>(COOP_MAX_H, std::max<int>(2, (int)((fmax + 95) / 96))) : 0;
-        want = std::min(want, (int)COOP_MAX_H);
-        while (want > 0 && (long long)((n + 7) / 8) * (1 + want) > n_cu / 8) want--;      // the groups of a launch are dealt round-robin to the XCDs: per XCD ceil(n / 8) groups on n_cu / 8 CUs
-        // A large batch seldom has the device to itself -- a lock-step replay drives it from two host threads, and a launch that fills the chip with
-        // helpers makes the other thread's launch queue behind it (64 streams: 10.8 K windows/s with seven helpers per window against 12.1 K with
-        // two; 128 streams: 15.5 K with three against 17.7 K with two; profiles/r05_replay_coop_helpers.txt).  From 24 windows on a launch takes
-        // half the chip -- three quarters if that is what two helpers per window need; TCV_COOP_H / tcv_set_cooperative still decide otherwise.
-        if (n >= 24 && g_coop_helpers < 0 && !getenv("TCV_COOP_H")) {
-            int w2 = want;
-            while (w2 > 0 && (long long)n * (1 + w2) > n_cu / 2) w2--;
-            if (w2 < 2 && want >= 2 && (long long)n * 3 <= (long long)n_cu * 3 / 4) w2 = 2;
-            want = std::min(want, w2);
-        }
-        if (want == 1 && g_coop_helpers < 0 && !getenv("TCV_COOP_H")) want = 0;      // a single helper is not worth the hand-offs
-        coop_h = want;
-    }
-    // (a plan out of the cache carries the hash of its template, computed once by the thread that built it)
-    auto plan_hash_of = [](const Packed &pk) -> unsigned long long { return pk.tmpl ? pk.tmpl->hash : tcv::plan_content_hash(pk.hdr, pk.ints); };
-    auto pack_all = [&](int md, std::string &msg) -> int {
-        const int nth = host_op.threads(std::min(n, 16));
-        std::vector<int> rcs(n, TCV_OK);
-        std::vector<std::string> msgs(nth);
-        std::vector<int> who(n, 0);
-        tcv::parallel_items(n, nth, [&](int w, int t) {
-            rcs[w] = pack_problem(*problems[w], b->packed[w], nullptr, md, chain_lds, true, md == 0 ? coop_h : 0);      // plan + data size
-            who[w] = t;
-            if (rcs[w] != TCV_OK && msgs[t].empty()) msgs[t] = tcv_last_error();      // the message is thread-local
-            // hash of the plan for the structure de-duplication below (a plan out of the cache is de-duplicated by its template: hashed
-            // there, once per template, not once per window)
-            if (rcs[w] == TCV_OK && !b->packed[w].tmpl && !b->packed[w].key_hashed) b->packed[w].plan_hash = plan_hash_of(b->packed[w]);
-        });
-        for (int w = 0; w < n; w++) if (rcs[w] != TCV_OK) { msg = msgs[who[w]]; return rcs[w]; }
-        return TCV_OK;
-    };
-    {
-        std::string msg;
-        int rc = pack_all(mode, msg);
-        // a window that does not fit half a CU's LDS (more than ~280 landmarks: its vectors over the unknowns and the chain's working set leave no
-        // pool for the visual chunks) gives the WHOLE batch one workgroup per CU with all 160 KiB -- up to 1024 landmarks / 4096 point factors --
-        // instead of failing; such a batch runs at 1 / 1.7 of the two-per-CU rate
-        if (rc == TCV_ERR_TOO_LARGE && mode == 0 && chain_lds < (int)LDS_DOUBLES && !getenv("TCV_CHAIN_LDS_DOUBLES")) {
-            chain_lds = (int)LDS_DOUBLES; b->chain_lds = chain_lds;
-            msg.clear();
-            rc = pack_all(mode, msg);
-        }
-        if (rc == TCV_OK && mode == 0 && coop_h > 0)
-            for (int w = 0; w < n; w++) {      // what the cooperative master assumes: the prior staged in one piece, one IMU chunk
-                const PlanHdr &H = b->packed[w].hdr;
-                if (!H.chain || H.n_imu_chunk > 1 || H.camw != (int)CAM_W || (H.prior_n > 0 && H.prior_n * H.prior_n + 2 * H.prior_n > H.c_stage_cap)) {      // (the export layout of the helpers holds CAM_W-wide vectors)
-                    coop_h = 0;
-                    rc = pack_all(mode, msg);
-                    break;
-                }
-            }
-        if (rc == TCV_OK && mode == 0)
-            for (int w = 0; w < n; w++)
-                if (!b->packed[w].hdr.chain) {      // a window is not chain-eligible: the whole batch uses the dense layout
-                    mode = 1; b->chain = false; coop_h = 0;
-                    rc = pack_all(mode, msg);
-                    break;
-                }
-        if (rc != TCV_OK) { batch_free(b); if (!msg.empty()) set_error(msg); return rc; }
-    }
+    b->chain = g_solver_variant == 0;
+    // chain layout: two workgroups share a CU's LDS when the batch is larger than the chip; a batch that leaves CUs idle anyway gives
+    // every workgroup the whole 160 KiB (fewer chunk passes over the visual factors, the prior's J0 staged in one piece)
+    b->chain_lds = (n <= n_cu && !getenv("TCV_CHAIN_LDS_DOUBLES")) ? (int)LDS_DOUBLES : chain_lds_doubles();
+    size_t fmax = 0;
+    for (int w = 0; w < n; w++) fmax = std::max(fmax, problems[w]->proj.size() + problems[w]->line.size());
+    if (b->chain) b->coop_h = coop_helper_count(n, fmax, n_cu);
+    if (int rc = pack_plans(b, host_op)) return rc;
     const auto t_plans = std::chrono::steady_clock::now();
-    std::map<const PlanTemplate *, int> plan_of_tmpl;   // windows that share a cached plan template share the device plan
-    size_t dtotal = 0;
-    for (int w = 0; w < n; w++) {
-        Packed &pk = b->packed[w];
-        const PlanInts &pints = pk.tmpl ? pk.tmpl->ints : pk.ints;
-        int pid = -1;
-        if (pk.tmpl) { auto it = plan_of_tmpl.find(pk.tmpl.get()); if (it != plan_of_tmpl.end()) pid = it->second; }
-        if (pid < 0) {
-            // equal plans share one device copy: candidates by hash (computed with the packing, in parallel), confirmed by comparison -- the
-            // replay's windows are all different (200 KB of plan each), the benchmark's all equal
-            if (pk.tmpl) pk.plan_hash = plan_hash_of(pk);
-            std::vector<int> &cands = plan_by_hash[pk.plan_hash];
-            for (int c : cands)
-                if (plan_src[c].second == pints.size() && std::memcmp(&b->plans[c], &pk.hdr, sizeof(PlanHdr)) == 0 &&
-                    std::memcmp(plan_src[c].first, pints.data(), sizeof(int) * pints.size()) == 0) { pid = c; break; }
-            if (pid < 0) {
-                pid = (int)b->plans.size();
-                cands.push_back(pid);
-                b->plans.push_back(pk.hdr);
-                b->plan_base.push_back((long long)ipool_size);
-                plan_src.push_back({pints.data(), pints.size()});      // (stays valid: pk.ints / the template live until the copy into the staging buffer)
-                ipool_size += pints.size();
-            }
-            if (pk.tmpl) plan_of_tmpl[pk.tmpl.get()] = pid;
-        }
-        pk.win.plan = pid;
-        pk.win.dbase = (long long)dtotal;
-        dtotal += (size_t)pk.win.n_doubles;
-        max_state = std::max(max_state, pk.hdr.nx + pk.hdr.nland);
-        max_nl = std::max(max_nl, pk.hdr.nc + pk.hdr.nland);
-        const int nt = pk.hdr.nt;
-        const size_t lds = b->chain ? (size_t)chain_lds * 8
-                                    : (size_t)(nt * (nt + 1) / 2 * 256 + 2 * ((pk.hdr.nx + pk.hdr.nland + 1) & ~1) + (3 * pk.hdr.camw + 176) + 64 + pk.hdr.lds_area) * 8;
-        max_lds = std::max(max_lds, lds);
-        b->spill_stride = std::max(b->spill_stride, pk.hdr.c_spill);
-        b->hcl_cap = std::max(b->hcl_cap, (pk.hdr.hcl_total + 63) & ~63);
-        b->input_bytes += 8.0 * pk.win.n_doubles;
-    }
-    // data half: every window written straight into one pinned upload buffer, in parallel
-    // ONE pinned staging buffer and ONE device blob for everything the kernels read: [data pool | window headers | plan headers | plan
-    // offsets | plan ints], one asynchronous copy on the calling thread's own stream (five synchronous copies through the default stream
-    // used to cost a lock-step frame more than its packing)
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_win = up16(sizeof(double) * std::max<size_t>(1, dtotal)), o_plans = up16(o_win + sizeof(WinHdr) * (size_t)n);
-    const size_t o_pbase = up16(o_plans + sizeof(PlanHdr) * b->plans.size()), o_ipool = up16(o_pbase + sizeof(long long) * b->plan_base.size());
-    // device-resident priors (tcv_batch_get_priors_device): nothing of them is packed or uploaded.  Their J0 | r0 | x0 regions live in a
-    // device-only tail behind the uploaded blob (WinHdr::d_prior is relative to the window's slice and simply points there), filled by one
-    // splice job per window on the upload's stream
-    std::vector<int> splice_win, splice_imu_win;
-    std::vector<long long> tail_off(n, -1), tail_imu(n, -1);
-    size_t tail_doubles = 0, n_jobs = 0;
-    for (int w = 0; w < n; w++) {
-        if (b->packed[w].dev_prior_doubles > 0) { splice_win.push_back(w); tail_off[w] = (long long)tail_doubles; tail_doubles += ((size_t)b->packed[w].dev_prior_doubles + 1) & ~(size_t)1; n_jobs++; }
-        if (b->packed[w].dev_imu_doubles > 0) { splice_imu_win.push_back(w); tail_imu[w] = (long long)tail_doubles; tail_doubles += ((size_t)b->packed[w].dev_imu_doubles + 1) & ~(size_t)1; n_jobs += problems[w]->imu.size(); }
-    }
-    const size_t o_jobs = up16(o_ipool + sizeof(int) * std::max<size_t>(1, ipool_size));
-    const size_t in_bytes = up16(o_jobs + sizeof(PriorSplice) * n_jobs);
-    const size_t dev_bytes = in_bytes + sizeof(double) * tail_doubles;
-    if ((in_bytes + sizeof(double) * tail_doubles) / sizeof(double) >= ((size_t)1 << 31)) { batch_free(b); set_error("batch too large (data pool offsets are 32-bit)"); return TCV_ERR_TOO_LARGE; }
-    double *h_dpool = (double *)host_staging_acquire(in_bytes);
-    if (!h_dpool) { batch_free(b); set_error("hipHostMalloc (upload staging) failed"); return TCV_ERR_HIP; }
-    const auto t_dedup = std::chrono::steady_clock::now();
-    {
-        const int nth = host_op.threads(std::min(n, 16));
-        std::vector<int> rcs(n, TCV_OK);
-        std::vector<std::string> msgs(nth);
-        std::vector<int> who(n, 0);
-        const int n_plans = (int)plan_src.size();
-        tcv::parallel_items(n + n_plans, nth, [&](int i, int t) {
-            if (i < n_plans) {      // the plans straight into the upload buffer (the larger items first)
-                std::memcpy((char *)h_dpool + o_ipool + sizeof(int) * (size_t)b->plan_base[i], plan_src[i].first, sizeof(int) * plan_src[i].second);
-                return;
-            }
-            const int w = i - n_plans;
-            rcs[w] = pack_problem_data(*problems[w], b->packed[w], nullptr, h_dpool + b->packed[w].win.dbase);
-            who[w] = t;
-            if (rcs[w] != TCV_OK && msgs[t].empty()) msgs[t] = tcv_last_error();
-        });
-        for (int w = 0; w < n; w++) { b->packed[w].ints.clear(); b->packed[w].ints.shrink_to_fit(); }
-        for (int w = 0; w < n; w++) if (rcs[w] != TCV_OK) { host_staging_release(h_dpool); batch_free(b); if (!msgs[who[w]].empty()) set_error(msgs[who[w]]); return rcs[w]; }
-        for (int w : splice_win) {      // the prior region of the window: in the tail, addressed relative to the window's own slice
-            Packed &pk = b->packed[w];
-            pk.win.d_prior = (int)((long long)(in_bytes / sizeof(double)) + tail_off[w] - pk.win.dbase);
-        }
-        for (int w : splice_imu_win) {  // likewise the constants of its (device-resident) IMU factors
-            Packed &pk = b->packed[w];
-            pk.win.d_imu = (int)((long long)(in_bytes / sizeof(double)) + tail_imu[w] - pk.win.dbase);
-        }
-        for (int w = 0; w < n; w++) b->wins.push_back(b->packed[w].win);
-    }
-    const auto t_packed = std::chrono::steady_clock::now();
-    b->plan_bytes = 4.0 * ipool_size;
-    b->state_stride = (max_state + 1) & ~1;
-    b->delta_stride = (max_nl + 1) & ~1;
-    b->lds_bytes = max_lds;
-    b->grid = std::min(n, n_cu * ((b->chain && chain_lds < (int)LDS_DOUBLES) ? 2 : 1));      // (two workgroups per CU only when each takes half its LDS)
-    if (const char *eg = getenv("TCV_GRID")) { const int g = atoi(eg); if (g > 0) b->grid = std::min(n, g); }      // tuning experiments
-    b->slots = b->grid;
-    b->n_cu = n_cu; b->coop_dev = dev;
-    if (b->chain && coop_h > 0) {
-        b->coop_h = coop_h;
-        b->coop_groups = std::min(n, 8 * std::max(1, (n_cu / 8) / (1 + coop_h)));      // whole groups per XCD
-        b->slots = b->coop_groups;
-        b->grid = (1 + coop_h) * ((b->coop_groups + 7) & ~7);
-        b->lds_bytes = (size_t)LDS_DOUBLES * 8;
-        int te_max = 0;
-        for (auto &H : b->plans) { b->coop_exp_chunks = std::max(b->coop_exp_chunks, H.n_vis_chunk); te_max = std::max(te_max, (H.nt_c * (H.nt_c + 1) / 2) << 8); }
-        b->coop_exp_stride = 2 * te_max + COOP_EXP_VEC;
-    }
-    const int scr = tcv_solve_scratch_doubles() + b->hcl_cap;
+    PlanSet ps;
+    dedup_plans(b, ps);
+    const BlobLayout L = blob_layout(b, ps);
+    if (L.dev_bytes / sizeof(double) >= ((size_t)1 << 31)) { set_error("batch too large (data pool offsets are 32-bit)"); return TCV_ERR_TOO_LARGE; }
     hipStream_t ust = tcv::util_stream();
-    // error exits from here on: the asynchronous upload below may still be reading the pinned staging buffer and writing the device blob --
-    // both go back to pools another host thread takes from -- so the stream is drained before anything is released
-    auto bail = [&]() { (void)(ust ? hipStreamSynchronize(ust) : hipDeviceSynchronize()); host_staging_release(h_dpool); h_dpool = nullptr; batch_free(b); };
-#define UP(dst, src, T, cnt)                                                                          \
-    do {                                                                                              \
-        hipError_t e_ = tcv::dev_malloc((void **)&dst, sizeof(T) * std::max<size_t>(1, (cnt)));             \
-        if (e_ != hipSuccess) { bail(); return hip_fail(e_, "hipMalloc"); }                    \
-        if (src) {                                                                                    \
-            e_ = hipMemcpy(dst, src, sizeof(T) * (cnt), hipMemcpyHostToDevice);                       \
-            if (e_ != hipSuccess) { bail(); return hip_fail(e_, "hipMemcpy H2D"); }            \
-        }                                                                                             \
-    } while (0)
-    auto t_marg = t_packed, t_issue = t_packed, t_alloc = t_packed;
-    if (marg_problems) {      // the marginalisation problems first: which IMU factor's sqrt_info the solve exports is part of the window headers
-        hipError_t e_ = tcv::dev_malloc((void **)&b->d_sqrt_out, sizeof(double) * (size_t)n * 225);
-        if (e_ != hipSuccess) { bail(); return hip_fail(e_, "hipMalloc"); }
-        const int rc = tcv_marg_attach(b, marg_problems, marg_drop, marg_num_drop);
-        if (rc != TCV_OK) { bail(); return rc; }
-        for (int w = 0; w < n; w++) b->wins[w].sqrt_export = tcv_marg_sqrt_source(b, w);
-    }
-    t_marg = std::chrono::steady_clock::now();
+    auto t_dedup = t_plans, t_packed = t_plans, t_marg = t_plans, t_issue = t_plans, t_alloc = t_plans;
     {
-        char *hb = (char *)h_dpool;
-        std::memcpy(hb + o_win, b->wins.data(), sizeof(WinHdr) * (size_t)n);
-        std::memcpy(hb + o_plans, b->plans.data(), sizeof(PlanHdr) * b->plans.size());
-        std::memcpy(hb + o_pbase, b->plan_base.data(), sizeof(long long) * b->plan_base.size());
-        PriorSplice *hj = (PriorSplice *)(hb + o_jobs);
-        for (size_t q = 0; q < splice_win.size(); q++) {
-            const int w = splice_win[q];
-            const tcv_prior *pr = problems[w]->prior[0].prior;
-            PriorSplice &J = hj[q];
-            std::memset(&J, 0, sizeof J);
-            J.src = pr->d_block; J.dst = b->packed[w].win.dbase + b->packed[w].win.d_prior;
-            J.n = pr->n; J.k0 = b->packed[w].win.prior_k0; J.nblk = (int)pr->size.size();
-            J.k0_src = b->packed[w].prior_k0_deferred ? pr->d_k0 : nullptr; J.win = w;
-            for (int k = 0; k < J.nblk; k++) { J.goff[k] = pr->x_goff[k]; J.size[k] = pr->size[k]; }
+        tcv::StagedTransfer up(ust, L.in_bytes);      // the pinned upload buffer; the device blob until the batch takes it over
+        if (!up.host) { set_error("hipHostMalloc (upload staging) failed"); return TCV_ERR_HIP; }
+        t_dedup = std::chrono::steady_clock::now();
+        if (int rc = pack_data(b, host_op, ps, L, (double *)up.host)) return rc;
+        t_packed = std::chrono::steady_clock::now();
+        set_launch_shape(b, n_cu);
+        // error exits from here on wait for the stream: tcv_marg_attach and the upload below put commands on it, and the asynchronous upload
+        // may still be reading the pinned staging buffer and writing the device blob -- both go back to pools another host thread takes from
+        up.issued();
+        if (marg_problems) {      // the marginalisation problems first: which IMU factor's sqrt_info the solve exports is part of the window headers
+            hipError_t e_ = tcv::dev_malloc((void **)&b->d_sqrt_out, sizeof(double) * (size_t)n * 225);
+            if (e_ != hipSuccess) return hip_fail(e_, "hipMalloc");
+            if (int rc = tcv_marg_attach(b, marg_problems, marg_drop, marg_num_drop)) return rc;
+            for (int w = 0; w < n; w++) b->wins[w].sqrt_export = tcv_marg_sqrt_source(b, w);
         }
-        {
-            size_t q = splice_win.size();
-            for (int w : splice_imu_win)
-                for (size_t f = 0; f < problems[w]->imu.size(); f++, q++) {
-                    PriorSplice &J = hj[q];
-                    std::memset(&J, 0, sizeof J);
-                    J.kind = 1; J.src = problems[w]->imu[f].dev->d_out;
-                    J.dst = b->packed[w].win.dbase + b->packed[w].win.d_imu + (long long)f * IMU_CONST;
-                }
-        }
-        hipError_t e_ = tcv::dev_malloc(&b->d_input, dev_bytes);
-        if (e_ == hipSuccess) e_ = hipMemcpyAsync(b->d_input, hb, in_bytes, hipMemcpyHostToDevice, ust);
-        if (e_ != hipSuccess) { bail(); return hip_fail(e_, "upload of the batch"); }
-        char *db = (char *)b->d_input;
-        b->d_dpool = (double *)db; b->d_win = (WinHdr *)(db + o_win); b->d_plans = (PlanHdr *)(db + o_plans);
-        b->d_plan_base = (long long *)(db + o_pbase); b->d_ipool = (int *)(db + o_ipool);
-        if (n_jobs > 0) {      // behind the upload on its stream; a source whose producer did not wait for its kernel carries an event
-            for (int w : splice_imu_win)
-                for (size_t f = 0; f < problems[w]->imu.size(); f++)
-                    if (const int rcw = problems[w]->imu[f].dev->dev->wait_ready(ust)) { bail(); return rcw; }
-            for (int w : splice_win)
-                if (const int rcw = problems[w]->prior[0].prior->dev->wait_ready(ust)) { bail(); return rcw; }
-            const int rcs = tcv::launch_prior_splice((const PriorSplice *)(db + o_jobs), (int)n_jobs, b->d_dpool, (void *)b->d_win, ust);
-            if (rcs != TCV_OK) { bail(); return rcs; }
-        }
-    }
-    t_issue = std::chrono::steady_clock::now();
-    UP(b->d_state, (double *)nullptr, double, (size_t)n * b->state_stride);
-    // the four buffers that start as zeros share ONE allocation and one memset: four fill kernels of 4 - 5 us with their launch gaps sat between
-    // the upload and the frame's solve (a lock-step frame's GPU timeline, tools/gpu_calls.md#r05_gpu_z43: ~50 us of a 2.1 ms frame)
-    size_t zero_bytes = 0;
-    {
-        auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t o_delta = 0, o_scr = up256(o_delta + sizeof(double) * std::max<size_t>(1, (size_t)n * b->delta_stride));
-        const size_t o_sum = up256(o_scr + sizeof(double) * std::max<size_t>(1, (size_t)b->slots * scr));
-        const size_t o_prof = up256(o_sum + sizeof(DevSummary) * std::max<size_t>(1, (size_t)n));
-        zero_bytes = up256(o_prof + sizeof(double) * std::max<size_t>(1, (size_t)32 * b->slots));
-        hipError_t e_ = tcv::dev_malloc(&b->d_zero, zero_bytes);
-        if (e_ != hipSuccess) { bail(); return hip_fail(e_, "hipMalloc"); }
-        char *z = (char *)b->d_zero;
-        b->d_delta = (double *)(z + o_delta); b->d_scratch = (double *)(z + o_scr); b->d_summary = (DevSummary *)(z + o_sum); b->d_prof = (double *)(z + o_prof);
-    }
-    if (b->chain) {
-        UP(b->d_imublk, (double *)nullptr, double, (size_t)b->slots * 16 * IMU_BLK);
-        UP(b->d_spill, (double *)nullptr, double, (size_t)b->slots * b->spill_stride);
-    }
-    if (b->coop_h > 0) {
-        UP(b->d_coop_ctl, (int *)nullptr, int, (size_t)b->coop_groups * COOP_CTL_INTS);
-        UP(b->d_coop_x, (double *)nullptr, double, (size_t)b->coop_groups * COOP_X_DOUBLES);
-        UP(b->d_coop_exp, (double *)nullptr, double, (size_t)b->coop_groups * b->coop_exp_chunks * b->coop_exp_stride);
-    }
-#undef UP
-    t_alloc = std::chrono::steady_clock::now();
-    e0 = hipMemsetAsync(b->d_zero, 0, zero_bytes, ust);
-    {      // the batch is complete on the device before any stream uses it (and the upload is drained before its staging buffer is released, whatever the memsets returned)
-        const hipError_t es = ust ? hipStreamSynchronize(ust) : hipDeviceSynchronize();
+        t_marg = std::chrono::steady_clock::now();
+        write_headers_and_jobs(b, L, (char *)up.host);
+        if (int rc = upload_and_splice(b, L, up)) return rc;
+        t_issue = std::chrono::steady_clock::now();
+        size_t zero_bytes = 0;
+        if ((e0 = alloc_work_buffers(b, &zero_bytes)) != hipSuccess) return hip_fail(e0, "hipMalloc");
+        t_alloc = std::chrono::steady_clock::now();
+        e0 = hipMemsetAsync(b->d_zero, 0, zero_bytes, ust);
+        // the batch is complete on the device before any stream uses it (and the upload is drained before its staging buffer is released, whatever the memsets returned)
+        const hipError_t es = up.wait();
         if (e0 == hipSuccess) e0 = es;
+        b->d_input = up.take_dev();      // (d_dpool, d_win, d_plans, d_plan_base, d_ipool point into it)
     }
-    host_staging_release(h_dpool);
-    h_dpool = nullptr;
     tcv::flush_deferred(ust);      // (this thread just waited for its stream)
-    if (e0 != hipSuccess) { batch_free(b); return hip_fail(e0, "upload of the batch"); }
+    if (e0 != hipSuccess) return hip_fail(e0, "upload of the batch");
     e0 = hipEventCreate(&b->ev0);
     if (e0 == hipSuccess) e0 = hipEventCreate(&b->ev1);
-    if (e0 != hipSuccess) { batch_free(b); return hip_fail(e0, "hipEventCreate"); }
+    if (e0 != hipSuccess) return hip_fail(e0, "hipEventCreate");
     const auto t_up = std::chrono::steady_clock::now();
     if (getenv("TCV_DEBUG_PACK")) {
-        const auto t_end = std::chrono::steady_clock::now();
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point c) { return std::chrono::duration<double, std::milli>(c - a).count(); };
         fprintf(stderr, "[batch_create] n %d: plans %.3f ms, plan pool + staging %.3f ms, data %.3f ms\n", n, ms(t_begin, t_plans), ms(t_plans, t_dedup), ms(t_dedup, t_packed));
         fprintf(stderr, "[batch_create] n %d: pack %.3f ms, marg attach %.3f ms, blob + upload issue + splice %.3f ms, allocations %.3f ms, memsets + sync %.3f ms (%d splice jobs, %.1f KB up)\n", n,
-                ms(t_begin, t_packed), ms(t_packed, t_marg), ms(t_marg, t_issue), ms(t_issue, t_alloc), ms(t_alloc, t_up), (int)n_jobs, in_bytes / 1024.0);
-        (void)t_end;
+                ms(t_begin, t_packed), ms(t_packed, t_marg), ms(t_marg, t_issue), ms(t_issue, t_alloc), ms(t_alloc, t_up), (int)L.n_jobs, L.in_bytes / 1024.0);
     }
-    *out = b;
+    *out = owner.release();
     return TCV_OK;
 }
 // The marginalisation problems of a batch that was created without them: their packing and upload can then run while the batch's solve
@@ -1163,6 +1184,12 @@ int tcv_batch_enter_stream(tcv_batch *b, void *hip_stream) {
     return TCV_OK;
 }
 
+static int wall_clock_khz() {
+    int dev = 0, khz = 0;
+    hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;      // 100 MHz on CDNA
+    return khz;
+}
 extern "C" int tcv_batch_solve(tcv_batch *b, const tcv_solver_options *o, void *hip_stream) {
     if (!b || !o) return TCV_ERR_INVALID;
     if (hip_stream == TCV_STREAM_THREAD) hip_stream = (void *)tcv::util_stream();
@@ -1187,22 +1214,18 @@ extern "C" int tcv_batch_solve(tcv_batch *b, const tcv_solver_options *o, void *
     bool coop = b->coop_h > 0 && o->workgroups_per_window != 1;
     if (coop && b->coop_claim == 0)      // (a claim still held: the previous cooperative solve of this batch, same stream order, same rotation)
         if (!coop_admit(b, b->coop_groups, 1 + b->coop_h)) coop = false;      // the XCDs are taken by other cooperative launches: the same plan on one workgroup per window, the same bits
+    const bool timed = o->max_solver_time_in_seconds > 0.0 && !o->fixed_iterations;
+    const int khz = (coop || timed) ? wall_clock_khz() : 0;      // the cooperative time-out and the solver's time budget count its ticks
     int grid = b->grid;
     b->last_wg = coop ? 1 + b->coop_h : 1;
     if (coop) {
         a.coop_h = b->coop_h; a.coop_groups = b->coop_groups; a.coop_exp_chunks = b->coop_exp_chunks; a.coop_exp_stride = b->coop_exp_stride;
         a.coop_ctl = b->d_coop_ctl; a.coop_x = b->d_coop_x; a.coop_exp = b->d_coop_exp; a.coop_rot = b->coop_rot;
-        int dev = 0, khz = 0;
-        hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;
         a.coop_timeout = (long long)khz * 2000;      // 2 s
     } else if (b->coop_h > 0) grid = b->slots;
     b->sqrt_out_valid = b->d_sqrt_out != nullptr;
     if (const char *sk = getenv("TCV_ABLATE_SKIP")) a.pad2 = (int)(unsigned)strtoul(sk, nullptr, 0);      // -DTCV_ABLATE builds only read it
-    if (o->max_solver_time_in_seconds > 0.0 && !o->fixed_iterations) {
-        int dev = 0, khz = 0;
-        hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;      // 100 MHz on CDNA
+    if (timed) {
         a.max_ticks = (long long)(o->max_solver_time_in_seconds * 1e3 * (double)khz);
         if (a.max_ticks < 1) a.max_ticks = 1;
     }
@@ -1237,21 +1260,8 @@ extern "C" int tcv_batch_synchronize(tcv_batch *b) {
     tcv_marg_elapsed(b);
     return TCV_OK;
 }
-extern "C" int tcv_batch_download_states(tcv_batch *b) {
-    if (!b || !b->solved) return TCV_ERR_INVALID;
-    if (b->pending) if (int rc = tcv_batch_synchronize(b)) return rc;
-    b->h_state.resize((size_t)b->n * b->state_stride);
-    {      // through pinned staging on the calling thread's own stream (the default stream serialises the host threads of a process)
-        const size_t bytes = sizeof(double) * b->h_state.size();
-        void *hs = host_staging_acquire(bytes);
-        if (!hs) { set_error("hipHostMalloc (download staging) failed"); return TCV_ERR_HIP; }
-        hipStream_t ust = tcv::util_stream();
-        hipError_t e_ = hipMemcpyAsync(hs, b->d_state, bytes, hipMemcpyDeviceToHost, ust);
-        if (e_ == hipSuccess) e_ = ust ? hipStreamSynchronize(ust) : hipDeviceSynchronize();
-        if (e_ == hipSuccess) std::memcpy(b->h_state.data(), hs, bytes);
-        host_staging_release(hs);
-        if (e_ != hipSuccess) return hip_fail(e_, "download of the states");
-    }
+// the solved states (tcv_batch::h_state) into the callers' parameter blocks: camera blocks in plan order, then the inverse depths
+static void scatter_states(const tcv_batch *b) {
     for (int w = 0; w < b->n; w++) {
         const Packed &pk = b->packed[w];
         const tcv_problem &p = *b->problems[w];
@@ -1260,6 +1270,13 @@ extern "C" int tcv_batch_download_states(tcv_batch *b) {
         for (int blk : pk.cam_block) { std::memcpy(p.blocks[blk].addr, x + off, sizeof(double) * p.blocks[blk].size); off += p.blocks[blk].size; }
         for (int blk : pk.lm_block) p.blocks[blk].addr[0] = x[off++];
     }
+}
+extern "C" int tcv_batch_download_states(tcv_batch *b) {
+    if (!b || !b->solved) return TCV_ERR_INVALID;
+    if (b->pending) if (int rc = tcv_batch_synchronize(b)) return rc;
+    b->h_state.resize((size_t)b->n * b->state_stride);
+    if (int rc = tcv::staged_download(b->h_state.data(), b->d_state, sizeof(double) * b->h_state.size(), "download of the states")) return rc;
+    scatter_states(b);
     return TCV_OK;
 }
 // Split form for callers that enqueue more work behind the solve: _begin puts the copy of the states (and of the summary heads) on `hip_stream`
@@ -1282,7 +1299,7 @@ extern "C" int tcv_batch_download_states_begin(tcv_batch *b, void *hip_stream) {
     if (e_ == hipSuccess) e_ = hipMemcpyAsync(hs, b->d_state, sbytes, hipMemcpyDeviceToHost, st);
     if (e_ == hipSuccess) e_ = hipMemcpy2DAsync(hs + sbytes, 32, b->d_summary, sizeof(DevSummary), 32, (size_t)b->n, hipMemcpyDeviceToHost, st);
     if (e_ == hipSuccess) e_ = hipEventRecord(b->ev_dl, st);
-    if (e_ != hipSuccess) { (void)(st ? hipStreamSynchronize(st) : hipDeviceSynchronize()); host_staging_release(hs); return hip_fail(e_, "download of the states"); }
+    if (e_ != hipSuccess) { (void)tcv::stream_wait(st); host_staging_release(hs); return hip_fail(e_, "download of the states"); }
     b->dl_staging = hs;
     return TCV_OK;
 }
@@ -1308,14 +1325,7 @@ extern "C" int tcv_batch_download_states_end(tcv_batch *b, int *num_iterations, 
     // the solve (and the gauge fix) lie behind the copy on the stream: they have finished -- its duration and the CUs its cooperative launch held
     coop_release(b);
     if (b->solved) (void)hipEventElapsedTime(&b->solve_ms, b->ev0, b->ev1);
-    for (int w = 0; w < b->n; w++) {
-        const Packed &pk = b->packed[w];
-        const tcv_problem &p = *b->problems[w];
-        const double *x = b->h_state.data() + (size_t)w * b->state_stride;
-        int off = 0;
-        for (int blk : pk.cam_block) { std::memcpy(p.blocks[blk].addr, x + off, sizeof(double) * p.blocks[blk].size); off += p.blocks[blk].size; }
-        for (int blk : pk.lm_block) p.blocks[blk].addr[0] = x[off++];
-    }
+    scatter_states(b);
     return TCV_OK;
 }
 // States into the callers' blocks AND the three numbers of the summary a per-frame caller reads (the reference reads one:
@@ -1342,15 +1352,9 @@ static void summary_to_public(const DevSummary &s, tcv_solver_summary *o) {
 extern "C" int tcv_batch_get_summaries(tcv_batch *b, tcv_solver_summary *out, int n) {
     if (!b || !out || n < 0 || n > b->n) { set_error("batch_get_summaries: n exceeds the batch size"); return TCV_ERR_INVALID; }
     if (b->pending) if (int rc = tcv_batch_synchronize(b)) return rc;
-    const size_t bytes = sizeof(DevSummary) * (size_t)n;
-    DevSummary *h = (DevSummary *)host_staging_acquire(std::max<size_t>(bytes, 16));
-    if (!h) { set_error("hipHostMalloc (download staging) failed"); return TCV_ERR_HIP; }
-    hipStream_t ust = tcv::util_stream();
-    hipError_t e_ = n ? hipMemcpyAsync(h, b->d_summary, bytes, hipMemcpyDeviceToHost, ust) : hipSuccess;
-    if (e_ == hipSuccess) e_ = ust ? hipStreamSynchronize(ust) : hipDeviceSynchronize();
-    if (e_ == hipSuccess) for (int i = 0; i < n; i++) summary_to_public(h[i], out + i);
-    host_staging_release(h);
-    if (e_ != hipSuccess) return hip_fail(e_, "download of the summaries");
+    std::vector<DevSummary> h(n);
+    if (int rc = tcv::staged_download(h.data(), b->d_summary, sizeof(DevSummary) * (size_t)n, "download of the summaries")) return rc;
+    for (int i = 0; i < n; i++) summary_to_public(h[i], out + i);
     return TCV_OK;
 }
 // tangent step of iteration 1 in problem order: free camera blocks in the order they were added
@@ -1646,7 +1650,6 @@ extern "C" int tcv_eval_imu_factors(int n, const tcv_imu_preintegration *pre, co
                                     int use_given, double *sqrt_io, double *res, double *jac) {
     if (n <= 0 || !pre || !params || !G || !sqrt_io || !res) return TCV_ERR_INVALID;
     if (int rc = device_ready()) return rc;
-    tcv_problem tmp;   // reuse the packer's constant layout
     std::vector<double> consts((size_t)n * IMU_CONST);
     for (int i = 0; i < n; i++) {
         double *D = consts.data() + (size_t)i * IMU_CONST;

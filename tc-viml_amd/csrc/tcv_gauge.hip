@@ -83,7 +83,7 @@ extern "C" int tcv_gauge_fix(int n, const double *R0, const double *P0, const do
         hipLaunchKernelGGL(gauge_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, d, d + 9, d + 12, d + 12 + 7 * n, o, o + 9 * n, o + 12 * n,
                            o + 15 * n);
         e = hipGetLastError();
-        if (e == hipSuccess) e = st ? hipStreamSynchronize(st) : hipDeviceSynchronize();
+        if (e == hipSuccess) e = tcv::stream_wait(st);
         std::vector<double> ho(nout);
         if (e == hipSuccess) e = hipMemcpy(ho.data(), o, sizeof(double) * nout, hipMemcpyDeviceToHost);
         if (e == hipSuccess) {

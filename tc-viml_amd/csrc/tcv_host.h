@@ -270,6 +270,26 @@ void host_staging_release(void *p);
 // buffers of commands left in flight on the calling thread's stream `st`: released at the thread's next wait on it (tcv_capi.hip)
 void defer_release(void *host_staging, void *dev_buf, hipStream_t st);
 void flush_deferred(hipStream_t st);
+hipError_t stream_wait(hipStream_t st);      // waits for the stream; for the device when `st` is the null stream
+// The buffers of ONE call's transfer: a pinned staging buffer and, optionally, one pooled device buffer, bound to the stream the call's
+// commands go to.  Both go back to process-wide pools that other host threads take from, so releasing them while a copy or a kernel on
+// `st` still uses them is a use-after-free across threads: once the call has said issued(), every exit waits for the stream first.
+struct StagedTransfer {
+    void *host, *dev = nullptr;
+    const hipStream_t st;
+    StagedTransfer(hipStream_t stream, size_t host_bytes) : host(host_staging_acquire(host_bytes)), st(stream) {}
+    StagedTransfer(const StagedTransfer &) = delete;
+    ~StagedTransfer();                                      // in flight: waits for the stream; then both buffers go back to their pools
+    hipError_t dev_alloc(size_t bytes) { return dev_malloc(&dev, bytes); }
+    void issued() { in_flight = true; }                     // a command that uses a buffer is on the stream, or about to be
+    hipError_t wait();                                      // no longer in flight once a wait has succeeded
+    void park();                                            // left in flight: the buffers are released at the thread's next wait on the stream (defer_release)
+    void *take_dev() { void *p = dev; dev = nullptr; return p; }      // the caller keeps the device buffer (and frees it behind this guard's wait)
+private:
+    bool in_flight = false;
+};
+// blocking download through pinned staging on the calling thread's own stream (the default stream serialises the host threads of a process)
+int staged_download(void *dst, const void *d_src, size_t bytes, const char *what);
 // a non-blocking stream of the calling thread on its current device, created on first use and kept: the one-shot entry points
 // (pre-integration, line association, gauge fix) launch there and wait for THAT stream, never for the device -- another host thread's
 // batches keep running (several estimator groups per GPU, bench.py --mode replay)

@@ -286,16 +286,16 @@ extern "C" int tcv_match_lines_batch(int n, const tcv_match_lines_args *args) {
     in_total = up16(o_mf + sizeof(int) * (size_t)(n + 1));
     if (int rc = device_ready()) return rc;
     const size_t total = in_total + fov_total + out_total;
-    char *h = (char *)tcv::host_staging_acquire(total);
-    if (!h) { set_error("hipHostMalloc (staging) failed"); return TCV_ERR_HIP; }
-    char *dv = nullptr;
-    hipError_t e = tcv::dev_malloc((void **)&dv, total);
     hipStream_t st = tcv::util_stream();
-    bool in_flight = false;
+    tcv::StagedTransfer io(st, total);      // both buffers in the layout above; every exit behind the first copy waits for the stream before they go back to their pools
+    char *h = (char *)io.host;
+    if (!h) { set_error("hipHostMalloc (staging) failed"); return TCV_ERR_HIP; }
+    hipError_t e = io.dev_alloc(total);
+    char *dv = (char *)io.dev;
     std::vector<size_t> o_pose(n), o_ex(n), o_R(n), o_T(n), o_K(n), o_map(n), o_dl(n);
     int cur_dev = 0;
     (void)hipGetDevice(&cur_dev);
-    for (int c = 0; c < n && e == hipSuccess; c++) if (args[c].map_device && args[c].map_device->dev != cur_dev) { tcv::host_staging_release(h); tcv::dev_free(dv); set_error("match_lines: map_device lives on another device"); return TCV_ERR_INVALID; }
+    for (int c = 0; c < n && e == hipSuccess; c++) if (args[c].map_device && args[c].map_device->dev != cur_dev) { set_error("match_lines: map_device lives on another device"); return TCV_ERR_INVALID; }
     if (e == hipSuccess) {
         // the staging buffer is filled by the worker threads (the calls' slices are disjoint): 64 calls with their maps are 3.4 MB of memcpy
         auto fill = [&](int c) {
@@ -314,7 +314,6 @@ extern "C" int tcv_match_lines_batch(int n, const tcv_match_lines_args *args) {
         if (nth > 1) tcv::parallel_run(nth, [&](int t) { for (int c = t; c < n; c += nth) fill(c); });
         else for (int c = 0; c < n; c++) fill(c);
     }
-    int rc = TCV_OK;
     int fov_blocks = 0, det_blocks = 0;
     if (e == hipSuccess) {
         LineArgs *tab = (LineArgs *)(h + o_tab);
@@ -338,7 +337,7 @@ extern "C" int tcv_match_lines_batch(int n, const tcv_match_lines_args *args) {
             det_blocks += a.n_det;
         }
         ff[n] = fov_blocks; mf[n] = det_blocks;
-        in_flight = true;
+        io.issued();
         e = hipMemcpyAsync(dv, h, in_total + fov_total, hipMemcpyHostToDevice, st);
     }
     if (e == hipSuccess) {
@@ -348,7 +347,7 @@ extern "C" int tcv_match_lines_batch(int n, const tcv_match_lines_args *args) {
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h + in_total, dv + in_total, fov_total + out_total, hipMemcpyDeviceToHost, st);
-    if (in_flight) { const hipError_t es = st ? hipStreamSynchronize(st) : hipDeviceSynchronize(); if (e == hipSuccess) e = es; }
+    if (e == hipSuccess) e = io.wait();      // (after an error the guard waits, at the exit)
     if (e == hipSuccess)
         for (int c = 0; c < n; c++) {
             const tcv_match_lines_args &a = args[c];
@@ -360,10 +359,7 @@ extern "C" int tcv_match_lines_batch(int n, const tcv_match_lines_args *args) {
             if (a.n_det && a.err) std::memcpy(a.err, ho + L[c].o_err, sizeof(float) * 3 * a.n_det);
             if (a.n_det && a.projected) std::memcpy(a.projected, ho + L[c].o_out, sizeof(double) * 4 * a.n_det);
         }
-    if (e != hipSuccess) rc = hip_fail(e, "match_lines");
-    tcv::host_staging_release(h);
-    tcv::dev_free(dv);
-    return rc;
+    return e == hipSuccess ? TCV_OK : hip_fail(e, "match_lines");
 }
 
 extern "C" int tcv_match_lines(int n_frames, const double *poses, const double *ex_pose, const double *Rbw, const double *Tbw, const double *K,

@@ -2275,10 +2275,11 @@ int tcv_marg_attach(tcv_batch *b, tcv_problem *const *marg_problems, double *con
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t o_hdr = up16(sizeof(double) * std::max<size_t>(1, d_total)), o_int = up16(o_hdr + sizeof(MargHdr) * hdrs.size());
     const size_t in_bytes = up16(o_int + sizeof(int) * std::max<size_t>(1, i_total));
-    char *h_in = (char *)tcv::host_staging_acquire(in_bytes);
+    hipStream_t ust = tcv::util_stream();
     // (released at every exit; once the asynchronous upload has been issued the stream is drained first: the pinned buffer goes back to a
     // pool another host thread takes from)
-    struct Staged { void *a; hipStream_t st; bool in_flight; ~Staged() { if (in_flight) (void)(st ? hipStreamSynchronize(st) : hipDeviceSynchronize()); tcv::host_staging_release(a); } } staged{h_in, nullptr, false};
+    tcv::StagedTransfer staged(ust, in_bytes);
+    char *h_in = (char *)staged.host;
     if (!h_in) { set_error("hipHostMalloc (upload staging) failed"); return TCV_ERR_HIP; }
     int *h_I = (int *)(h_in + o_int);
     double *h_D = (double *)h_in;
@@ -2291,11 +2292,7 @@ int tcv_marg_attach(tcv_batch *b, tcv_problem *const *marg_problems, double *con
         tcv::parallel_run(nth, copy);
     }
     s->lds_bytes = lds;
-    hipDeviceProp_t prop;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return TCV_ERR_HIP;
-    const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    const int n_cu = b->n_cu;      // (of the batch's device: tcv_batch_create sets it before anything attaches)
     // more windows than CUs and every window within half a CU's LDS: two 256-thread workgroups per CU; otherwise one of 512 threads
     const char *force = getenv("TCV_MARG_NT");
     const bool pair = force ? atoi(force) == MARG_NT_PAIR : (b->n > n_cu && lds <= (size_t)LDS_DOUBLES * 4);
@@ -2305,9 +2302,8 @@ int tcv_marg_attach(tcv_batch *b, tcv_problem *const *marg_problems, double *con
     s->grid = std::min(b->n, pair ? 2 * n_cu : n_cu);
     if (const char *eg = getenv("TCV_MARG_GRID")) { const int g = atoi(eg); if (g > 0) s->grid = std::min(s->grid, g); }      // tuning experiments (one workgroup per CU: TCV_MARG_GRID=256)
     {
-        hipStream_t ust = tcv::util_stream();
         hipError_t e_ = tcv::dev_malloc(&s->d_input, in_bytes);
-        if (e_ == hipSuccess) { staged.st = ust; staged.in_flight = true; e_ = hipMemcpyAsync(s->d_input, h_in, in_bytes, hipMemcpyHostToDevice, ust); }
+        if (e_ == hipSuccess) { staged.issued(); e_ = hipMemcpyAsync(s->d_input, h_in, in_bytes, hipMemcpyHostToDevice, ust); }
         // result blocks and, behind them, [status | k0] of every window: one buffer, kept alive by the device-resident priors that read it
         if (e_ == hipSuccess) e_ = tcv::dev_malloc((void **)&s->d_out, sizeof(double) * std::max<size_t>(1, (size_t)b->n * MARG_OUT_STRIDE) + sizeof(int) * 2 * (size_t)b->n);
         if (e_ == hipSuccess) { s->out_blob = std::make_shared<DevBlob>(); s->out_blob->p = s->d_out; (void)hipGetDevice(&s->out_blob->dev); s->d_status = (int *)(s->d_out + std::max<size_t>(1, (size_t)b->n * MARG_OUT_STRIDE)); }
@@ -2319,14 +2315,12 @@ int tcv_marg_attach(tcv_batch *b, tcv_problem *const *marg_problems, double *con
         // tcv_batch_enter_stream); the pinned staging buffer is parked until this thread's next wait on the stream.
         if (e_ == hipSuccess && ust != nullptr) {
             if (int rce = tcv_batch_enter_stream(b, (void *)ust)) return rce;
-            tcv::defer_release(h_in, nullptr, ust);
-            staged.in_flight = false; staged.a = nullptr;
-        } else if (e_ == hipSuccess) { e_ = hipDeviceSynchronize(); if (e_ == hipSuccess) staged.in_flight = false; }
+            staged.park();
+        } else if (e_ == hipSuccess) e_ = staged.wait();
         if (e_ != hipSuccess) return hip_fail(e_, "upload of the marginalisation problems");
         s->d_dpool = (double *)s->d_input; s->d_hdr = (MargHdr *)((char *)s->d_input + o_hdr); s->d_ipool = (int *)((char *)s->d_input + o_int);
     }
     if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) return TCV_ERR_HIP;
-    b->input_bytes += 0;   // marginalisation reads the same resident inputs
     return TCV_OK;
 }
 
@@ -2404,7 +2398,7 @@ int tcv_marg_download(tcv_batch *b, int compact) {
     hipStream_t ust = tcv::util_stream();      // (h_out is pinned: asynchronous copies on the calling thread's own stream)
     hipError_t e = compact ? hipMemcpy2DAsync(s->h_out, sizeof(double) * stride, s->d_out, sizeof(double) * MARG_OUT_STRIDE, sizeof(double) * stride, b->n, hipMemcpyDeviceToHost, ust)
                            : hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * stride * b->n, hipMemcpyDeviceToHost, ust);
-    if (e == hipSuccess) e = ust ? hipStreamSynchronize(ust) : hipDeviceSynchronize();
+    if (e == hipSuccess) e = tcv::stream_wait(ust);
     if (e == hipSuccess) e = hipMemcpy(s->h_status.data(), s->d_status, sizeof(int) * b->n, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
     s->h_valid = true;
@@ -2434,6 +2428,30 @@ extern "C" int tcv_batch_marg_status(tcv_batch *b, int *out, int n) {
     return TCV_OK;
 }
 
+// kernel status of a window: TCV_OK, or the error it stands for
+static int marg_status_error(int status) {
+    if (status < 0) { set_error("marginalisation kernel did not complete for this window"); return TCV_ERR_NUMERIC; }
+    // status 1: an eigen-solver ran into its sweep cap -- the decomposition is not converged and the prior would silently degrade every
+    // later window (the reference's SelfAdjointEigenSolver has no such exit); status 2 (safety net took over) is a valid result
+    if (status == 1) { set_error("marginalisation: eigen-decomposition did not converge (sweep cap)"); return TCV_ERR_NUMERIC; }
+    return TCV_OK;
+}
+// host-side layout of the prior a window's marginalisation makes (no numbers yet): kept blocks' sizes, columns, offsets in x0, addresses
+static tcv_prior *prior_layout(const MargWindow &mw) {
+    tcv_prior *pr = new tcv_prior();
+    pr->m = mw.m_total; pr->n = mw.hdr.n;     // the reference's m counts every marginalised dim (marginalization_factor.cpp:176-186)
+    int xo = 0;
+    for (size_t k = 0; k < mw.keep_block.size(); k++) {
+        pr->size.push_back(mw.keep_size[k]);
+        pr->idx.push_back(mw.keep_idx[k] - mw.hdr.m);      // (hdr.m: dropped dims that went through the eigen step)
+        pr->xoff.push_back(xo);
+        xo += mw.keep_size[k];
+        pr->addr.push_back(mw.keep_addr[k]);
+    }
+    pr->xsize = xo;
+    return pr;
+}
+
 int tcv_marg_get_prior(tcv_batch *b, int window, tcv_prior **out) {
     MargState *s = (MargState *)b->marg;
     if (!s || !s->ran || window < 0 || window >= b->n) { set_error("no marginalisation result for this window"); return TCV_ERR_INVALID; }
@@ -2450,26 +2468,13 @@ int tcv_marg_get_prior(tcv_batch *b, int window, tcv_prior **out) {
         status = s->h_status[window];
     } else {
         hipError_t e = hipMemcpy(o.data(), s->d_out + (size_t)window * MARG_OUT_STRIDE, sizeof(double) * MARG_OUT_STRIDE, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
-        e = hipMemcpy(&status, s->d_status + window, sizeof(int), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(&status, s->d_status + window, sizeof(int), hipMemcpyDeviceToHost);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
     }
-    if (status < 0) { set_error("marginalisation kernel did not complete for this window"); return TCV_ERR_NUMERIC; }
-    // status 1: an eigen-solver ran into its sweep cap -- the decomposition is not converged and the prior would silently degrade every
-    // later window (the reference's SelfAdjointEigenSolver has no such exit); status 2 (safety net took over) is a valid result
-    if (status == 1) { set_error("marginalisation: eigen-decomposition did not converge (sweep cap)"); return TCV_ERR_NUMERIC; }
-    tcv_prior *pr = new tcv_prior();
-    pr->m = mw.m_total; pr->n = n;            // the reference's m counts every marginalised dim (marginalization_factor.cpp:176-186)
-    int xo = 0;
-    for (size_t k = 0; k < mw.keep_block.size(); k++) {
-        pr->size.push_back(mw.keep_size[k]);
-        pr->idx.push_back(mw.keep_idx[k] - m);
-        pr->xoff.push_back(xo);
+    if (int rc = marg_status_error(status)) return rc;
+    tcv_prior *pr = prior_layout(mw);
+    for (size_t k = 0; k < mw.keep_block.size(); k++)
         for (int i = 0; i < mw.keep_size[k]; i++) pr->x0.push_back(o[MARG_OUT_X + mw.keep_goff[k] + i]);
-        xo += mw.keep_size[k];
-        pr->addr.push_back(mw.keep_addr[k]);
-    }
-    pr->xsize = xo;
     pr->J0.assign(o.begin() + MARG_OUT_J0, o.begin() + MARG_OUT_J0 + (size_t)n * n);
     pr->r0.assign(o.begin() + MARG_OUT_R0, o.begin() + MARG_OUT_R0 + n);
     if (have_schur) {
@@ -2503,16 +2508,7 @@ int tcv_marg_get_priors_device(tcv_batch *b, tcv_prior **out, int n, bool nowait
     }
     std::vector<int> st(2 * (size_t)n, 0);
     if (nowait) { for (int w = 0; w < n; w++) st[n + w] = -1; }      // status unknown here (tcv_batch_marg_status later), k0 read on the device
-    else {
-        hipStream_t ust = tcv::util_stream();
-        int *hs = (int *)tcv::host_staging_acquire(sizeof(int) * st.size());
-        if (!hs) { set_error("hipHostMalloc (download staging) failed"); return TCV_ERR_HIP; }
-        hipError_t e = hipMemcpyAsync(hs, s->d_status, sizeof(int) * st.size(), hipMemcpyDeviceToHost, ust);
-        if (e == hipSuccess) e = ust ? hipStreamSynchronize(ust) : hipDeviceSynchronize();
-        if (e == hipSuccess) std::memcpy(st.data(), hs, sizeof(int) * st.size());
-        tcv::host_staging_release(hs);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H (marginalisation status)");
-    }
+    else if (int rcd = tcv::staged_download(st.data(), s->d_status, sizeof(int) * st.size(), "hipMemcpy D2H (marginalisation status)")) return rcd;
     for (int w = 0; w < n; w++) out[w] = nullptr;
     int rc = TCV_OK;
     for (int w = 0; w < n && rc == TCV_OK; w++) {
@@ -2520,19 +2516,11 @@ int tcv_marg_get_priors_device(tcv_batch *b, tcv_prior **out, int n, bool nowait
         if (mw.empty_keep) { tcv_prior *pr = new tcv_prior(); pr->m = mw.m_total; pr->n = 0; out[w] = pr; continue; }      // empty prior: host-resident, nothing to splice
         if (mw.hdr.nblk == 0) continue;      // not marginalised: out[w] stays NULL
         const int status = st[w], k0 = st[n + w];
-        if (status < 0) { set_error("marginalisation kernel did not complete for this window"); rc = TCV_ERR_NUMERIC; break; }
-        if (status == 1) { set_error("marginalisation: eigen-decomposition did not converge (sweep cap)"); rc = TCV_ERR_NUMERIC; break; }
+        if ((rc = marg_status_error(status)) != TCV_OK) break;
         if (k0 < 0 && !nowait) { set_error("NaN in marginalisation result"); rc = TCV_ERR_NUMERIC; break; }
         if ((int)mw.keep_block.size() > PRIOR_SPLICE_MAX_BLOCKS) { set_error("device-resident prior: too many kept blocks"); rc = TCV_ERR_TOO_LARGE; break; }
-        tcv_prior *pr = new tcv_prior();
-        pr->m = mw.m_total; pr->n = mw.hdr.n;
-        int xo = 0;
-        for (size_t k = 0; k < mw.keep_block.size(); k++) {
-            pr->size.push_back(mw.keep_size[k]); pr->idx.push_back(mw.keep_idx[k] - mw.hdr.m); pr->xoff.push_back(xo);
-            pr->x_goff.push_back(mw.keep_goff[k]); pr->addr.push_back(mw.keep_addr[k]);
-            xo += mw.keep_size[k];
-        }
-        pr->xsize = xo;
+        tcv_prior *pr = prior_layout(mw);
+        pr->x_goff.assign(mw.keep_goff.begin(), mw.keep_goff.begin() + mw.keep_block.size());
         pr->dev = s->out_blob; pr->d_block = s->d_out + (size_t)w * MARG_OUT_STRIDE; pr->k0 = k0; pr->host = false;
         pr->d_status = s->d_status + w; pr->d_k0 = s->d_status + n + w;
         out[w] = pr;

@@ -225,6 +225,12 @@ using namespace tcv;
 // One pinned staging buffer, one copy in, everything on the calling thread's own stream: [init 12 n | samples 7 ns | first n, count n
 // (ints)] -> device; the kernel's output records (PREINT_OUT doubles each) either come back through the same staging buffer
 // (tcv_preintegrate) or stay where they are, in a buffer of their own that the returned handles share (tcv_preintegrate_device).
+// the kernel's output record (PREINT_OUT doubles, layout: tcv_host.h tcv_preint) as the C-ABI's struct
+static void unpack_record(const double *o, tcv_imu_preintegration &p) {
+    std::memcpy(p.delta_p, o, 24); std::memcpy(p.delta_q, o + 3, 32); std::memcpy(p.delta_v, o + 7, 24);
+    std::memcpy(p.linearized_ba, o + 10, 24); std::memcpy(p.linearized_bg, o + 13, 24); p.sum_dt = o[16];
+    std::memcpy(p.jacobian, o + 17, 225 * 8); std::memcpy(p.covariance, o + 242, 225 * 8);
+}
 static int preintegrate_core(int n, const int *first, const int *count, const double *samples7, int num_samples, const double *acc0_gyr0_ba_bg,
                              const double noise[4], tcv_imu_preintegration *out, tcv_preint **handles) {
     if (n <= 0 || !first || !count || !samples7 || num_samples < 0 || !acc0_gyr0_ba_bg || !noise || (!out && !handles)) return TCV_ERR_INVALID;
@@ -236,38 +242,39 @@ static int preintegrate_core(int n, const int *first, const int *count, const do
     for (int i = 0; i < 4; i++) a.noise[i] = noise[i];
     const size_t ns = (size_t)std::max(1, num_samples);
     const size_t in_d = 12 * (size_t)n + 7 * ns, in_bytes = sizeof(double) * in_d + sizeof(int) * 2 * (size_t)n, out_bytes = sizeof(double) * PREINT_OUT * (size_t)n;
-    char *h = (char *)tcv::host_staging_acquire(in_bytes + (out ? out_bytes : 0));
-    if (!h) { set_error("hipHostMalloc (staging) failed"); return TCV_ERR_HIP; }
-    char *d = nullptr, *d_res = nullptr;      // inputs (+ outputs of the host variant); the device variant's outputs
     hipStream_t st = tcv::util_stream();
-    bool in_flight = false;
-    auto done = [&](int rc) {
-        if (in_flight) (void)(st ? hipStreamSynchronize(st) : hipDeviceSynchronize());      // the pinned buffer and the blobs go back to pools
-        tcv::host_staging_release(h); (void)tcv::dev_free(d);
-        if (rc != TCV_OK) (void)tcv::dev_free(d_res);
-        return rc;
-    };
+    // the device variant's outputs, owned by the blob the handles share.  Declared before the guard: an error exit destroys the guard first,
+    // which waits for the stream, and only then the blob (both give their buffers back to pools)
+    std::shared_ptr<tcv::DevBlob> blob;
+    tcv::StagedTransfer io(st, in_bytes + (out ? out_bytes : 0));      // pinned [inputs | outputs of the host variant]; device inputs (+ outputs of the host variant)
+    char *h = (char *)io.host;
+    if (!h) { set_error("hipHostMalloc (staging) failed"); return TCV_ERR_HIP; }
     static const bool dbg = getenv("TCV_DEBUG_EST") != nullptr;      // developer: where a call's time goes
     auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = dbg ? now_us() : 0.0;
     const size_t out_off = (in_bytes + 15) & ~(size_t)15;
-    hipError_t e = tcv::dev_malloc((void **)&d, out_off + (handles ? 0 : out_bytes) + 16);
-    if (e == hipSuccess && handles) e = tcv::dev_malloc((void **)&d_res, out_bytes);
-    if (e != hipSuccess) return done(hip_fail(e, "hipMalloc"));
+    hipError_t e = io.dev_alloc(out_off + (handles ? 0 : out_bytes) + 16);
+    if (e == hipSuccess && handles) {
+        blob = std::make_shared<tcv::DevBlob>();
+        (void)hipGetDevice(&blob->dev);
+        e = tcv::dev_malloc(&blob->p, out_bytes);
+    }
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc");
+    char *d = (char *)io.dev, *d_res = blob ? (char *)blob->p : nullptr;
     double *hd = (double *)h;
     std::memcpy(hd, acc0_gyr0_ba_bg, sizeof(double) * 12 * (size_t)n);
     if (num_samples) std::memcpy(hd + 12 * (size_t)n, samples7, sizeof(double) * 7 * (size_t)num_samples);
     int *hi = (int *)(hd + in_d);
     std::memcpy(hi, first, sizeof(int) * n); std::memcpy(hi + n, count, sizeof(int) * n);
-    in_flight = true;
+    io.issued();
     const double t1 = dbg ? now_us() : 0.0;
-    if ((e = hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return done(hip_fail(e, "hipMemcpyAsync"));
+    if ((e = hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(e, "hipMemcpyAsync");
     a.init = (const double *)d; a.samples = (const double *)d + 12 * (size_t)n; a.first = (const int *)((const double *)d + in_d); a.count = a.first + n;
     a.out = handles ? (double *)d_res : (double *)(d + out_off);
     hipLaunchKernelGGL(preint_kernel, dim3(std::min(n, 4096)), dim3(tcv::PRE_NT), 0, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return done(hip_fail(e, "preint kernel launch"));
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "preint kernel launch");
     char *ho = h + in_bytes;
-    if (out && (e = hipMemcpyAsync(ho, (const char *)a.out, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return done(hip_fail(e, "hipMemcpyAsync"));
+    if (out && (e = hipMemcpyAsync(ho, (const char *)a.out, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "hipMemcpyAsync");
     const double t2 = dbg ? now_us() : 0.0;
     // device variant: nobody on the host needs the result -- the commands stay in flight on this thread's stream, the handles' blob carries
     // an event for consumers on other streams / host readers, the staging buffers are released at the thread's next wait on the stream
@@ -276,22 +283,11 @@ static int preintegrate_core(int n, const int *first, const int *count, const do
     if (handles && st && !no_defer && hipEventCreateWithFlags(&ready, hipEventDisableTiming) == hipSuccess) {
         if (hipEventRecord(ready, st) != hipSuccess) { (void)hipEventDestroy(ready); ready = nullptr; }
     }
-    if (!ready) {
-        if ((e = (st ? hipStreamSynchronize(st) : hipDeviceSynchronize())) != hipSuccess) return done(hip_fail(e, "hipStreamSynchronize"));
-        in_flight = false;
-    }
+    if (!ready && (e = io.wait()) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     if (dbg) fprintf(stderr, "[preint] n %d (%s): allocations + staging %.0f us, issue %.0f us, wait %.0f us\n", n, handles ? "device" : "host", t1 - t0, t2 - t1, now_us() - t2);
     if (out)
-        for (int i = 0; i < n; i++) {
-            const double *o = (const double *)ho + (size_t)i * PREINT_OUT;
-            tcv_imu_preintegration &p = out[i];
-            std::memcpy(p.delta_p, o, 24); std::memcpy(p.delta_q, o + 3, 32); std::memcpy(p.delta_v, o + 7, 24);
-            std::memcpy(p.linearized_ba, o + 10, 24); std::memcpy(p.linearized_bg, o + 13, 24); p.sum_dt = o[16];
-            std::memcpy(p.jacobian, o + 17, 225 * 8); std::memcpy(p.covariance, o + 242, 225 * 8);
-        }
+        for (int i = 0; i < n; i++) unpack_record((const double *)ho + (size_t)i * PREINT_OUT, out[i]);
     if (handles) {
-        auto blob = std::make_shared<tcv::DevBlob>();
-        blob->p = d_res; (void)hipGetDevice(&blob->dev);
         blob->ready = ready;
         for (int i = 0; i < n; i++) {
             tcv_preint *q = new tcv_preint();
@@ -302,8 +298,7 @@ static int preintegrate_core(int n, const int *first, const int *count, const do
             handles[i] = q;
         }
     }
-    if (ready) { tcv::defer_release(h, d, st); return TCV_OK; }
-    (void)done(TCV_OK);
+    if (ready) io.park();      // (else: waited for above, released here)
     return TCV_OK;
 }
 extern "C" int tcv_preintegrate(int n, const int *first, const int *count, const double *samples7, int num_samples,
@@ -329,10 +324,7 @@ int tcv_preint_host(const tcv_preint *pre) {
     const hipError_t e = hipMemcpy(o, pre->d_out, sizeof o, hipMemcpyDeviceToHost);
     if (sw) (void)hipSetDevice(cur);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H (device-resident pre-integration)");
-    tcv_imu_preintegration &p = pre->pod;
-    std::memcpy(p.delta_p, o, 24); std::memcpy(p.delta_q, o + 3, 32); std::memcpy(p.delta_v, o + 7, 24);
-    std::memcpy(p.linearized_ba, o + 10, 24); std::memcpy(p.linearized_bg, o + 13, 24); p.sum_dt = o[16];
-    std::memcpy(p.jacobian, o + 17, 225 * 8); std::memcpy(p.covariance, o + 242, 225 * 8);
+    unpack_record(o, pre->pod);
     pre->host = true;
     return TCV_OK;
 }
