@@ -42,7 +42,17 @@ int main() {
             options.linear_solver_type = SPARSE_SCHUR;
             options.trust_region_strategy_type = DOGLEG;
             options.max_num_iterations = 8;
+            // Problem::Evaluate around the solve: the cost by factor family at the states before and after
+            auto evaluate = [&](const char *when) {
+                double cost = 0, fam[4];
+                std::vector<double> residuals, gradient;
+                if (!problem.Evaluate(Problem::EvaluateOptions(), &cost, &residuals, &gradient, fam)) throw std::runtime_error("Problem::Evaluate failed");
+                std::printf("evaluate (%s): cost %.17g = prior %.17g + imu %.17g + points %.17g + lines %.17g; %d residuals, %d gradient entries\n", when, cost, fam[0],
+                            fam[1], fam[2], fam[3], (int)residuals.size(), (int)gradient.size());
+            };
+            evaluate("before");
             Solve(options, &problem, &summary);                                    // :1900
+            evaluate("after");
         }                                                                          // problem (and its factors) destroyed here, like :2119
         std::printf("solve: %d iterations, cost %.6g -> %.6g, inverse depth %.6f\n", (int)summary.iterations.size(), summary.initial_cost, summary.final_cost,
                     para_Feature[0][0]);

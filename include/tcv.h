@@ -345,6 +345,49 @@ int tcv_batch_layout(const tcv_batch *b);
 int tcv_batch_stats(tcv_batch *b, double *input_bytes, double *solve_ms, double *marg_ms);
 int tcv_batch_size(const tcv_batch *b);
 
+/* ---- ceres::Problem::Evaluate (problem.h: Evaluate(const EvaluateOptions &, double *cost, vector<double> *residuals,
+ *      vector<double> *gradient, CRSMatrix *jacobian)), batched on the device ------------------------------------------- */
+/* Problem::EvaluateOptions: apply_loss_function as in Ceres (1: residuals and gradient are the loss-corrected ones, costs are
+ * 0.5 rho(|r|^2); 0: whitened residuals, costs 0.5 |r|^2).  `at`: the states a batch is evaluated at -- the uploaded initial states or
+ * the states the last tcv_batch_solve left in HBM (gauge-fixed if that solve / a tcv_batch_gauge_fix fixed them).  want_*: which
+ * per-window arrays the kernel writes beside the scalars. */
+typedef enum { TCV_EVALUATE_AT_INITIAL = 0, TCV_EVALUATE_AT_SOLUTION = 1 } tcv_evaluate_at;
+typedef struct {
+    int at;                  /* tcv_evaluate_at */
+    int apply_loss_function; /* default 1 */
+    int want_residuals, want_gradient, want_block_costs; /* default 0 */
+} tcv_evaluate_options;
+void tcv_evaluate_options_default(tcv_evaluate_options *o);
+/* Problem::Evaluate for every window of the batch, asynchronous on `hip_stream` like tcv_batch_solve (TCV_STREAM_THREAD honoured),
+ * ordered behind the batch's work in flight; any number of times, before or after a solve (at = solution before any solve:
+ * TCV_ERR_INVALID).  It changes nothing a later solve / marginalisation reads.  Every sum has a fixed order: the same bits from run to
+ * run and whatever else is in the batch. */
+int tcv_batch_evaluate(tcv_batch *b, const tcv_evaluate_options *o, void *hip_stream);
+/* Problem::NumResiduals(), NumResidualBlocks() and the gradient's length (sum of the tangent sizes of the non-constant blocks) of one
+ * window; any pointer may be NULL.  Host only. */
+int tcv_batch_evaluation_dims(const tcv_batch *b, int window, int *num_residuals, int *num_residual_blocks, int *num_local);
+/* The last evaluation of one window (waits for it).  cost = ((family_cost[0] + family_cost[1]) + family_cost[2]) + family_cost[3], the
+ * costs of the marginalisation prior, the IMU factors, the point factors (relocalisation factors included) and the line factors;
+ * gradient_max_norm = max |gradient[i]| (-1 when the gradient was not asked for).  Arrays (each may be NULL; *_cap = room in doubles,
+ * too little: TCV_ERR_INVALID; an array the options did not ask for: TCV_ERR_INVALID):
+ *   residuals    the prior's n rows, then IMU, point and line factors, each family in the order the caller added them
+ *   block_costs  one robustified cost per residual block, same order (Problem::Evaluate on one ResidualBlockId at a time)
+ *   gradient     J'r in tangent space, layout of tcv_batch_get_first_step: free camera blocks in the order they were added (pose
+ *                blocks through PoseLocalParameterization's 6 columns), then the inverse depths in order of first use
+ * NaN / Inf in the result: TCV_ERR_NUMERIC (the outputs are still written). */
+int tcv_batch_get_evaluation(tcv_batch *b, int window, double *cost, double family_cost[4], double *gradient_max_norm,
+                             double *residuals, int residuals_cap, double *block_costs, int block_costs_cap, double *gradient,
+                             int gradient_cap);
+/* the scalars of every window in one device round trip: cost[n], family_cost[4 n], gradient_max_norm[n] (any may be NULL; n = batch size) */
+int tcv_batch_get_evaluation_costs(tcv_batch *b, double *cost, double *family_cost, double *gradient_max_norm, int n);
+/* Problem::Evaluate for one problem at the CURRENT values of the caller's parameter blocks (host pointers, left untouched): a one-window
+ * batch evaluated at its initial state (`at` is ignored).  Any output may be NULL; residuals holds tcv_problem_num_residuals(p) doubles,
+ * gradient tcv_problem_num_effective_parameters(p), family_cost 4. */
+int tcv_problem_evaluate(tcv_problem *p, const tcv_evaluate_options *o, double *cost, double *residuals, double *gradient,
+                         double *family_cost);
+/* Problem::NumEffectiveParameters(): sum of the tangent sizes of the problem's non-constant parameter blocks */
+int tcv_problem_num_effective_parameters(const tcv_problem *p);
+
 /* ---- Estimator::double2vector() gauge fix (estimator.cpp:1537-1581) ------------------------ */
 /* The yaw of frame 0 and its position are unobservable: after the solve the window is rotated back about the
  * vertical by the yaw drift of frame 0 (Utility::R2ypr / ypr2R, utility.h:70-112; full rotation near the Euler

@@ -125,6 +125,20 @@ class Problem {                                                           // cer
         own(owned_cost_, f); if (loss) own(owned_loss_, loss);
     }
     inline void AddResidualBlock(MarginalizationFactor *f, LossFunction *, const std::vector<double *> &blocks);
+    // ceres::Problem::EvaluateOptions / Problem::Evaluate(options, &cost, &residuals, &gradient, nullptr) at the current values of the
+    // parameter blocks, which stay untouched (tcv_problem_evaluate); family_cost (optional, 4 doubles): the cost of the prior, the IMU,
+    // the point and the line factors.  Any output may be null.  false: the evaluation failed (a NaN, like Ceres).
+    struct EvaluateOptions { bool apply_loss_function = true; };
+    bool Evaluate(const EvaluateOptions &o, double *cost, std::vector<double> *residuals, std::vector<double> *gradient, double *family_cost = nullptr) {
+        tcv_evaluate_options eo;
+        tcv_evaluate_options_default(&eo);
+        eo.apply_loss_function = o.apply_loss_function ? 1 : 0;
+        if (residuals) residuals->assign((size_t)tcv_problem_num_residuals(p_), 0.0);
+        if (gradient) gradient->assign((size_t)tcv_problem_num_effective_parameters(p_), 0.0);
+        const int rc = tcv_problem_evaluate(p_, &eo, cost, residuals ? residuals->data() : nullptr, gradient ? gradient->data() : nullptr, family_cost);
+        if (rc != TCV_OK && rc != TCV_ERR_NUMERIC) detail::check(rc, "tcv_problem_evaluate");
+        return rc == TCV_OK;
+    }
     tcv_problem *handle() { return p_; }
 
   private:

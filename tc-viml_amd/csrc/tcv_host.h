@@ -217,6 +217,8 @@ struct tcv_batch {
     // marginalisation
     void *marg = nullptr;                 // tcv_marg.hip state
     void (*marg_free)(tcv_batch *) = nullptr;
+    // evaluation (tcv_batch_evaluate)
+    void *eval = nullptr;                 // tcv_capi.hip EvalState: owner lists, staging and output buffers, made at the first evaluation
 };
 
 

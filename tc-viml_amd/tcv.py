@@ -43,6 +43,8 @@ EXPORTS = [
     "tcv_problems_set_marginalization_prior", "tcv_priors_destroy",
     "tcv_match_lines_batch", "tcv_preintegrate_device", "tcv_preint_sum_dt", "tcv_preint_export", "tcv_preint_destroy", "tcv_problem_add_imu_factor_device",
     "tcv_microbench_fp64", "tcv_problem_plan_ints", "tcv_set_packer_reference", "tcv_plan_cache_stats", "tcv_problems_pack_bench", "tcv_line_map_create", "tcv_line_map_destroy", "tcv_batch_download_states_brief", "tcv_thread_stream_slot", "tcv_batch_download_states_begin", "tcv_batch_download_states_end",
+    "tcv_evaluate_options_default", "tcv_batch_evaluate", "tcv_batch_evaluation_dims", "tcv_batch_get_evaluation", "tcv_batch_get_evaluation_costs",
+    "tcv_problem_evaluate", "tcv_problem_num_effective_parameters",
 ]
 
 
@@ -59,6 +61,14 @@ class SolverOptions(C.Structure):
     _fields_ = [("max_num_iterations", C.c_int), ("max_solver_time_in_seconds", C.c_double),
                 ("fixed_iterations", C.c_int), ("workgroups_per_window", C.c_int), ("use_mfma", C.c_int),
                 ("threads_per_window", C.c_int), ("record_first_step", C.c_int)]
+
+
+class EvaluateOptions(C.Structure):
+    _fields_ = [("at", C.c_int), ("apply_loss_function", C.c_int), ("want_residuals", C.c_int), ("want_gradient", C.c_int),
+                ("want_block_costs", C.c_int)]
+
+
+EVALUATE_AT_INITIAL, EVALUATE_AT_SOLUTION = 0, 1
 
 
 class SolverSummary(C.Structure):
@@ -178,6 +188,14 @@ def lib():
         L.tcv_match_lines.argtypes = [C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _ip, _dp, C.c_double,
                                       C.c_double, C.c_int, C.POINTER(C.c_ubyte), _ip, C.POINTER(C.c_float), _dp]
         L.tcv_eval_projection_td_factors.argtypes = [C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, _dp, _dp]
+        L.tcv_evaluate_options_default.argtypes = [C.POINTER(EvaluateOptions)]
+        L.tcv_evaluate_options_default.restype = None
+        L.tcv_batch_evaluate.argtypes = [vp, C.POINTER(EvaluateOptions), vp]
+        L.tcv_batch_evaluation_dims.argtypes = [vp, C.c_int, _ip, _ip, _ip]
+        L.tcv_batch_get_evaluation.argtypes = [vp, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int]
+        L.tcv_batch_get_evaluation_costs.argtypes = [vp, _dp, _dp, _dp, C.c_int]
+        L.tcv_problem_evaluate.argtypes = [vp, C.POINTER(EvaluateOptions), _dp, _dp, _dp, _dp]
+        L.tcv_problem_num_effective_parameters.argtypes = [vp]
         _lib = L
     return _lib
 
@@ -219,6 +237,16 @@ def default_options(max_num_iterations=8, fixed_iterations=True, use_mfma=True, 
     o.use_mfma = int(use_mfma)
     o.threads_per_window = threads
     o.record_first_step = int(record_first_step)
+    return o
+
+
+def evaluate_options(at="initial", apply_loss_function=True, residuals=False, gradient=False, block_costs=False):
+    """tcv_evaluate_options (Problem::EvaluateOptions plus the evaluation point and the arrays wanted)"""
+    o = EvaluateOptions()
+    lib().tcv_evaluate_options_default(C.byref(o))
+    o.at = {"initial": EVALUATE_AT_INITIAL, "solution": EVALUATE_AT_SOLUTION}[at] if isinstance(at, str) else int(at)
+    o.apply_loss_function = int(apply_loss_function)
+    o.want_residuals = int(residuals); o.want_gradient = int(gradient); o.want_block_costs = int(block_costs)
     return o
 
 
@@ -351,6 +379,16 @@ class Window:
         if self.td is not None:
             out["td"] = self.td.copy()
         return out
+
+    def evaluate(self, apply_loss_function=True, residuals=True, gradient=True):
+        """tcv_problem_evaluate: Problem::Evaluate at the current values of this window's state arrays (left untouched).
+        Returns dict(cost, family_cost (4), residuals, gradient); an array that was not asked for is None."""
+        o = evaluate_options("initial", apply_loss_function)
+        cost = C.c_double(); fam = np.zeros(4)
+        r = np.zeros(lib().tcv_problem_num_residuals(self.h)) if residuals else None
+        g = np.zeros(lib().tcv_problem_num_effective_parameters(self.h)) if gradient else None
+        check(lib().tcv_problem_evaluate(self.h, C.byref(o), C.byref(cost), dptr(r) if residuals else None, dptr(g) if gradient else None, dptr(fam)))
+        return dict(cost=cost.value, family_cost=fam, residuals=r, gradient=g)
 
     def plan_stats(self):
         out = np.zeros(16, np.int32)
@@ -513,6 +551,38 @@ class Batch:
 
     def marginalize(self, stream=None):
         check(lib().tcv_batch_marginalize(self.h, stream))
+
+    def evaluate(self, at="initial", apply_loss_function=True, residuals=False, gradient=False, block_costs=False, stream=None):
+        """tcv_batch_evaluate: Problem::Evaluate for every window, asynchronous on `stream`; read the results with `evaluation` /
+        `evaluation_costs`."""
+        self._eval_opts = evaluate_options(at, apply_loss_function, residuals, gradient, block_costs)
+        check(lib().tcv_batch_evaluate(self.h, C.byref(self._eval_opts), stream))
+
+    def evaluation_dims(self, window):
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        check(lib().tcv_batch_evaluation_dims(self.h, window, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(num_residuals=a.value, num_residual_blocks=b.value, num_local=c.value)
+
+    def evaluation(self, window):
+        """the last evaluation of one window (waits for it): dict(cost, family_cost (4), gradient_max_norm, residuals, block_costs,
+        gradient); the arrays the evaluation was not asked for are None"""
+        d = self.evaluation_dims(window)
+        o = self._eval_opts
+        cost, gmax = C.c_double(), C.c_double()
+        fam = np.zeros(4)
+        r = np.zeros(d["num_residuals"]) if o.want_residuals else None
+        bc = np.zeros(d["num_residual_blocks"]) if o.want_block_costs else None
+        g = np.zeros(d["num_local"]) if o.want_gradient else None
+        check(lib().tcv_batch_get_evaluation(self.h, window, C.byref(cost), dptr(fam), C.byref(gmax), dptr(r) if r is not None else None, 0 if r is None else len(r),
+                                             dptr(bc) if bc is not None else None, 0 if bc is None else len(bc), dptr(g) if g is not None else None, 0 if g is None else len(g)))
+        return dict(cost=cost.value, family_cost=fam, gradient_max_norm=gmax.value, residuals=r, block_costs=bc, gradient=g)
+
+    def evaluation_costs(self):
+        """every window's scalars in one device round trip: cost (n,), family_cost (n, 4), gradient_max_norm (n,)"""
+        n = len(self.windows)
+        cost = np.zeros(n); fam = np.zeros((n, 4)); gmax = np.zeros(n)
+        check(lib().tcv_batch_get_evaluation_costs(self.h, dptr(cost), dptr(fam), dptr(gmax), n))
+        return cost, fam, gmax
 
     def marg_status(self):
         out = np.zeros(len(self.windows), np.int32)
