@@ -195,7 +195,7 @@ enum { SCR_HP = 8256, SCR_SQ = 16 * 225, SCR_LM = 1024 };      // the landmark/c
 template <int NT>
 __device__ __forceinline__ void ctx_scratch_layout(Ctx<NT> &C, gbl_d *scr) {
     C.v_s = scr; C.v_g = scr + SCR_NL; C.v_D = scr + 2 * SCR_NL; C.v_ghat = scr + 3 * SCR_NL; C.v_y = scr + 4 * SCR_NL;
-    C.v_p = scr + 5 * SCR_NL; C.v_rc = scr + 6 * SCR_NL; C.v_sd = scr + 7 * SCR_NL;
+    C.v_p = scr + 5 * SCR_NL; C.v_rc = scr + 6 * SCR_NL; C.v_sd = scr + 7 * SCR_NL;      // (v_p: unused since the Plus forms the step itself, dogleg_p)
     C.l_hll = scr + 8 * SCR_NL; C.l_gl = C.l_hll + SCR_LM; C.l_invk = C.l_gl + SCR_LM;
     C.g_hp = C.l_invk + SCR_LM; C.g_pr = C.g_hp + SCR_HP; C.g_pdx = C.g_pr + 128;
     C.g_sqrt = C.g_pdx + 128;
@@ -2052,6 +2052,35 @@ __device__ __noinline__ bool chain_backward(TCV_CTX_PARAMS) {
     return __ballot(bad) == 0ull;
 }
 
+// Coupling of one landmark with the camera vector: t = sum over its slots k, in slot order, of h[6 k + e] * w[off_k + e], w = ycam or sc o ycam.
+// Four slots per trip: slot indices clamped to the landmark's last slot and the couplings masked to zero afterwards (a conditional load
+// gets a wait of its own, chain_entry_fetch), so that every load of the group is in flight before the first FMA instead of one global
+// round trip per slot.  (0 * w + t == t: w is a finite entry of the landmark's own last slot, or the sum is NaN either way.)
+template <bool SCALED>
+__device__ __forceinline__ double lm_slot_dot(const gbl_d *h, cst_i *so, int s0, int s1, const lds_d *sc, const lds_d *ycam) {
+    double t = 0;
+    for (int s = s0; s < s1; s += 4) {
+        int off[4];
+        double hv[4][6], w[4][6];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int sj = min(s + j, s1 - 1);
+            off[j] = so[sj];
+#pragma unroll
+            for (int e = 0; e < 6; e++) hv[j][e] = h[(sj - s0) * 6 + e];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int e = 0; e < 6; e++) w[j][e] = SCALED ? sc[off[j] + e] * ycam[off[j] + e] : ycam[off[j] + e];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int e = 0; e < 6; e++) t += ((s + j < s1) ? hv[j][e] : 0.0) * w[j][e];
+    }
+    return t;
+}
+
 // ---- scale, regularise, factorise and solve (J'J + mu D^2) y = J'r ---------------------------------
 // On return (true): v_y = y (scaled space, camera then landmarks), v_D, v_ghat set, scal = {gg, q}.
 struct FinOut { double gg, q; bool ok; };
@@ -2100,17 +2129,12 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) FinOut finalize_and_
     if (ABL(C, AB_FIN_SCALE)) {
         cst_i *lm = ip + P.o_lm, *sp = ip + P.o_lmslotptr, *so = ip + P.o_lmslot;
         for (int l = tid; l < L; l += NT) {
-            const gbl_d *h = C.g_hcl + lm[2 * l];
-            double t = 0;
-            const int s0 = sp[l], s1 = sp[l + 1];
-            for (int s = s0; s < s1; s++) {
-                const int off = so[s];
-#pragma unroll
-                for (int e = 0; e < 6; e++) t += h[(s - s0) * 6 + e] * C.ycam[off + e];
-            }
-            const double gh = C.v_ghat[nc + l];
-            const double ul = C.v_s[nc + l] * gh / C.v_D[nc + l];
-            acc[1] += t * t * C.l_invk[l] + 2.0 * t * ul + C.l_hll[l] * ul * ul;
+            const int ho = lm[2 * l], s0 = sp[l], s1 = sp[l + 1];
+            // (the landmark's own values are loaded with its slot table: one round trip, then the slots)
+            const double gh = C.v_ghat[nc + l], sl = C.v_s[nc + l], D = C.v_D[nc + l], ik = C.l_invk[l], hll = C.l_hll[l];
+            const double t = lm_slot_dot<false>(C.g_hcl + ho, so, s0, s1, C.sc, C.ycam);
+            const double ul = sl * gh / D;
+            acc[1] += t * t * ik + 2.0 * t * ul + hll * ul * ul;
             acc[0] += gh * gh;
         }
     }
@@ -2189,15 +2213,10 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) FinOut finalize_and_
     if ((!CHAIN || tid >= 64) && ABL(C, AB_LM_BACK)) {
         cst_i *lm = ip + P.o_lm, *sp = ip + P.o_lmslotptr, *so = ip + P.o_lmslot;
         for (int l = l_first; l < L; l += l_step) {
-            const gbl_d *h = C.g_hcl + lm[2 * l];
-            double t = 0;
-            const int s0 = sp[l], s1 = sp[l + 1];
-            for (int s = s0; s < s1; s++) {
-                const int off = so[s];
-#pragma unroll
-                for (int e = 0; e < 6; e++) t += h[(s - s0) * 6 + e] * (C.sc[off + e] * C.ycam[off + e]);
-            }
-            const double y = (C.l_gl[l] - t) * C.l_invk[l] / C.v_s[nc + l];
+            const int ho = lm[2 * l], s0 = sp[l], s1 = sp[l + 1];
+            const double gl = C.l_gl[l], ik = C.l_invk[l], sl = C.v_s[nc + l];
+            const double t = lm_slot_dot<true>(C.g_hcl + ho, so, s0, s1, C.sc, C.ycam);
+            const double y = (gl - t) * ik / sl;
             C.v_y[nc + l] = y;
             if (!(fabs(y) < 1e300)) bad = true;
         }
@@ -2218,30 +2237,40 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) FinOut finalize_and_
 }
 
 // ---- ambient-space helpers ---------------------------------------------------------------------------
+// element i of the dogleg step in scaled-J space, p = ca * (ghat / D) + cb * y, from the three scratch vectors
+__device__ __forceinline__ double dogleg_p(const gbl_d *v_s, int i, double ca, double cb) {
+    const double gh = (v_s + 3 * SCR_NL)[i], D = (v_s + 2 * SCR_NL)[i], y = (v_s + 4 * SCR_NL)[i];
+    return ca * (gh / D) + cb * y;
+}
 template <int NT>
-__device__ __noinline__ void apply_plus(TCV_CTX_PARAMS, const lds_d *x, const gbl_d *delta_scaled, const gbl_d *s, lds_d *xo) {
+__device__ __noinline__ void apply_plus(TCV_CTX_PARAMS, const lds_d *x, double ca_, double cb_, lds_d *xo) {
     Ctx<NT> C = ctx_from_args<NT>(TCV_CTX_FORWARD);
-    // delta = step o scale; per block Plus (pose_local_parameterization.cpp:3-19) or x + delta
+    // delta = step o scale; per block Plus (pose_local_parameterization.cpp:3-19) or x + delta.  The step is formed here from ghat, D and y
+    // (dogleg_p): stored to v_p by the kernel and read back it cost a store, a barrier and a memory round trip per iteration
     cst_plan &P = *C.P;
     cst_i *blk = C.ip + P.o_blk;
+    const double ca = uni_d(ca_), cb = uni_d(cb_);
+    const gbl_d *s = C.v_s;
     for (int b = C.tid; b < P.nblk; b += NT) {
         const int gs = blk[b * 4], go = blk[b * 4 + 1], lo = blk[b * 4 + 2], kind = blk[b * 4 + 3];
         if (lo < 0) {
             for (int i = 0; i < gs; i++) xo[go + i] = x[go + i];
         } else if (kind == KIND_POSE) {
-            double d[6], xv[7], ov[7];
+            double d[6], pv[6], xv[7], ov[7];
 #pragma unroll
-            for (int i = 0; i < 6; i++) d[i] = delta_scaled[lo + i] * s[lo + i];
+            for (int i = 0; i < 6; i++) pv[i] = dogleg_p(s, lo + i, ca, cb);
+#pragma unroll
+            for (int i = 0; i < 6; i++) d[i] = pv[i] * s[lo + i];
 #pragma unroll
             for (int i = 0; i < 7; i++) xv[i] = x[go + i];
             pose_plus(xv, d, ov);
 #pragma unroll
             for (int i = 0; i < 7; i++) xo[go + i] = ov[i];
         } else {
-            for (int i = 0; i < gs; i++) xo[go + i] = x[go + i] + delta_scaled[lo + i] * s[lo + i];
+            for (int i = 0; i < gs; i++) { const double pi = dogleg_p(s, lo + i, ca, cb); xo[go + i] = x[go + i] + pi * s[lo + i]; }
         }
     }
-    for (int l = C.tid; l < P.nland; l += NT) xo[P.nx + l] = x[P.nx + l] + delta_scaled[P.nc + l] * s[P.nc + l];
+    for (int l = C.tid; l < P.nland; l += NT) { const double pl = dogleg_p(s, P.nc + l, ca, cb); xo[P.nx + l] = x[P.nx + l] + pl * s[P.nc + l]; }
 }
 
 struct Norms2 { double xn2, dn2; };      // returned in registers: reference outputs of a non-inlined function live in scratch memory
@@ -2426,33 +2455,82 @@ __global__ void __launch_bounds__(NT) __attribute__((disable_tail_calls)) __attr
         if (P.prior_n > 0 && ABL(C, AB_SETUP)) {
             const int n = P.prior_n, nr = n - W->prior_k0;      // J0 without its leading zero rows: nr x n, column-major (tcv_packed.h)
             cst_d *J0g = C.dp + W->d_prior;
-            const bool in_lds = nr * n <= (C.ntiles << 8) + (CHAIN ? P.c_pool : 0);
-            if (in_lds) copy_doubles<NT>(lds, J0g, nr * n, tid);
-            __syncthreads();
-            for (int e = tid; e < n * (n + 1) / 2; e += NT) {      // packed index e = a (a + 1) / 2 + b, b <= a: every lane has an entry
-                int a = (int)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
-                while ((a + 1) * (a + 2) / 2 <= e) a++;
-                while (a * (a + 1) / 2 > e) a--;
-                const int b = e - a * (a + 1) / 2;
-                double s0 = 0, s1 = 0;
-                if (in_lds) {
-                    // (two accumulators by row parity, rows ascending: dropping the zero rows leaves each chain's non-zero terms in their
-                    // order -- an odd number of dropped rows only swaps the names of the two chains -- so s0 + s1 keeps its bits)
-                    const lds_d *ca = lds + nr * a, *cb = lds + nr * b;
-                    int i = 0;
-                    for (; i + 7 < nr; i += 8) {      // eight rows' loads in flight, the two accumulators updated in the original order
-                        double a8[8], b8[8];
+            const int lds_cap = (C.ntiles << 8) + (CHAIN ? P.c_pool : 0);
+            const bool in_lds = nr * n <= lds_cap;
+            // J0 in LDS: every lane forms 2 x 2 blocks of entries (columns 2a, 2a+1 against 2b, 2b+1, b <= a), so that four loaded values feed
+            // four FMAs.  The blocks of the lower triangle are enumerated as a rectangle -- block row r carries row r and, behind it, row
+            // nb - 1 - r: nb + 1 blocks each -- and the columns are staged with an odd stride where that fits (lanes of a wave read the same
+            // row of different columns).  Every entry keeps the sum it had entry by entry: two accumulators by row parity, rows ascending,
+            // s0 + s1 last (dropping the zero rows leaves each accumulator's non-zero terms in their order -- an odd number of dropped rows
+            // only swaps the names of the two -- so the sum keeps its bits).
+            if (in_lds) {
+                const int ldj = ((nr | 1) * n <= lds_cap) ? (nr | 1) : nr, tot = nr * n;
+                if (tot > 0) {
+                    int c = tid / nr, i = tid - c * nr;
+                    const int dc = NT / nr, di = NT - dc * nr;
+                    for (int idx = tid; idx < tot; idx += 8 * NT) {      // eight loads in flight per trip
+                        double v[8];
+                        int o[8];
 #pragma unroll
-                        for (int u = 0; u < 8; u++) { a8[u] = ca[i + u]; b8[u] = cb[i + u]; }
+                        for (int k = 0; k < 8; k++) {
+                            v[k] = J0g[min(idx + k * NT, tot - 1)];
+                            o[k] = c * ldj + i;
+                            c += dc; i += di;
+                            if (i >= nr) { i -= nr; c++; }
+                        }
 #pragma unroll
-                        for (int u = 0; u < 8; u += 2) { s0 += a8[u] * b8[u]; s1 += a8[u + 1] * b8[u + 1]; }
+                        for (int k = 0; k < 8; k++) if (idx + k * NT < tot) lds[o[k]] = v[k];
                     }
-                    for (; i + 1 < nr; i += 2) { s0 += ca[i] * cb[i]; s1 += ca[i + 1] * cb[i + 1]; }
-                    if (nr & 1) s0 += ca[nr - 1] * cb[nr - 1];
-                } else {
-                    for (int i = 0; i < nr; i++) s0 += J0g[i + nr * a] * J0g[i + nr * b];
                 }
-                C.g_hp[a * (a + 1) / 2 + b] = s0 + s1;
+                __syncthreads();
+                const int nb = (n + 1) >> 1, nrect = ((nb + 1) >> 1) * (nb + 1);
+                for (int e = tid; e < nrect; e += NT) {
+                    const int r = e / (nb + 1), cc = e - r * (nb + 1);
+                    if (cc > r && nb - 1 - r == r) continue;      // odd nb: the middle row stands alone
+                    const int bA = cc <= r ? r : nb - 1 - r, bB = cc <= r ? cc : cc - r - 1;
+                    const int a0 = 2 * bA, a1 = min(a0 + 1, n - 1), b0 = 2 * bB, b1 = min(b0 + 1, n - 1);      // (a clamped column is formed and not stored)
+                    const lds_d *pa0 = lds + ldj * a0, *pa1 = lds + ldj * a1, *pb0 = lds + ldj * b0, *pb1 = lds + ldj * b1;
+                    double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};      // entries (a0, b0), (a0, b1), (a1, b0), (a1, b1)
+                    int i = 0;
+                    for (; i + 3 < nr; i += 4) {      // four rows' loads in flight, the accumulators updated in row order
+                        double x0[4], x1[4], y0[4], y1[4];
+#pragma unroll
+                        for (int u = 0; u < 4; u++) { x0[u] = pa0[i + u]; x1[u] = pa1[i + u]; y0[u] = pb0[i + u]; y1[u] = pb1[i + u]; }
+#pragma unroll
+                        for (int u = 0; u < 4; u += 2) {
+                            s0[0] += x0[u] * y0[u]; s1[0] += x0[u + 1] * y0[u + 1];
+                            s0[1] += x0[u] * y1[u]; s1[1] += x0[u + 1] * y1[u + 1];
+                            s0[2] += x1[u] * y0[u]; s1[2] += x1[u + 1] * y0[u + 1];
+                            s0[3] += x1[u] * y1[u]; s1[3] += x1[u + 1] * y1[u + 1];
+                        }
+                    }
+                    for (; i + 1 < nr; i += 2) {
+                        const double x00 = pa0[i], x01 = pa0[i + 1], x10 = pa1[i], x11 = pa1[i + 1], y00 = pb0[i], y01 = pb0[i + 1], y10 = pb1[i], y11 = pb1[i + 1];
+                        s0[0] += x00 * y00; s1[0] += x01 * y01;
+                        s0[1] += x00 * y10; s1[1] += x01 * y11;
+                        s0[2] += x10 * y00; s1[2] += x11 * y01;
+                        s0[3] += x10 * y10; s1[3] += x11 * y11;
+                    }
+                    if (nr & 1) {
+                        const double x0 = pa0[nr - 1], x1 = pa1[nr - 1], y0 = pb0[nr - 1], y1 = pb1[nr - 1];
+                        s0[0] += x0 * y0; s0[1] += x0 * y1; s0[2] += x1 * y0; s0[3] += x1 * y1;
+                    }
+                    const bool has_a1 = a0 + 1 < n, has_b1 = b0 + 1 < n;
+                    C.g_hp[a0 * (a0 + 1) / 2 + b0] = s0[0] + s1[0];
+                    if (has_b1 && bB < bA) C.g_hp[a0 * (a0 + 1) / 2 + b0 + 1] = s0[1] + s1[1];      // (on the diagonal block that entry is above the diagonal)
+                    if (has_a1) C.g_hp[(a0 + 1) * (a0 + 2) / 2 + b0] = s0[2] + s1[2];
+                    if (has_a1 && has_b1) C.g_hp[(a0 + 1) * (a0 + 2) / 2 + b0 + 1] = s0[3] + s1[3];
+                }
+            } else {
+                for (int e = tid; e < n * (n + 1) / 2; e += NT) {      // J0 does not fit: entry by entry from global memory, packed index e = a (a + 1) / 2 + b, b <= a
+                    int a = (int)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
+                    while ((a + 1) * (a + 2) / 2 <= e) a++;
+                    while (a * (a + 1) / 2 > e) a--;
+                    const int b = e - a * (a + 1) / 2;
+                    double s0 = 0;
+                    for (int i = 0; i < nr; i++) s0 += J0g[i + nr * a] * J0g[i + nr * b];
+                    C.g_hp[a * (a + 1) / 2 + b] = s0 + 0.0;      // (+ 0.0 as before, when the second accumulator of the LDS path was added here too)
+                }
             }
         }
         __syncthreads();
@@ -2580,11 +2658,11 @@ __global__ void __launch_bounds__(NT) __attribute__((disable_tail_calls)) __attr
             }
             invalid = 0;
             TCV_MARK(C, PH_DOGLEG);
-            for (int i = tid; i < nl; i += NT) (K.v_s + 5 * SCR_NL)[i] = ca * ((K.v_s + 3 * SCR_NL)[i] / (K.v_s + 2 * SCR_NL)[i]) + cb * (K.v_s + 4 * SCR_NL)[i];
-            __syncthreads();
-            if (ABL(C, AB_PLUS)) apply_plus<NT>(TCV_CTX_ARGS(K), K.xs, K.v_s + 5 * SCR_NL, K.v_s, K.xc);
+            // the step p = ca * (ghat / D) + cb * y is formed where it is used, from the vectors finalize_and_solve left behind its barriers:
+            // no store of v_p, no barrier and no read-back in front of the Plus
+            if (ABL(C, AB_PLUS)) apply_plus<NT>(TCV_CTX_ARGS(K), K.xs, ca, cb, K.xc);
             if (A.first_delta && it == 1)
-                for (int i = tid; i < nl; i += NT) A.first_delta[(size_t)win * A.delta_stride + i] = (K.v_s + 5 * SCR_NL)[i] * K.v_s[i];
+                for (int i = tid; i < nl; i += NT) { const double pi = dogleg_p(K.v_s, i, ca, cb); A.first_delta[(size_t)win * A.delta_stride + i] = pi * K.v_s[i]; }
             __syncthreads();
             TCV_MARK(C, PH_PLUS);
             const double mu_next = uni_d(fmax(1e-8, 2.0 * mu / 10.0));
