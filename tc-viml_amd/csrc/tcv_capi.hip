@@ -534,11 +534,9 @@ extern "C" int tcv_problems_pack_bench(tcv_problem *const *problems, int n, int 
     for (int b = 0; b < n; b += frame) {
         const int m = std::min(frame, n - b), nth = std::max(1, std::min(threads, m));
         std::vector<Packed> packed(m);
-        auto one = [&](int w) {
+        tcv::parallel_items(m, nth, [&](int w, int) {
             err.note(b + w, b + w, pack_problem(*problems[b + w], packed[w], nullptr, g_solver_variant, coop_chunks > 0 ? (int)LDS_DOUBLES : 0, true, coop_chunks));
-        };
-        if (getenv("TCV_PACK_BENCH_STRIDED")) tcv::parallel_run(nth, [&](int t) { for (int w = t; w < m; w += nth) one(w); });      // (a fixed share per thread: up to round 5)
-        else tcv::parallel_items(m, nth, [&](int w, int) { one(w); });
+        });
     }
     *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (getenv("TCV_DEBUG_PACK2")) tcv::pack_laps_print();

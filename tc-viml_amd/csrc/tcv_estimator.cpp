@@ -24,7 +24,7 @@
 #include "../../include/tcv_estimator.h"
 namespace tcv { hipStream_t util_stream(); hipStream_t aux_stream(); }      // (tcv_capi.hip: the calling thread's utility stream and its second stream)
 #include <functional>
-#include "tcv_packed.h"      // parallel_run, HostOp: the persistent host worker threads of the packer
+#include "tcv_hostpool.h"      // parallel_items, async_run, HostOp: the persistent host worker threads
 
 namespace tcv { void set_error(const std::string &s); }
 int tcv_marg_layout_n(const tcv_batch *b, int window);      // (tcv_marg.hip: n of the prior a window's attached marginalisation problem makes, known before the kernel runs)

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -14,6 +15,7 @@
 
 #include "../../include/tcv.h"
 #include "tcv_packed.h"
+#include "tcv_hostpool.h"
 
 namespace tcv {
 // a device allocation shared between its producer (a batch) and the handles that still read it (device-resident priors)
@@ -76,10 +78,7 @@ struct ProjFac { double pts[6]; double sqrt_info, loss_a; int b[4]; double aux[8
 struct LineFac { double d[9]; double K[9], R[9], T[3]; double loss_a; int b; };
 struct PriorFac { const tcv_prior *prior; std::vector<int> b; };
 
-// Int pools of the plans (~170 KB per window) come from a process-wide free list of power-of-two blocks: a malloc of that size is a fresh
-// mmap whose pages fault in on first touch (~100 us per plan, as much as building it); a live estimator makes and drops one per frame.
-void *plan_block_alloc(size_t bytes);
-void plan_block_free(void *p, size_t bytes);
+// allocator of the plans' int pools: blocks of the process-wide free list (tcv_hostpool.h)
 template <class T> struct PlanAlloc {
     typedef T value_type;
     PlanAlloc() = default;
@@ -266,6 +265,24 @@ void set_error(const std::string &s);
 // coop_chunks > 0: plan for the cooperative (small-batch) kernel with at least that many visual chunks (tcv_packed.h COOP_*)
 int pack_problem(const tcv_problem &p, Packed &out, const double *imu_sqrt, int mode = 0, int chain_lds = 0, bool plan_only = false, int coop_chunks = 0);
 int pack_problem_data(const tcv_problem &p, Packed &out, const double *imu_sqrt, double *dst);
+// Where the doubles of a window go: a Sink counts (no destination), writes into a buffer that was sized by a counting pass (the solve
+// windows: all of a batch straight into one upload buffer), or appends to a vector (the marginalisation problems).
+struct Sink {
+    double *dst = nullptr;
+    std::vector<double> *vec = nullptr;
+    size_t n = 0;
+    explicit Sink(double *d) : dst(d) {}
+    explicit Sink(std::vector<double> &v) : vec(&v) {}
+    void put(const double *s, size_t k) { if (vec) vec->insert(vec->end(), s, s + k); else if (dst) std::memcpy(dst + n, s, k * sizeof(double)); n += k; }
+    void put1(double v) { if (vec) vec->push_back(v); else if (dst) dst[n] = v; n++; }
+    void zeros(size_t k) { if (vec) vec->insert(vec->end(), k, 0.0); else if (dst) std::memset(dst + n, 0, k * sizeof(double)); n += k; }
+};
+// The record layouts that the solve and the marginalisation kernels both read (the marginalisation reads the solve batch's copy where it
+// can: MargHdr::imu_abs, prior_abs), each with its one host writer (tcv_pack.cpp); prior_splice_kernel writes the first two on the device.
+void put_imu_const(Sink &D, const tcv_imu_preintegration &q);      // IMU_CONST doubles: [dp 3 | dq 4 | dv 3 | ba 3 | bg 3 | sum_dt | dp_dba dp_dbg dq_dbg dv_dba dv_dbg 9 each | covariance 225]
+void put_prior_region(Sink &D, const tcv_prior &pr, int k0);       // J0 rows k0 .. n - 1 (column-major) | r0[k0 ..] | x0; the prior is on the host (tcv_prior_host)
+// one projection record [pts 6 | aux 8 (ProjectionTdFactor only)]; `first` is the window's first record, whose sqrt_info and loss all share
+int put_proj_record(Sink &D, const ProjFac &f, const ProjFac &first);
 // pinned host staging buffers for uploads / downloads, recycled through a small per-process pool (hipHostMalloc costs milliseconds)
 void *host_staging_acquire(size_t bytes);
 void host_staging_release(void *p);

@@ -12,7 +12,6 @@
 #include <vector>
 
 #include "tcv_host.h"
-#include "tcv_packed.h"      // parallel_run, host_threads
 #include "tcv_math.h"
 
 namespace tcv {

@@ -2088,6 +2088,7 @@ static int pack_marg(const tcv_problem &p, double *const *drop, int ndrop, const
     H.d_x = dmark();
     for (int c = 0; c < nblk; c++) { const ParamBlock &pb = p.blocks[orig[c]]; D.insert(D.end(), pb.addr, pb.addr + pb.size); }
     H.d_imu = dmark();
+    Sink DS(D);      // the records shared with the solve windows: one writer each (tcv_host.h)
     // the factor's constants are the solve problem's (same pre-integration): the kernel reads them from the solve batch's pool
     H.imu_abs = -1;
     if (H.sqrt_src >= 0 && solve_pk && !getenv("TCV_MARG_OWN_IMU")) H.imu_abs = solve_pk->win.dbase + solve_pk->win.d_imu + (long long)H.sqrt_src * IMU_CONST;
@@ -2095,33 +2096,23 @@ static int pack_marg(const tcv_problem &p, double *const *drop, int ndrop, const
         if (H.imu_abs >= 0) break;
         if (f.dev) { if (int rc = tcv_preint_host(f.dev)) return rc; }      // (no shared copy to read from: the numbers are needed here)
         const tcv_imu_preintegration &q = f.dev ? f.dev->pod : f.pre;
-        D.insert(D.end(), q.delta_p, q.delta_p + 3); D.insert(D.end(), q.delta_q, q.delta_q + 4);
-        D.insert(D.end(), q.delta_v, q.delta_v + 3); D.insert(D.end(), q.linearized_ba, q.linearized_ba + 3);
-        D.insert(D.end(), q.linearized_bg, q.linearized_bg + 3); D.push_back(q.sum_dt);
-        const int rc[5][2] = {{0, 9}, {0, 12}, {3, 12}, {6, 9}, {6, 12}};
-        for (auto &b : rc) for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) D.push_back(q.jacobian[(b[0] + i) * 15 + b[1] + j]);
-        D.insert(D.end(), q.covariance, q.covariance + 225);
+        put_imu_const(DS, q);
     }
     H.d_proj = dmark();
-    double psi = 0, pla = 0;
     for (size_t k = 0; k < p.proj.size(); k++) {
         const ProjFac &f = p.proj[porder[k]];
-        if (k == 0) { psi = f.sqrt_info; pla = f.loss_a; }
-        else if (f.sqrt_info != psi || f.loss_a != pla) { set_error("projection factors must share sqrt_info and loss"); return TCV_ERR_UNSUPPORTED; }
+        if (int rc = put_proj_record(DS, f, p.proj[porder[0]])) return rc;
         if (p.blocks[f.b[3]].size != 1) { set_error("projection factor: 4th block must be an inverse depth"); return TCV_ERR_UNSUPPORTED; }
-        D.insert(D.end(), f.pts, f.pts + 6);
-        if (f.btd >= 0) D.insert(D.end(), f.aux, f.aux + 8);
     }
+    const double psi = p.proj.empty() ? 0.0 : p.proj[porder[0]].sqrt_info, pla = p.proj.empty() ? 0.0 : p.proj[porder[0]].loss_a;
     H.d_prior = dmark();
     H.prior_abs = -1;
     if (pr && solve_p && solve_pk && !solve_p->prior.empty() && solve_p->prior[0].prior == pr && solve_pk->hdr.prior_n == pr->n && !getenv("TCV_MARG_OWN_PRIOR"))
-        { H.prior_abs = solve_pk->win.dbase + solve_pk->win.d_prior; H.prior_k0 = solve_pk->prior_k0_deferred ? -1 : solve_pk->win.prior_k0; }      // same layout: J0 | r0 | x0 without the leading zero rows (tcv_pack.cpp)
+        { H.prior_abs = solve_pk->win.dbase + solve_pk->win.d_prior; H.prior_k0 = solve_pk->prior_k0_deferred ? -1 : solve_pk->win.prior_k0; }      // the same record: put_prior_region, or the splice kernel's copy of it
     else if (pr) {
         if (int rc = tcv_prior_host(pr)) return rc;      // (a device-resident prior that the solve problem does not share: its numbers are needed here)
-        const int n0 = pr->n, k0 = prior_keep_zero_rows() ? 0 : prior_zero_rows(pr->J0.data(), pr->r0.data(), n0);
-        H.prior_k0 = k0;
-        for (int j = 0; j < n0; j++) D.insert(D.end(), pr->J0.begin() + (size_t)n0 * j + k0, pr->J0.begin() + (size_t)n0 * (j + 1));
-        D.insert(D.end(), pr->r0.begin() + k0, pr->r0.end()); D.insert(D.end(), pr->x0.begin(), pr->x0.end());
+        H.prior_k0 = prior_keep_zero_rows() ? 0 : prior_zero_rows(pr->J0.data(), pr->r0.data(), pr->n);
+        put_prior_region(DS, *pr, H.prior_k0);
     }
     H.d_misc = dmark();
     D.insert(D.end(), p.G, p.G + 3); D.push_back(psi); D.push_back(pla); D.push_back(0.0); D.push_back(p.td_TR); D.push_back(p.td_ROW);

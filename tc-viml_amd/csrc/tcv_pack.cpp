@@ -1,7 +1,6 @@
 // Packer: ceres::Problem-shaped graph (estimator.cpp:1679-1886) -> device plan + window data
 // (tcv_packed.h).  Everything structural that the reference redoes per frame through
 // AddParameterBlock / AddResidualBlock pointer chasing is resolved here, once, into flat gather lists.
-#include <sched.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -11,228 +10,12 @@
 #include <list>
 #include <map>
 #include <mutex>
-#include <functional>
-#include <deque>
-#include <condition_variable>
-#include <thread>
 #include <tuple>
 #include <unordered_map>
 
 #include "tcv_host.h"
 
 namespace tcv {
-
-// ---- host thread budget (HostOp, tcv_packed.h)
-static int host_core_grant_probe() {
-    int g = (int)std::thread::hardware_concurrency();
-    if (g <= 0) g = 1;
-#if defined(__linux__)
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof set, &set) == 0) { const int c = CPU_COUNT(&set); if (c > 0) g = std::min(g, c); }
-    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {      // cgroup v2: "<quota> <period>" or "max <period>"
-        char q[64]; long long per = 0;
-        if (fscanf(f, "%63s %lld", q, &per) == 2 && per > 0 && strcmp(q, "max") != 0) { const long long quota = atoll(q); if (quota > 0) g = std::min<long long>(g, std::max<long long>(1, (quota + per - 1) / per)); }
-        fclose(f);
-    } else if (FILE *f1 = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) {      // cgroup v1
-        long long quota = -1, per = 0;
-        if (fscanf(f1, "%lld", &quota) != 1) quota = -1;
-        fclose(f1);
-        if (FILE *f2 = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) { if (fscanf(f2, "%lld", &per) != 1) per = 0; fclose(f2); }
-        if (quota > 0 && per > 0) g = std::min<long long>(g, std::max<long long>(1, (quota + per - 1) / per));
-    }
-#endif
-    if (const char *e = getenv("TCV_HOST_THREADS")) { const int v = atoi(e); if (v > 0) g = v; }
-    return std::max(1, g);
-}
-static int host_core_grant() {
-    static const int grant = host_core_grant_probe();      // (once: several host threads ask at the same time)
-    return grant;
-}
-static std::atomic<int> g_host_ops{0};
-HostOp::HostOp() { g_host_ops.fetch_add(1, std::memory_order_relaxed); }
-HostOp::~HostOp() { g_host_ops.fetch_sub(1, std::memory_order_relaxed); }
-int host_threads(int want) {
-    const int active = std::max(1, g_host_ops.load(std::memory_order_relaxed));
-    return std::max(1, std::min(want, std::max(1, host_core_grant() / active)));
-}
-int HostOp::threads(int want) const { return host_threads(want); }
-
-// ---- persistent worker threads (parallel_run, tcv_packed.h) ------------------------------------------------------------------
-// A batch-level call has three or four short parallel sections (plans, data, marginalisation problems, copies): 16 std::thread
-// creations and joins per section were ~2 ms of a 512-window tcv_batch_create.  The workers are created once (up to the core grant
-// minus the caller), sleep on a condition variable and claim task indices of the posted calls; the CALLER claims indices too, so a call
-// makes progress whatever the workers are busy with, and returns when every index has finished.  The pool object is never destroyed
-// (the detached workers may outlive static destruction).
-namespace {
-struct ParCall {
-    const std::function<void(int)> *fn;
-    std::function<void(int)> own;      // async_run: the call owns its function (nobody waits for it)
-    int n;
-    std::atomic<int> next{0}, done{0};
-    std::mutex mu;
-    std::condition_variable cv;
-};
-struct WorkerPool {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::shared_ptr<ParCall>> q;
-    int nworkers = 0;
-    std::atomic<unsigned> posted{0};      // calls pushed so far: what a worker polls before it goes to sleep
-    std::atomic<int> sleepers{0};         // workers inside cv.wait: a post with nobody asleep skips the futex
-};
-WorkerPool &worker_pool() { static WorkerPool *P = new WorkerPool(); return *P; }
-// TCV_WORKER_SPIN_US = t > 0: a worker that has just finished a section polls for the next one for t microseconds before it sleeps on the
-// condition variable, and the caller polls for its last task the same way (a lock-step frame is a burst of short parallel sections a few
-// microseconds apart).  Measured on the 2 x 64-core host at 8 / 64 / 128 replay streams with t = 40 and 150: the same windows/s within the
-// run-to-run spread and 15 - 40 % more CPU time (profiles/r05_replay_host_workers.txt) -- so the default is 0: sleep at once.
-int worker_spin_us() {
-    static const int us = [] { const char *e = getenv("TCV_WORKER_SPIN_US"); const int v = e ? atoi(e) : 0; return std::max(0, std::min(v, 2000)); }();
-    return us;
-}
-inline void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#else
-    std::this_thread::yield();
-#endif
-}
-void run_call(ParCall &c) {
-    for (;;) {
-        const int t = c.next.fetch_add(1, std::memory_order_relaxed);
-        if (t >= c.n) return;
-        (*c.fn)(t);
-        if (c.done.fetch_add(1, std::memory_order_acq_rel) + 1 == c.n) { std::lock_guard<std::mutex> g(c.mu); c.cv.notify_all(); }
-    }
-}
-void worker_main() {
-    WorkerPool &P = worker_pool();
-    unsigned seen = P.posted.load(std::memory_order_acquire);
-    for (;;) {
-        std::shared_ptr<ParCall> c;
-        {
-            std::unique_lock<std::mutex> g(P.mu);
-            for (;;) {
-                while (!P.q.empty() && P.q.front()->next.load(std::memory_order_relaxed) >= P.q.front()->n) P.q.pop_front();      // fully claimed
-                if (!P.q.empty()) { c = P.q.front(); break; }
-                seen = P.posted.load(std::memory_order_acquire);
-                const int spin = worker_spin_us();
-                if (spin > 0) {      // poll outside the lock, then look again
-                    g.unlock();
-                    const auto t_end = std::chrono::steady_clock::now() + std::chrono::microseconds(spin);
-                    bool news = false;
-                    for (int it = 0;; it++) {
-                        if (P.posted.load(std::memory_order_acquire) != seen) { news = true; break; }
-                        cpu_relax();
-                        if ((it & 63) == 63 && std::chrono::steady_clock::now() >= t_end) break;
-                    }
-                    g.lock();
-                    if (news) continue;
-                    if (P.posted.load(std::memory_order_acquire) != seen) continue;
-                }
-                P.sleepers.fetch_add(1, std::memory_order_relaxed);
-                P.cv.wait(g);
-                P.sleepers.fetch_sub(1, std::memory_order_relaxed);
-            }
-        }
-        run_call(*c);
-    }
-}
-void wait_call(ParCall &c) {
-    const int spin = worker_spin_us();
-    if (spin > 0) {
-        const auto t_end = std::chrono::steady_clock::now() + std::chrono::microseconds(spin);
-        for (int it = 0;; it++) {
-            if (c.done.load(std::memory_order_acquire) >= c.n) return;
-            cpu_relax();
-            if ((it & 63) == 63 && std::chrono::steady_clock::now() >= t_end) break;
-        }
-    }
-    std::unique_lock<std::mutex> g(c.mu);
-    c.cv.wait(g, [&] { return c.done.load(std::memory_order_acquire) >= c.n; });
-}
-}  // namespace
-void parallel_run(int nth, const std::function<void(int)> &fn) {
-    if (nth <= 1) { fn(0); return; }
-    static const bool off = getenv("TCV_NO_WORKER_POOL") != nullptr;      // A/B: a thread per task, as before
-    if (off) {
-        std::vector<std::thread> th;
-        for (int t = 0; t < nth; t++) th.emplace_back(fn, t);
-        for (auto &x : th) x.join();
-        return;
-    }
-    WorkerPool &P = worker_pool();
-    auto c = std::make_shared<ParCall>();
-    c->fn = &fn; c->n = nth;
-    bool wake;
-    {
-        std::lock_guard<std::mutex> g(P.mu);
-        const int want = std::min(31, std::max(1, host_core_grant() - 1));
-        while (P.nworkers < std::min(want, nth - 1)) { std::thread(worker_main).detach(); P.nworkers++; }
-        P.q.push_back(c);
-        P.posted.fetch_add(1, std::memory_order_release);
-        wake = P.sleepers.load(std::memory_order_relaxed) > 0;
-    }
-    if (wake) P.cv.notify_all();
-    run_call(*c);
-    wait_call(*c);
-}
-
-void parallel_items(int n, int nth, const std::function<void(int, int)> &fn) {
-    if (n <= 0) return;
-    nth = std::min(nth, n);
-    if (nth <= 1) { for (int i = 0; i < n; i++) fn(i, 0); return; }
-    std::atomic<int> next{0};
-    parallel_run(nth, [&](int t) { for (;;) { const int i = next.fetch_add(1, std::memory_order_relaxed); if (i >= n) return; fn(i, t); } });
-}
-
-// ---- blocks of the plans' int pools (PlanAlloc, tcv_host.h): power-of-two size classes from 16 KB, a bounded free list per class
-namespace {
-struct BlockPool { std::mutex mu; std::vector<void *> idle[12]; };      // 16 KB .. 32 MB
-BlockPool &block_pool() { static BlockPool *p = new BlockPool(); return *p; }
-inline int block_class(size_t bytes, size_t &cap) { int c = 0; cap = (size_t)16 << 10; while (cap < bytes) { cap <<= 1; c++; } return c; }
-}  // namespace
-void *plan_block_alloc(size_t bytes) {
-    if (bytes < ((size_t)16 << 10)) return ::operator new(bytes);
-    size_t cap;
-    const int c = block_class(bytes, cap);
-    if (c < 12) {
-        BlockPool &P = block_pool();
-        std::lock_guard<std::mutex> g(P.mu);
-        if (!P.idle[c].empty()) { void *p = P.idle[c].back(); P.idle[c].pop_back(); return p; }
-    }
-    return ::operator new(cap);
-}
-void plan_block_free(void *p, size_t bytes) {
-    if (!p) return;
-    if (bytes < ((size_t)16 << 10)) { ::operator delete(p); return; }
-    size_t cap;
-    const int c = block_class(bytes, cap);
-    if (c < 12) {
-        BlockPool &P = block_pool();
-        std::lock_guard<std::mutex> g(P.mu);
-        if (P.idle[c].size() < (size_t)(c <= 5 ? 192 : 8)) { P.idle[c].push_back(p); return; }      // (<= 512 KB: the plans of a lock-step frame; larger blocks: a handful)
-    }
-    ::operator delete(p);
-}
-
-// fire and forget on the worker pool (the retired problems of a lock-step frame are destroyed this way: 0.3 ms of the caller's frame
-// at 64 windows).  Without workers -- a one-core grant -- the function runs here.
-void async_run(std::function<void()> fn) {
-    WorkerPool &P = worker_pool();
-    bool have_worker;
-    {
-        std::lock_guard<std::mutex> g(P.mu);
-        if (P.nworkers == 0 && host_core_grant() > 1) { std::thread(worker_main).detach(); P.nworkers++; }
-        have_worker = P.nworkers > 0;
-    }
-    if (!have_worker) { fn(); return; }
-    auto c = std::make_shared<ParCall>();
-    auto sp = std::make_shared<std::function<void()>>(std::move(fn));
-    c->own = [sp](int) { (*sp)(); };
-    c->fn = &c->own; c->n = 1;
-    { std::lock_guard<std::mutex> g(P.mu); P.q.push_back(c); P.posted.fetch_add(1, std::memory_order_release); }
-    P.cv.notify_one();
-}
 
 // TCV_PRIOR_FULL: keep the exact-zero rows of the prior (A/B partner of the default).  The environment is read once per batch
 // (prior_refresh_switch), not once per window.
@@ -345,7 +128,7 @@ struct RowProg {
     std::vector<int> units, items;
     int n_units = 0, n_wave_units = 0;
 };
-static bool emit_rows(const DestList &dl, RowProg &out, bool inline_items, int wave_items = WAVE_UNIT_ITEMS, int wave_max = WAVE_UNIT_MAX) {
+static bool emit_rows(const DestList &dl, RowProg &out, bool inline_items) {
     struct U { int u0, u1, u2, u3, n; };
     std::vector<U> us;
     us.reserve(dl.keys.size() * 4);
@@ -379,7 +162,7 @@ static bool emit_rows(const DestList &dl, RowProg &out, bool inline_items, int w
     for (auto &u : us) {
         out.units.push_back(u.u0); out.units.push_back(u.u1); out.units.push_back(u.u2);
         if (inline_items) out.units.push_back(u.u3);
-        if (!inline_items && u.n > wave_items && out.n_wave_units < wave_max) out.n_wave_units++;
+        if (!inline_items && u.n > WAVE_UNIT_ITEMS && out.n_wave_units < WAVE_UNIT_MAX) out.n_wave_units++;
     }
     out.n_units = (int)us.size();
     return true;
@@ -418,8 +201,6 @@ struct CamPlan {
     PlanHdr hdr;                 // the camera fields: nblk, nc, nx, npp, nt, ntp, n_imu, prior_*, n_imu_chunk, flags, td_cam, camw, chain, n_e, nt_c, c_spill,
                                  // n_frames and the o_* / n_* of the tables below
     std::vector<int> ints;       // [blk | imu | prior | pcol | idest | iunit | iitem | ichunk | pdest | chain | frames], a multiple of 4 ints
-    std::vector<int> loff;       // tangent offset of every camera block (-1 constant)
-    std::vector<int> goff;
 };
 struct CamKey {
     std::vector<int> k;
@@ -433,11 +214,51 @@ std::unordered_map<CamKey, std::shared_ptr<const CamPlan>, CamKeyHash> g_cam_cac
 long long g_cam_hits = 0, g_cam_misses = 0;
 enum { CAM_CACHE_MAX = 512 };
 
-// what the camera half is built from (filled by pack_plan's classification)
+// Sizes of the camera side: THE derivation -- the LDS budgets of the visual half, the camera half's tables and the plan header all read
+// this one result (cam_sizes).
+struct CamSizes {
+    int nblk = 0, nx = 0, nc = 0;      // camera blocks, their ambient and tangent dims
+    int npp = 0;                       // the "pose part": the leading tangent dims the visual factors touch (free poses, then Td)
+    int nt = 0, ntp = 0, nt_c = 0;     // tile rows of the augmented system (nc + 1 rhs row), tile rows covering npp, tile rows of the chain layout's pose system
+    int camw = 0, td_cam = -1;         // width of the LDS vectors over the camera tangent space; camera block of Td (-1: none)
+    std::vector<int> gsize, goff, loff, kind;      // per camera block: ambient size and offset, tangent offset (-1 constant), kind
+};
+// L: landmarks of the window (they share the solver's nl-sized vectors with the camera side)
+int cam_sizes(const tcv_problem &p, const std::vector<int> &cam_block, const std::vector<int> &cam_of, int td_blk, int L, CamSizes &S) {
+    const int nblk = S.nblk = (int)cam_block.size();
+    std::vector<int> &gsize = S.gsize, &goff = S.goff, &loff = S.loff, &kind = S.kind;
+    gsize.resize(nblk); goff.resize(nblk); loff.assign(nblk, -1); kind.resize(nblk);
+    int nx = 0, nc = 0;
+    for (int c = 0; c < nblk; c++) {
+        const ParamBlock &pb = p.blocks[cam_block[c]];
+        gsize[c] = pb.size; kind[c] = pb.kind; goff[c] = nx; nx += pb.size;
+    }
+    for (int c = 0; c < nblk; c++)
+        if (kind[c] == KIND_POSE && !p.blocks[cam_block[c]].constant) { loff[c] = nc; nc += 6; }
+    // Td comes right behind the poses: its column rides through the 6-wide gather machinery as a pseudo block whose other five
+    // columns are structural zeros, so five more tangent rows must follow it.  It counts as part of the "pose part" npp: the
+    // leading tangent dims the visual factors touch (landmark Schur corrections of the diagonal and the right-hand side).
+    const int td_cam = S.td_cam = td_blk >= 0 ? cam_of[td_blk] : -1;
+    if (td_cam >= 0 && !p.blocks[td_blk].constant) { loff[td_cam] = nc; nc += 1; }
+    const int npp = nc;
+    for (int c = 0; c < nblk; c++)
+        if (kind[c] != KIND_POSE && c != td_cam && !p.blocks[cam_block[c]].constant) { loff[c] = nc; nc += gsize[c]; }
+    S.nx = nx; S.nc = nc; S.npp = npp;
+    if (nc < 1) { set_error("no free camera-side parameter block"); return TCV_ERR_INVALID; }
+    S.nt = (nc + 1 + 15) / 16; S.ntp = (npp + 15) / 16;
+    // camera tangent dims: 171 for the 11 frames + extrinsic of OptimizationWithLine (172 with Td), 177 with the relocalisation pose (:1854-1886)
+    if (nc > CAM_MAX - 1 || npp > 88 || nc + L > SCR_NL || L > 1024) { set_error("window too large for the fused solver (camera tangent dim > 183)"); return TCV_ERR_TOO_LARGE; }
+    S.camw = nc <= CAM_W - 1 ? (int)CAM_W : (int)CAM_MAX;
+    // (Td's gather slot is six columns wide, tcv_packed.h: the pose tiles have to cover the five structural zeros behind its column)
+    S.nt_c = (std::max(npp + 1, (td_cam >= 0 && loff[td_cam] >= 0) ? loff[td_cam] + 6 : 0) + 15) / 16;
+    return TCV_OK;
+}
+
+// what the camera half is built from (filled by pack_plan's cam_for)
 struct CamIn {
     const tcv_problem *p;
     const std::vector<int> *cam_block, *cam_of;
-    int td_blk;
+    const CamSizes *sizes;
     bool want_chain;
     int per_imu;                 // IMU factors per staging chunk (a function of the LDS pool the visual half leaves: part of the key)
 };
@@ -445,32 +266,12 @@ struct CamIn {
 int build_cam(const CamIn &in, CamPlan &out) {
     const tcv_problem &p = *in.p;
     const std::vector<int> &cam_block = *in.cam_block, &cam_of = *in.cam_of;
-    const int nblk = (int)cam_block.size();
-    const int td_blk = in.td_blk;
-    std::vector<int> gsize(nblk), goff(nblk), loff(nblk, -1), kind(nblk);
-    int nx = 0, nc = 0;
-    for (int c = 0; c < nblk; c++) {
-        const ParamBlock &pb = p.blocks[cam_block[c]];
-        gsize[c] = pb.size; kind[c] = pb.kind; goff[c] = nx; nx += pb.size;
-        if (pb.kind == KIND_EUCLID && pb.size > 15) { set_error("Euclidean block wider than 15"); return TCV_ERR_UNSUPPORTED; }
-    }
+    const CamSizes &S = *in.sizes;
+    const std::vector<int> &gsize = S.gsize, &goff = S.goff, &loff = S.loff, &kind = S.kind;
+    const int nblk = S.nblk, nx = S.nx, nc = S.nc, npp = S.npp, nt = S.nt, ntp = S.ntp, camw = S.camw, td_cam = S.td_cam, nt_c = S.nt_c;
     for (int c = 0; c < nblk; c++)
-        if (kind[c] == KIND_POSE && !p.blocks[cam_block[c]].constant) { loff[c] = nc; nc += 6; }
-    // Td comes right behind the poses: its column rides through the 6-wide gather machinery as a pseudo block whose other five
-    // columns are structural zeros, so five more tangent rows must follow it.  It counts as part of the "pose part" npp: the
-    // leading tangent dims the visual factors touch (landmark Schur corrections of the diagonal and the right-hand side).
-    const int td_cam = td_blk >= 0 ? cam_of[td_blk] : -1;
-    if (td_cam >= 0 && !p.blocks[td_blk].constant) { loff[td_cam] = nc; nc += 1; }
-    const int npp = nc;
-    for (int c = 0; c < nblk; c++)
-        if (kind[c] != KIND_POSE && c != td_cam && !p.blocks[cam_block[c]].constant) { loff[c] = nc; nc += gsize[c]; }
-    if (nc < 1) { set_error("no free camera-side parameter block"); return TCV_ERR_INVALID; }
-    const int nt = (nc + 1 + 15) / 16, ntp = (npp + 15) / 16;
+        if (kind[c] == KIND_EUCLID && gsize[c] > 15) { set_error("Euclidean block wider than 15"); return TCV_ERR_UNSUPPORTED; }
     if (td_cam >= 0 && loff[td_cam] >= 0 && loff[td_cam] + 6 > nt * 16) { set_error("Td block: no room for its gather slot"); return TCV_ERR_UNSUPPORTED; }
-    // camera tangent dims: 171 for the 11 frames + extrinsic of OptimizationWithLine (172 with Td), 177 with the relocalisation pose (:1854-1886)
-    if (nc > CAM_MAX - 1 || npp > 88) { set_error("window too large for the fused solver (camera tangent dim > 183)"); return TCV_ERR_TOO_LARGE; }
-    const int camw = nc <= CAM_W - 1 ? (int)CAM_W : (int)CAM_MAX;
-    out.loff = loff; out.goff = goff;
 
     // ---- chain layout: the free Euclidean camera blocks (speed-biases, 9 wide) only meet their IMU neighbours and the
     // prior, so they are eliminated one after the other BEFORE the dense pose system (block-sparse Cholesky with the poses
@@ -522,13 +323,12 @@ int build_cam(const CamIn &in, CamPlan &out) {
     }
     if (in.want_chain && !use_chain) { out.eligible = false; return TCV_OK; }
     // (Td's gather slot is six columns wide, tcv_packed.h: the pose tiles have to cover the five structural zeros behind its column)
-    const int nt_c = (std::max(npp + 1, (td_cam >= 0 && loff[td_cam] >= 0) ? loff[td_cam] + 6 : 0) + 15) / 16;
 
     PlanHdr &H = out.hdr;
     std::memset(&H, 0, sizeof(H));
     H.nblk = nblk; H.nc = nc; H.nx = nx; H.npp = npp; H.nt = nt; H.ntp = ntp;
     H.n_imu = (int)p.imu.size();
-    H.flags = td_blk >= 0 ? 1 : 0; H.td_cam = td_cam; H.camw = camw;
+    H.flags = td_cam >= 0 ? 1 : 0; H.td_cam = td_cam; H.camw = camw;
     H.chain = use_chain ? 1 : 0; H.n_e = (int)chain.size(); H.nt_c = nt_c;
     std::vector<int> &I = out.ints;
     I.clear();
@@ -732,7 +532,7 @@ void cam_key(const CamIn &in, CamKey &key) {
     std::vector<int> &k = key.k;
     k.clear();
     k.reserve(64 + cam_block.size() + 4 * p.imu.size());
-    k.push_back(in.want_chain ? 1 : 0); k.push_back(in.per_imu); k.push_back(in.td_blk >= 0 ? cam_of[in.td_blk] : -1); k.push_back((int)cam_block.size());
+    k.push_back(in.want_chain ? 1 : 0); k.push_back(in.per_imu); k.push_back(in.sizes->td_cam); k.push_back((int)cam_block.size());
     for (int b : cam_block) { const ParamBlock &pb = p.blocks[b]; k.push_back(pb.size | (pb.kind << 8) | ((int)pb.constant << 16)); }
     k.push_back((int)p.imu.size());
     for (auto &f : p.imu) for (int j = 0; j < 4; j++) k.push_back(cam_of[f.b[j]]);
@@ -777,7 +577,7 @@ int get_cam(const CamIn &in, std::shared_ptr<const CamPlan> &out, bool use_cache
 // (stable).  Two passes over the factors with a direct-index table of a few hundred slots (block ORDINALS instead of tangent offsets:
 // every pose-kind block is 6 wide) -- a count pass that also records the order of first appearance, and a fill pass --, then a
 // counting sort of the units.  ~8x faster than the generic path on a replay window (500 point factors, 90 landmarks).
-struct ProgScratch { std::vector<int> cnt, start, order, ukey; };
+struct ProgScratch { std::vector<int> cnt, start, order, ukey, vprog, sprog, vchunk_tab; };      // (the last three: PlanBuild::pr)
 ProgScratch &prog_scratch() { thread_local ProgScratch s; return s; }
 
 // slots of the table: [TILE 16 x 16 ordinals | G / RC 16 | per landmark (HLL) | per landmark slot (HCL)]
@@ -786,7 +586,7 @@ enum { PS_TILE = 0, PS_G = 256, PS_LM = 272 };
 // writes [units (3 ints each) | items] behind `prog` (which the caller has aligned); n_units / n_wave_units / n_items describe them
 struct ProgOut { int n_units = 0, n_wave_units = 0, n_items = 0; };
 template <class Walk, class DestOf>
-bool fast_prog(int nslot, Walk &&walk, DestOf &&dest_of, std::vector<int> &prog, ProgOut &po, int wave_items, int wave_max) {
+bool fast_prog(int nslot, Walk &&walk, DestOf &&dest_of, std::vector<int> &prog, ProgOut &po) {
     ProgScratch &S = prog_scratch();
     S.cnt.assign(nslot, 0); S.order.clear();
     // pass A: counts + order of first appearance
@@ -830,9 +630,9 @@ bool fast_prog(int nslot, Walk &&walk, DestOf &&dest_of, std::vector<int> &prog,
             un[3 * pos] = (int)(((unsigned)q.kind << 28) | ((unsigned)ncols << 24) | ((unsigned)ea << 20) | (unsigned)n);
             un[3 * pos + 1] = u1; un[3 * pos + 2] = ib;
         }
-        if (n > wave_items) nw += nrow;
+        if (n > WAVE_UNIT_ITEMS) nw += nrow;
     }
-    po.n_units = nu; po.n_wave_units = std::min(nw, wave_max); po.n_items = total;
+    po.n_units = nu; po.n_wave_units = std::min(nw, (int)WAVE_UNIT_MAX); po.n_items = total;
     return true;
 }
 
@@ -849,6 +649,13 @@ namespace {
 std::mutex g_lap_mu;
 std::map<std::string, std::pair<double, long long>> g_laps;
 void pack_lap_add(const char *what, double us) { std::lock_guard<std::mutex> g(g_lap_mu); auto &e = g_laps[what]; e.first += us; e.second++; }
+struct Lap {      // time since the previous lap, booked under `what`
+    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+    void operator()(const char *what) {
+        static const bool dbg_t = getenv("TCV_DEBUG_PACK2") != nullptr;
+        if (dbg_t) { const auto t = std::chrono::steady_clock::now(); pack_lap_add(what, std::chrono::duration<double, std::micro>(t - t_prev).count()); t_prev = std::chrono::steady_clock::now(); }
+    }
+};
 }  // namespace
 void pack_laps_print() {
     std::lock_guard<std::mutex> g(g_lap_mu);
@@ -861,17 +668,48 @@ static std::atomic<int> g_pack_reference{getenv("TCV_PACK_REF") ? 1 : 0};
 void set_pack_reference(int on) { g_pack_reference.store(on ? 1 : 0, std::memory_order_relaxed); }
 bool pack_reference() { return g_pack_reference.load(std::memory_order_relaxed) != 0; }
 
-// structural half: plan header, int pool and the host-side maps (everything that does not depend on the VALUES of the window)
+// ---- structural half: plan header, int pool and the host-side maps (everything that does not depend on the VALUES of the window) --------
+// pack_plan (below) is a sequence of phases over one PlanBuild: what a phase reads and writes is what it touches of that struct.
 // coop_chunks > 0: plan for the cooperative kernel (tcv_packed.h COOP_*): at least that many visual chunks of at most 256 point factors
 // each (one helper workgroup per chunk, one lane per factor), and an LDS budget that leaves room for a helper's second tile set
-static int pack_plan(const tcv_problem &p, Packed &out, int mode, int chain_lds, int coop_chunks) {
+namespace {
+struct VChunk { int pb, pn, lb, ln, lmb, lmn; };      // sorted point factors [pb, pb + pn), line factors [lb, lb + ln), landmarks [lmb, lmb + lmn)
+
+struct PlanBuild {
+    const tcv_problem &p;
+    Packed &out;
+    const int mode, chain_lds, coop_chunks;
+    const bool ref_path = pack_reference();      // the generic gather-program builder (DestList + emit_rows) and no camera-half cache: the reference of tests/test_pack_cpu.py
+    // classification
+    std::vector<int> lm_of, cam_of;      // problem block -> landmark / camera block (-1: the other side)
+    int td_blk = -1;                     // problem block of Td (-1: plain ProjectionFactors)
+    int L = 0, nproj = 0, nline = 0;
+    CamSizes cs;
+    // LDS budgets (doubles): landmark coupling area and staging of the visual phase, the chain layout's pool
+    int area_cap = 0, stage_cap = 0, c_pool = 0;
+    bool dense_fits = false;
+    std::shared_ptr<const CamPlan> cam;      // the chosen camera half
+    bool use_chain = false;
+    // landmark tables
+    int prec = 0, td_t = -1, ncol_f = 3;      // doubles per staged point record; tangent offset of Td (-1: none or constant); column groups per point factor
+    std::vector<int> lmptr;                   // L + 1: sorted point factors of every landmark
+    std::vector<int> slotptr, slot_t;         // slots of a landmark = the distinct free pose-kind blocks (and Td) it is seen from, in order of first appearance
+    std::vector<signed char> fslot;           // per sorted factor and column group: its slot (-1: constant block)
+    std::vector<int> ft, e_off, line_t;       // tangent offset per sorted factor and column group (-1 constant); L + 1 offsets of the landmarks' slices in the coupling store; per line factor
+    // chunks and their gather programs: visual programs, Schur programs and chunk table (o_vchunk) of the last emit_all (reused: a plan per window per frame)
+    std::vector<VChunk> vch;
+    ProgScratch &pr = prog_scratch();
+    Lap lap;
+    // the fast path indexes blocks by ordinal = tangent offset / 6: every slot of the pose part is 6 wide (Td: its 6-wide gather slot) and
+    // there are at most 16 of them (npp <= 88); anything else takes the generic path
+    bool fast_ok() const { return !ref_path && cs.npp <= 90; }
+};
+
+// ---- 1. classify blocks: landmarks = size-1 Euclidean blocks used only as 4th block of projection factors
+int classify_blocks(PlanBuild &B) {
+    const tcv_problem &p = B.p;
+    Packed &out = B.out;
     const int nb = (int)p.blocks.size();
-    static const bool dbg_t = getenv("TCV_DEBUG_PACK2") != nullptr;      // developer: where the symbolic packing spends its time
-    const bool ref_path = g_pack_reference.load(std::memory_order_relaxed) != 0;      // the generic gather-program builder (DestList + emit_rows) and no camera-half cache: the reference of tests/test_pack_cpu.py
-    static const bool no_cache = getenv("TCV_NO_CAM_CACHE") != nullptr;      // (TCV_NO_PLAN_CACHE switches the whole-plan cache off, this one the camera halves')
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) { if (dbg_t) { const auto t = std::chrono::steady_clock::now(); pack_lap_add(what, std::chrono::duration<double, std::micro>(t - t_prev).count()); t_prev = std::chrono::steady_clock::now(); } };
-    // ---- classify blocks: landmarks = size-1 Euclidean blocks used only as 4th block of projection factors
     std::vector<int> use_other(nb, 0);
     for (auto &f : p.proj) { for (int k = 0; k < 3; k++) use_other[f.b[k]]++; if (f.btd >= 0) use_other[f.btd]++; }
     // ProjectionTdFactor (ESTIMATE_TD): all point factors or none, one shared 1-dim Td block
@@ -885,10 +723,12 @@ static int pack_plan(const tcv_problem &p, Packed &out, int mode, int chain_lds,
         const ParamBlock &pb = p.blocks[td_blk];
         if (pb.size != 1 || pb.kind != KIND_EUCLID) { set_error("Td must be a size-1 Euclidean block"); return TCV_ERR_UNSUPPORTED; }
     }
+    B.td_blk = td_blk;
     for (auto &f : p.imu) for (int k = 0; k < 4; k++) use_other[f.b[k]]++;
     for (auto &f : p.line) use_other[f.b]++;
     for (auto &f : p.prior) for (int b : f.b) use_other[b]++;
-    std::vector<int> lm_of(nb, -1), cam_of(nb, -1);
+    std::vector<int> &lm_of = B.lm_of, &cam_of = B.cam_of;
+    lm_of.assign(nb, -1); cam_of.assign(nb, -1);
     out.cam_block.clear(); out.lm_block.clear();
     // landmark numbering = order of first appearance in the projection factors (feature_index, estimator.cpp:1743)
     for (auto &f : p.proj) {
@@ -902,7 +742,7 @@ static int pack_plan(const tcv_problem &p, Packed &out, int mode, int chain_lds,
     }
     for (int b = 0; b < nb; b++)
         if (lm_of[b] < 0) { cam_of[b] = (int)out.cam_block.size(); out.cam_block.push_back(b); }
-    const int nblk = (int)out.cam_block.size(), L = (int)out.lm_block.size();
+    B.L = (int)out.lm_block.size(); B.nproj = (int)p.proj.size(); B.nline = (int)p.line.size();
     for (auto &f : p.proj)
         for (int k = 0; k < 3; k++)
             if (p.blocks[f.b[k]].kind != KIND_POSE || p.blocks[f.b[k]].size != 7) {
@@ -917,91 +757,98 @@ static int pack_plan(const tcv_problem &p, Packed &out, int mode, int chain_lds,
         }
     for (auto &f : p.line)
         if (p.blocks[f.b].kind != KIND_POSE) { set_error("line factor: block must be a pose"); return TCV_ERR_UNSUPPORTED; }
+    return TCV_OK;
+}
 
-    // ---- sizes of the camera side (the tables themselves come from the camera half below)
-    int nx = 0, nc = 0, npose_free = 0;
-    for (int c = 0; c < nblk; c++) {
-        const ParamBlock &pb = p.blocks[out.cam_block[c]];
-        nx += pb.size;
-        if (pb.kind == KIND_POSE && !pb.constant) npose_free++;
-    }
-    const int td_cam = td_blk >= 0 ? cam_of[td_blk] : -1;
-    const int td_free = (td_cam >= 0 && !p.blocks[td_blk].constant) ? 1 : 0;
-    const int npp = 6 * npose_free + td_free;
-    nc = npp;
-    for (int c = 0; c < nblk; c++) { const ParamBlock &pb = p.blocks[out.cam_block[c]]; if (pb.kind != KIND_POSE && c != td_cam && !pb.constant) nc += pb.size; }
-    if (nc < 1) { set_error("no free camera-side parameter block"); return TCV_ERR_INVALID; }
-    const int nt = (nc + 1 + 15) / 16, ntp = (npp + 15) / 16;
-    const int ntiles = nt * (nt + 1) / 2, pp_tiles = ntp * (ntp + 1) / 2;
-    if (nc > CAM_MAX - 1 || npp > 88 || nc + L > SCR_NL || L > 1024) { set_error("window too large for the fused solver (camera tangent dim > 183)"); return TCV_ERR_TOO_LARGE; }
-    const int camw = nc <= CAM_W - 1 ? (int)CAM_W : (int)CAM_MAX;
-    const int nxl = (nx + L + 1) & ~1;
-    int area_cap = LDS_DOUBLES - ntiles * 256 - 2 * nxl - (3 * camw + 176) - 64;
-    int stage_cap = (ntiles - pp_tiles) * 256;
+// ---- 2. camera sizes and LDS budgets
+// the dense layout's split: what the tiles of the whole camera system and the vectors leave is the landmark coupling area, the tiles outside
+// the pose part are free for staging during the visual phase
+void dense_budgets(PlanBuild &B) {
+    const CamSizes &S = B.cs;
+    const int ntiles = S.nt * (S.nt + 1) / 2, pp_tiles = S.ntp * (S.ntp + 1) / 2;
+    const int nxl = (S.nx + B.L + 1) & ~1;
+    B.area_cap = LDS_DOUBLES - ntiles * 256 - 2 * nxl - (3 * S.camw + 176) - 64;
+    B.stage_cap = (ntiles - pp_tiles) * 256;
+}
+int camera_budgets(PlanBuild &B) {
+    if (int rc = cam_sizes(B.p, B.out.cam_block, B.cam_of, B.td_blk, B.L, B.cs)) return rc;
+    const CamSizes &S = B.cs;
+    dense_budgets(B);
     // (the dense layout holds the whole camera system in LDS tiles: 12 tile rows -- a window with the relocalisation pose -- do not fit; such a
-    // window needs the chain layout, decided below)
-    const bool dense_fits = area_cap >= 512;
-    if (!dense_fits && mode != 0) { set_error("window too large for the fused solver (LDS)"); return TCV_ERR_TOO_LARGE; }
-    const int td_t_pre = td_free ? 6 * npose_free : -1;
-    const int nt_c = (std::max(npp + 1, td_t_pre >= 0 ? td_t_pre + 6 : 0) + 15) / 16, ctiles = nt_c * (nt_c + 1) / 2;
-    const int c_vec = 2 * nxl + (3 * camw + 176) + 64 + 112;
-    const int c_lds = coop_chunks > 0 ? (LDS_DOUBLES - ctiles * 256 - 8) : ((chain_lds >= 6144 && chain_lds <= LDS_DOUBLES) ? (chain_lds & ~1) : chain_lds_doubles());
-    const int c_pool = c_lds - ctiles * 256 - c_vec;
-    const int n_imu = (int)p.imu.size();
+    // window needs the chain layout, decided by choose_cam)
+    B.dense_fits = B.area_cap >= 512;
+    if (!B.dense_fits && B.mode != 0) { set_error("window too large for the fused solver (LDS)"); return TCV_ERR_TOO_LARGE; }
+    const int nxl = (S.nx + B.L + 1) & ~1;
+    const int ctiles = S.nt_c * (S.nt_c + 1) / 2;
+    const int c_vec = 2 * nxl + (3 * S.camw + 176) + 64 + 112;
+    const int c_lds = B.coop_chunks > 0 ? (LDS_DOUBLES - ctiles * 256 - 8) : ((B.chain_lds >= 6144 && B.chain_lds <= LDS_DOUBLES) ? (B.chain_lds & ~1) : chain_lds_doubles());
+    B.c_pool = c_lds - ctiles * 256 - c_vec;
+    return TCV_OK;
+}
 
-    // ---- the camera half: chain layout if the graph allows it and its LDS pool holds the chain's working set
+// ---- 3. the camera half: chain layout if the graph allows it and its LDS pool holds the chain's working set
+// TCV_OK and B.cam, a negative status, or 1: the chain layout's pool has no room for an IMU record
+int cam_for(PlanBuild &B, bool chain) {
+    static const bool no_cache = getenv("TCV_NO_CAM_CACHE") != nullptr;      // (TCV_NO_PLAN_CACHE switches the whole-plan cache off, this one the camera halves')
+    const int n_imu = (int)B.p.imu.size();
+    const int imu_cap = chain ? B.c_pool : B.area_cap;       // chain mode: the whole pool holds IMU records
+    if (n_imu > 0 && imu_cap < IMU_REC) { if (chain) return 1; set_error("no LDS room for IMU staging"); return TCV_ERR_TOO_LARGE; }
     CamIn cin;
-    cin.p = &p; cin.cam_block = &out.cam_block; cin.cam_of = &cam_of; cin.td_blk = td_blk;
-    std::shared_ptr<const CamPlan> cam;
-    bool use_chain = (mode == 0);
-    auto cam_for = [&](bool chain) -> int {
-        const int imu_cap = chain ? c_pool : area_cap;       // chain mode: the whole pool holds IMU records
-        if (n_imu > 0 && imu_cap < IMU_REC) { if (chain) return 1; set_error("no LDS room for IMU staging"); return TCV_ERR_TOO_LARGE; }
-        cin.want_chain = chain; cin.per_imu = std::max(1, std::min(n_imu, imu_cap / IMU_REC));
-        return get_cam(cin, cam, !ref_path && !no_cache);
-    };
-    if (use_chain) {
-        const int rc = cam_for(true);
+    cin.p = &B.p; cin.cam_block = &B.out.cam_block; cin.cam_of = &B.cam_of; cin.sizes = &B.cs;
+    cin.want_chain = chain; cin.per_imu = std::max(1, std::min(n_imu, imu_cap / IMU_REC));
+    return get_cam(cin, B.cam, !B.ref_path && !no_cache);
+}
+// the dense layout, chosen at once or after the chain layout turned out not to fit: its budgets and its camera half
+int use_dense_layout(PlanBuild &B) {
+    B.use_chain = false;
+    if (!B.dense_fits) { set_error("window too large for the fused solver (LDS; its speed-bias blocks do not form a chain either)"); return TCV_ERR_TOO_LARGE; }
+    dense_budgets(B);
+    return cam_for(B, false);
+}
+int choose_cam(PlanBuild &B) {
+    B.use_chain = (B.mode == 0);
+    if (B.use_chain) {
+        const int rc = cam_for(B, true);
         if (rc < 0) return rc;
-        if (rc == 1 || !cam->eligible || c_pool < chain_pool_doubles(cam->hdr.n_e, nt_c) || c_pool < IMU_REC) use_chain = false;
+        if (rc == 1 || !B.cam->eligible || B.c_pool < chain_pool_doubles(B.cam->hdr.n_e, B.cs.nt_c) || B.c_pool < IMU_REC) B.use_chain = false;
     }
-    if (!use_chain) {
-        if (!dense_fits) { set_error("window too large for the fused solver (LDS; its speed-bias blocks do not form a chain either)"); return TCV_ERR_TOO_LARGE; }
-        const int rc = cam_for(false);
-        if (rc != TCV_OK) return rc;
-    }
-    const std::vector<int> *loffp = &cam->loff;
-    lap("classification + camera half");
+    return B.use_chain ? TCV_OK : use_dense_layout(B);
+}
 
-    const int prec = td_blk >= 0 ? (int)PROJ_TD_REC : (int)PROJ_REC;      // doubles per staged point record
-    const int td_t = td_cam >= 0 ? (*loffp)[td_cam] : -1;
-
-    // ---- projection factors sorted by landmark (stable), landmark slots
-    const int nproj = (int)p.proj.size(), nline = (int)p.line.size();
-    std::vector<int> &order = out.proj_order;
+// ---- 4. projection factors sorted by landmark (stable), landmark slots
+int landmark_slots(PlanBuild &B) {
+    const tcv_problem &p = B.p;
+    const std::vector<int> &loff = B.cs.loff, &lm_of = B.lm_of, &cam_of = B.cam_of;
+    const int L = B.L, nproj = B.nproj, nline = B.nline;
+    B.prec = B.td_blk >= 0 ? (int)PROJ_TD_REC : (int)PROJ_REC;
+    B.td_t = B.cs.td_cam >= 0 ? loff[B.cs.td_cam] : -1;
+    const int td_t = B.td_t;
+    std::vector<int> &order = B.out.proj_order;
     order.resize(nproj);
-    std::vector<int> lmptr(L + 1, 0);
+    std::vector<int> &lmptr = B.lmptr;
+    lmptr.assign(L + 1, 0);
     for (auto &f : p.proj) lmptr[lm_of[f.b[3]] + 1]++;
     for (int l = 0; l < L; l++) lmptr[l + 1] += lmptr[l];
     {      // stable counting sort by landmark
         std::vector<int> pos(lmptr.begin(), lmptr.end() - 1);
         for (int i = 0; i < nproj; i++) order[pos[lm_of[p.proj[i].b[3]]]++] = i;
     }
-    // slots of a landmark = the distinct free pose-kind blocks (and Td) it is seen from, in order of first appearance: flat arrays, and per
-    // sorted factor the slot of each of its columns (-1: constant block)
-    const int ncol_f = td_t >= 0 ? 4 : 3;
-    std::vector<int> slotptr(L + 1, 0), slot_t;
-    std::vector<signed char> fslot((size_t)nproj * 4, -1);
-    std::vector<int> ft((size_t)nproj * 4, -1);      // per sorted factor: tangent offset of each column group (-1 constant)
+    // flat arrays, and per sorted factor the slot of each of its columns
+    const int ncol_f = B.ncol_f = td_t >= 0 ? 4 : 3;
+    std::vector<int> &slotptr = B.slotptr, &slot_t = B.slot_t, &ft = B.ft, &e_off = B.e_off;
+    std::vector<signed char> &fslot = B.fslot;
+    slotptr.assign(L + 1, 0); slot_t.clear();
+    fslot.assign((size_t)nproj * 4, -1);
+    ft.assign((size_t)nproj * 4, -1);
     slot_t.reserve((size_t)L * 8);
-    std::vector<int> e_off(L + 1, 0);
+    e_off.assign(L + 1, 0);
     for (int l = 0; l < L; l++) {
         const int s0 = (int)slot_t.size();
         slotptr[l] = s0;
         for (int k = lmptr[l]; k < lmptr[l + 1]; k++) {
             const ProjFac &f = p.proj[order[k]];
             for (int s = 0; s < ncol_f; s++) {
-                const int t = s < 3 ? (*loffp)[cam_of[f.b[s]]] : td_t;
+                const int t = s < 3 ? loff[cam_of[f.b[s]]] : td_t;
                 ft[(size_t)k * 4 + s] = t;
                 if (t < 0) continue;
                 int q = s0;
@@ -1024,302 +871,304 @@ static int pack_plan(const tcv_problem &p, Packed &out, int mode, int chain_lds,
         for (int a2 = 0; a2 < ncol_f; a2++) for (int b2 = 0; b2 < a2; b2++)
             if (t4[a2] >= 0 && t4[a2] == t4[b2]) { set_error("projection factor uses one block twice"); return TCV_ERR_UNSUPPORTED; }
     }
-    std::vector<int> line_t(nline);
-    for (int k = 0; k < nline; k++) line_t[k] = (*loffp)[cam_of[p.line[k].b]];
+    B.line_t.resize(nline);
+    for (int k = 0; k < nline; k++) B.line_t[k] = loff[cam_of[p.line[k].b]];
+    return TCV_OK;
+}
 
-    // ---- visual chunks (whole landmarks; lines ride in chunk 0).  Staging holds the factor records AND the chunk's
-    // gather program (units + items), so both count against the capacity.
-    struct VChunk { int pb, pn, lb, ln, lmb, lmn; };
-    std::vector<VChunk> vch;
-    auto build_chunks = [&](int stage_cap, int area_cap, std::vector<VChunk> &vch) -> int {
-        vch.clear();
-        const int npose = npp / 6;
-        const int npb = npose + (td_t >= 0 ? 1 : 0);
-        const int base_prog = 3 * (npb * (npb + 1) / 2 * 6 + npb);      // upper bound on tile + gradient units
-        auto need = [&](int recs, int nf, int nl_, int slots, int nln) {
-            const int ints = base_prog + 3 * (slots + nl_) + (td_t >= 0 ? 19 : 13) * nf + 2 * nln;      // items per point factor: 6 (10) block pairs + 3 (4) gradients + 3 (4) landmark couplings + 1
-            return ((recs + 1) & ~1) + (ints + 1) / 2 + 8;
-        };
-        if (need(nline * LINE_REC, 0, 0, 0, nline) > stage_cap) { set_error("too many line factors for LDS staging"); return TCV_ERR_TOO_LARGE; }
-        // whole landmarks per chunk, greedily; the line factors ride in the LAST chunk (the least full one) if they fit
-        VChunk cur{0, 0, 0, 0, 0, 0};
-        int recs = 0, hcl = 0, nf_c = 0, slots_c = 0;
-        for (int l = 0; l < L; l++) {
-            const int nf = lmptr[l + 1] - lmptr[l], ns = slotptr[l + 1] - slotptr[l], nh = 6 * ns + 2;
-            if (need(nf * prec, nf, 1, ns, 0) > stage_cap || nh + 3 > area_cap) { set_error("landmark track too long for LDS staging"); return TCV_ERR_TOO_LARGE; }
-            if (need(recs + nf * prec, nf_c + nf, cur.lmn + 1, slots_c + ns, 0) > stage_cap || hcl + nh + 3 * (cur.lmn + 1) > area_cap) {
-                vch.push_back(cur);
-                cur = VChunk{lmptr[l], 0, 0, 0, l, 0};
-                recs = 0; hcl = 0; nf_c = 0; slots_c = 0;
-            }
-            cur.pn += nf; cur.lmn += 1; recs += nf * prec; hcl += nh; nf_c += nf; slots_c += ns;
-        }
-        if (nline > 0 && need(recs + nline * LINE_REC, nf_c, cur.lmn, slots_c, nline) > stage_cap) {
-            vch.push_back(cur);
-            cur = VChunk{lmptr[L], 0, 0, 0, L, 0};
-        }
-        cur.ln = nline;
-        vch.push_back(cur);
-        return TCV_OK;
+// ---- 5. visual chunks (whole landmarks).  Staging holds the factor records AND the chunk's gather program (units + items), so both count
+// against the capacity.
+// dense layout: whole landmarks per chunk, greedily, sized by an estimate of the visual program; the line factors ride in the LAST chunk
+// (the least full one) if they fit
+int dense_chunks(const PlanBuild &B, int stage_cap, int area_cap, std::vector<VChunk> &vch) {
+    const std::vector<int> &lmptr = B.lmptr, &slotptr = B.slotptr;
+    const int L = B.L, nline = B.nline, prec = B.prec;
+    const bool td = B.td_t >= 0;
+    vch.clear();
+    const int npose = B.cs.npp / 6;
+    const int npb = npose + (td ? 1 : 0);
+    const int base_prog = 3 * (npb * (npb + 1) / 2 * 6 + npb);      // upper bound on tile + gradient units
+    auto need = [=](int recs, int nf, int nl_, int slots, int nln) {
+        const int ints = base_prog + 3 * (slots + nl_) + (td ? 19 : 13) * nf + 2 * nln;      // items per point factor: 6 (10) block pairs + 3 (4) gradients + 3 (4) landmark couplings + 1
+        return ((recs + 1) & ~1) + (ints + 1) / 2 + 8;
     };
-    static const int wu_v = getenv("TCV_WU_V") ? atoi(getenv("TCV_WU_V")) : (int)WAVE_UNIT_ITEMS, wu_s = getenv("TCV_WU_S") ? atoi(getenv("TCV_WU_S")) : (int)WAVE_UNIT_ITEMS,
-                     wu_max = getenv("TCV_WU_MAX") ? atoi(getenv("TCV_WU_MAX")) : (int)WAVE_UNIT_MAX;      // tuning experiments
-    // the two gather programs of one chunk: the generic builder (reference) ...
-    auto chunk_progs_ref = [&](const VChunk &c, RowProg &vp, RowProg &sp) -> int {
-        DestList dl, sl;
-        std::vector<Col> cols;
-        cols.reserve(4);
-        for (int k = 0; k < c.pn; k++) {
-            const ProjFac &f = p.proj[order[c.pb + k]];
-            const int l = lm_of[f.b[3]];
-            const int base = k * prec;
-            if (base >= (1 << 21)) { set_error("staging offset overflow"); return TCV_ERR_TOO_LARGE; }
-            auto mk = [&](int ca, int cb) { return (int)(((unsigned)base << 11) | ((unsigned)ca << 6) | ((unsigned)cb << 1)); };
-            cols.clear();
-            for (int s2 = 0; s2 < 3; s2++) cols.push_back(Col{(*loffp)[cam_of[f.b[s2]]], 6 * s2, 6});
-            if (td_t >= 0) cols.push_back(Col{td_t, 20, 6});      // [td | 5 zero columns]
-            add_pairs(dl, cols, mk, 19);
-            for (auto &cc : cols) {
-                if (cc.t < 0) continue;
-                const int *sb = slot_t.data() + slotptr[l], *se = slot_t.data() + slotptr[l + 1];
-                const int slot = (int)(std::find(sb, se, cc.t) - sb);
-                dl.add(DK_HCL, e_off[l] + 6 * slot, 0, 6, 1, mk(18, cc.c));      // Hcl[e] += sum J[:,18] * J[:, c + e]
+    if (need(nline * LINE_REC, 0, 0, 0, nline) > stage_cap) { set_error("too many line factors for LDS staging"); return TCV_ERR_TOO_LARGE; }
+    VChunk cur{0, 0, 0, 0, 0, 0};
+    int recs = 0, hcl = 0, nf_c = 0, slots_c = 0;
+    for (int l = 0; l < L; l++) {
+        const int nf = lmptr[l + 1] - lmptr[l], ns = slotptr[l + 1] - slotptr[l], nh = 6 * ns + 2;
+        if (need(nf * prec, nf, 1, ns, 0) > stage_cap || nh + 3 > area_cap) { set_error("landmark track too long for LDS staging"); return TCV_ERR_TOO_LARGE; }
+        if (need(recs + nf * prec, nf_c + nf, cur.lmn + 1, slots_c + ns, 0) > stage_cap || hcl + nh + 3 * (cur.lmn + 1) > area_cap) {
+            vch.push_back(cur);
+            cur = VChunk{lmptr[l], 0, 0, 0, l, 0};
+            recs = 0; hcl = 0; nf_c = 0; slots_c = 0;
+        }
+        cur.pn += nf; cur.lmn += 1; recs += nf * prec; hcl += nh; nf_c += nf; slots_c += ns;
+    }
+    if (nline > 0 && need(recs + nline * LINE_REC, nf_c, cur.lmn, slots_c, nline) > stage_cap) {
+        vch.push_back(cur);
+        cur = VChunk{lmptr[L], 0, 0, 0, L, 0};
+    }
+    cur.ln = nline;
+    vch.push_back(cur);
+    return TCV_OK;
+}
+// chain layout: the landmarks dealt evenly to k chunks.  Point factors: an even split, except that a boundary a few factors above a
+// multiple of 64 is pulled down to it -- one lane evaluates one factor, so 64 + 68 + 68 factors cost five wavefront passes of the
+// evaluation and 64 + 64 + 72 cost four.  Line factors: dealt so that the chunks' record volumes even out (the chunk with more point
+// factors gets fewer lines).
+void chain_chunks(const PlanBuild &B, int k, std::vector<VChunk> &cand) {
+    const std::vector<int> &lmptr = B.lmptr;
+    cand.clear();
+    int l = 0, lines_left = B.nline, lb_next = 0;
+    const long long rec_even = ((long long)B.nproj * B.prec + (long long)B.nline * LINE_REC) / k;
+    for (int c = 0; c < k; c++) {
+        VChunk cur{lmptr[l], 0, lb_next, 0, l, 0};
+        int target = (int)((long long)(c + 1) * B.nproj / k);
+        if (target % 64 <= 8 && target >= 64) target -= target % 64;
+        while (l < B.L && (c == k - 1 || lmptr[l + 1] <= target || cur.lmn == 0)) { cur.pn += lmptr[l + 1] - lmptr[l]; cur.lmn++; l++; }
+        int ln_c = c == k - 1 ? lines_left : (int)std::max<long long>(0, std::min<long long>(lines_left, (rec_even - (long long)cur.pn * B.prec + LINE_REC / 2) / LINE_REC));
+        cur.ln = ln_c; lb_next += ln_c; lines_left -= ln_c;
+        cand.push_back(cur);
+    }
+}
+
+// ---- 6. the two gather programs of one chunk: the generic builder (reference) ...
+int chunk_progs_ref(const PlanBuild &B, const VChunk &c, std::vector<int> &vprog, std::vector<int> &sprog, ProgOut &vp, ProgOut &sp) {
+    const tcv_problem &p = B.p;
+    const std::vector<int> &loff = B.cs.loff, &cam_of = B.cam_of, &order = B.out.proj_order, &slotptr = B.slotptr, &slot_t = B.slot_t, &e_off = B.e_off;
+    const int prec = B.prec, td_t = B.td_t;
+    DestList dl, sl;
+    std::vector<Col> cols;
+    cols.reserve(4);
+    for (int k = 0; k < c.pn; k++) {
+        const ProjFac &f = p.proj[order[c.pb + k]];
+        const int l = B.lm_of[f.b[3]];
+        const int base = k * prec;
+        if (base >= (1 << 21)) { set_error("staging offset overflow"); return TCV_ERR_TOO_LARGE; }
+        auto mk = [base](int ca, int cb) { return (int)(((unsigned)base << 11) | ((unsigned)ca << 6) | ((unsigned)cb << 1)); };
+        cols.clear();
+        for (int s2 = 0; s2 < 3; s2++) cols.push_back(Col{loff[cam_of[f.b[s2]]], 6 * s2, 6});
+        if (td_t >= 0) cols.push_back(Col{td_t, 20, 6});      // [td | 5 zero columns]
+        add_pairs(dl, cols, mk, 19);
+        for (auto &cc : cols) {
+            if (cc.t < 0) continue;
+            const int *sb = slot_t.data() + slotptr[l], *se = slot_t.data() + slotptr[l + 1];
+            const int slot = (int)(std::find(sb, se, cc.t) - sb);
+            dl.add(DK_HCL, e_off[l] + 6 * slot, 0, 6, 1, mk(18, cc.c));      // Hcl[e] += sum J[:,18] * J[:, c + e]
+        }
+        dl.add(DK_HLL, l, 0, 2, 1, mk(18, 18));                              // acc[0] = hll, acc[1] = gl (columns 18, 19)
+    }
+    for (int k = 0; k < c.ln; k++) {
+        const LineFac &f = p.line[c.lb + k];
+        const int base = c.pn * prec + k * LINE_REC;
+        if (base >= (1 << 21)) { set_error("staging offset overflow"); return TCV_ERR_TOO_LARGE; }
+        auto mk = [base](int ca, int cb) { return (int)(((unsigned)base << 11) | ((unsigned)ca << 6) | ((unsigned)cb << 1) | 1u); };
+        cols.clear();
+        cols.push_back(Col{loff[cam_of[f.b]], 0, 6});
+        add_pairs(dl, cols, mk, 6);
+    }
+    for (int l = c.lmb; l < c.lmb + c.lmn; l++) {
+        const int *sl_t = slot_t.data() + slotptr[l];
+        const int nsl = slotptr[l + 1] - slotptr[l];
+        for (int a2 = 0; a2 < nsl; a2++) {
+            const unsigned hoff = (unsigned)(e_off[l] - e_off[c.lmb]), ns = (unsigned)nsl;
+            auto mk = [hoff, ns](int sa, int sb) { return (int)((hoff << 18) | (ns << 12) | ((unsigned)sa << 6) | (unsigned)sb); };
+            sl.add(DK_TILE, sl_t[a2], sl_t[a2], 6, 0, mk(a2, a2));
+            sl.add(DK_RC, sl_t[a2], 0, 6, 1, mk(63, a2));                // rc[t + e] += gl/kappa * Hcl[slot][e]
+            for (int b2 = 0; b2 < a2; b2++) {
+                if (sl_t[a2] > sl_t[b2]) sl.add(DK_TILE, sl_t[a2], sl_t[b2], 6, 6, mk(a2, b2));
+                else sl.add(DK_TILE, sl_t[b2], sl_t[a2], 6, 6, mk(b2, a2));
             }
-            dl.add(DK_HLL, l, 0, 2, 1, mk(18, 18));                              // acc[0] = hll, acc[1] = gl (columns 18, 19)
+        }
+    }
+    dl.finish(); sl.finish();
+    RowProg rv, rs;
+    if (!emit_rows(dl, rv, false) || !emit_rows(sl, rs, false)) { set_error("gather program field overflow"); return TCV_ERR_TOO_LARGE; }
+    auto put = [](const RowProg &r, std::vector<int> &prog, ProgOut &po) {
+        prog.insert(prog.end(), r.units.begin(), r.units.end()); prog.insert(prog.end(), r.items.begin(), r.items.end());
+        po.n_units = r.n_units; po.n_wave_units = r.n_wave_units; po.n_items = (int)r.items.size();
+    };
+    put(rv, vprog, vp); put(rs, sprog, sp);
+    return TCV_OK;
+}
+// ... and the fast one (same programs, int by int)
+inline void tile_dest(int sl, int &kind, int &o0, int &o1, int &la, int &lb) { const int oa = sl >> 4, ob = sl & 15; kind = DK_TILE; o0 = 6 * oa; o1 = 6 * ob; la = 6; lb = oa == ob ? 0 : 6; }
+int chunk_progs_fast(const PlanBuild &B, const VChunk &c, std::vector<int> &vprog, std::vector<int> &sprog, ProgOut &vp, ProgOut &sp) {
+    const tcv_problem &p = B.p;
+    const std::vector<int> &lm_of = B.lm_of, &order = B.out.proj_order, &slotptr = B.slotptr, &slot_t = B.slot_t, &ft = B.ft, &e_off = B.e_off, &line_t = B.line_t;
+    const std::vector<signed char> &fslot = B.fslot;
+    const int prec = B.prec, ncol_f = B.ncol_f;
+    if ((c.pn > 0 && (long long)(c.pn - 1) * prec >= (1 << 21)) || (c.ln > 0 && (long long)c.pn * prec + (long long)(c.ln - 1) * LINE_REC >= (1 << 21))) { set_error("staging offset overflow"); return TCV_ERR_TOO_LARGE; }
+    const int sp0 = slotptr[c.lmb];
+    const int PS_HCL = PS_LM + c.lmn, nslot = PS_HCL + (slotptr[c.lmb + c.lmn] - sp0);
+    const int colc[4] = {0, 6, 12, 20};
+    auto vis_walk = [&](auto add) {
+        for (int k = 0; k < c.pn; k++) {
+            const int kk = c.pb + k;
+            const int l = lm_of[p.proj[order[kk]].b[3]];
+            const int *t4 = ft.data() + (size_t)kk * 4;
+            const unsigned base = (unsigned)(k * prec) << 11;
+            for (int a2 = 0; a2 < ncol_f; a2++) {
+                if (t4[a2] < 0) continue;
+                const int oa = t4[a2] / 6, ca = colc[a2];
+                add(PS_TILE + oa * 16 + oa, (int)(base | ((unsigned)ca << 6) | ((unsigned)ca << 1)));
+                add(PS_G + oa, (int)(base | (19u << 6) | ((unsigned)ca << 1)));
+                for (int b2 = 0; b2 < a2; b2++) {
+                    if (t4[b2] < 0) continue;
+                    const int ob = t4[b2] / 6, cb = colc[b2];
+                    if (t4[a2] > t4[b2]) add(PS_TILE + oa * 16 + ob, (int)(base | ((unsigned)ca << 6) | ((unsigned)cb << 1)));
+                    else add(PS_TILE + ob * 16 + oa, (int)(base | ((unsigned)cb << 6) | ((unsigned)ca << 1)));
+                }
+            }
+            for (int a2 = 0; a2 < ncol_f; a2++) {
+                if (t4[a2] < 0) continue;
+                add(PS_HCL + (slotptr[l] - sp0) + fslot[(size_t)kk * 4 + a2], (int)(base | (18u << 6) | ((unsigned)colc[a2] << 1)));
+            }
+            add(PS_LM + (l - c.lmb), (int)(base | (18u << 6) | (18u << 1)));
         }
         for (int k = 0; k < c.ln; k++) {
-            const LineFac &f = p.line[c.lb + k];
-            const int base = c.pn * prec + k * LINE_REC;
-            if (base >= (1 << 21)) { set_error("staging offset overflow"); return TCV_ERR_TOO_LARGE; }
-            auto mk = [&](int ca, int cb) { return (int)(((unsigned)base << 11) | ((unsigned)ca << 6) | ((unsigned)cb << 1) | 1u); };
-            cols.clear();
-            cols.push_back(Col{(*loffp)[cam_of[f.b]], 0, 6});
-            add_pairs(dl, cols, mk, 6);
+            const int t = line_t[c.lb + k];
+            if (t < 0) continue;
+            const unsigned base = (unsigned)(c.pn * prec + k * LINE_REC) << 11;
+            const int o = t / 6;
+            add(PS_TILE + o * 16 + o, (int)(base | 1u));
+            add(PS_G + o, (int)(base | (6u << 6) | 1u));
         }
+    };
+    auto vis_dest = [&](int sl, int &kind, int &o0, int &o1, int &la, int &lb) {
+        if (sl < PS_G) tile_dest(sl, kind, o0, o1, la, lb);
+        else if (sl < PS_LM) { kind = DK_G; o0 = 6 * (sl - PS_G); o1 = 0; la = 6; lb = 1; }
+        else if (sl < PS_HCL) { kind = DK_HLL; o0 = c.lmb + (sl - PS_LM); o1 = 0; la = 2; lb = 1; }
+        else {
+            const int q = sp0 + (sl - PS_HCL);      // global slot index: its landmark by binary search in slotptr
+            const int l = (int)(std::upper_bound(slotptr.begin() + c.lmb, slotptr.begin() + c.lmb + c.lmn + 1, q) - slotptr.begin()) - 1;
+            kind = DK_HCL; o0 = e_off[l] + 6 * (q - slotptr[l]); o1 = 0; la = 6; lb = 1;
+        }
+    };
+    if (!fast_prog(nslot, vis_walk, vis_dest, vprog, vp)) { set_error("gather program field overflow"); return TCV_ERR_TOO_LARGE; }
+    auto sch_walk = [&](auto add) {
         for (int l = c.lmb; l < c.lmb + c.lmn; l++) {
             const int *sl_t = slot_t.data() + slotptr[l];
             const int nsl = slotptr[l + 1] - slotptr[l];
+            const unsigned hdr = ((unsigned)(e_off[l] - e_off[c.lmb]) << 18) | ((unsigned)nsl << 12);
             for (int a2 = 0; a2 < nsl; a2++) {
-                const unsigned hoff = (unsigned)(e_off[l] - e_off[c.lmb]), ns = (unsigned)nsl;
-                auto mk = [&](int sa, int sb) { return (int)((hoff << 18) | (ns << 12) | ((unsigned)sa << 6) | (unsigned)sb); };
-                sl.add(DK_TILE, sl_t[a2], sl_t[a2], 6, 0, mk(a2, a2));
-                sl.add(DK_RC, sl_t[a2], 0, 6, 1, mk(63, a2));                // rc[t + e] += gl/kappa * Hcl[slot][e]
+                const int oa = sl_t[a2] / 6;
+                add(PS_TILE + oa * 16 + oa, (int)(hdr | ((unsigned)a2 << 6) | (unsigned)a2));
+                add(PS_G + oa, (int)(hdr | (63u << 6) | (unsigned)a2));
                 for (int b2 = 0; b2 < a2; b2++) {
-                    if (sl_t[a2] > sl_t[b2]) sl.add(DK_TILE, sl_t[a2], sl_t[b2], 6, 6, mk(a2, b2));
-                    else sl.add(DK_TILE, sl_t[b2], sl_t[a2], 6, 6, mk(b2, a2));
+                    const int ob = sl_t[b2] / 6;
+                    if (sl_t[a2] > sl_t[b2]) add(PS_TILE + oa * 16 + ob, (int)(hdr | ((unsigned)a2 << 6) | (unsigned)b2));
+                    else add(PS_TILE + ob * 16 + oa, (int)(hdr | ((unsigned)b2 << 6) | (unsigned)a2));
                 }
             }
         }
-        dl.finish(); sl.finish();
-        if (!emit_rows(dl, vp, false, wu_v, wu_max) || !emit_rows(sl, sp, false, wu_s, wu_max)) { set_error("gather program field overflow"); return TCV_ERR_TOO_LARGE; }
-        return TCV_OK;
     };
-    // ... and the fast one (same programs, int by int)
-    auto chunk_progs_fast = [&](const VChunk &c, std::vector<int> &vprog, std::vector<int> &sprog, ProgOut &vp, ProgOut &sp) -> int {
-        if ((c.pn > 0 && (long long)(c.pn - 1) * prec >= (1 << 21)) || (c.ln > 0 && (long long)c.pn * prec + (long long)(c.ln - 1) * LINE_REC >= (1 << 21))) { set_error("staging offset overflow"); return TCV_ERR_TOO_LARGE; }
-        const int sp0 = slotptr[c.lmb];
-        const int PS_HCL = PS_LM + c.lmn, nslot = PS_HCL + (slotptr[c.lmb + c.lmn] - sp0);
-        const int colc[4] = {0, 6, 12, 20};
-        auto vis_walk = [&](auto add) {
-            for (int k = 0; k < c.pn; k++) {
-                const int kk = c.pb + k;
-                const int l = lm_of[p.proj[order[kk]].b[3]];
-                const int *t4 = ft.data() + (size_t)kk * 4;
-                const unsigned base = (unsigned)(k * prec) << 11;
-                for (int a2 = 0; a2 < ncol_f; a2++) {
-                    if (t4[a2] < 0) continue;
-                    const int oa = t4[a2] / 6, ca = colc[a2];
-                    add(PS_TILE + oa * 16 + oa, (int)(base | ((unsigned)ca << 6) | ((unsigned)ca << 1)));
-                    add(PS_G + oa, (int)(base | (19u << 6) | ((unsigned)ca << 1)));
-                    for (int b2 = 0; b2 < a2; b2++) {
-                        if (t4[b2] < 0) continue;
-                        const int ob = t4[b2] / 6, cb = colc[b2];
-                        if (t4[a2] > t4[b2]) add(PS_TILE + oa * 16 + ob, (int)(base | ((unsigned)ca << 6) | ((unsigned)cb << 1)));
-                        else add(PS_TILE + ob * 16 + oa, (int)(base | ((unsigned)cb << 6) | ((unsigned)ca << 1)));
-                    }
-                }
-                for (int a2 = 0; a2 < ncol_f; a2++) {
-                    if (t4[a2] < 0) continue;
-                    add(PS_HCL + (slotptr[l] - sp0) + fslot[(size_t)kk * 4 + a2], (int)(base | (18u << 6) | ((unsigned)colc[a2] << 1)));
-                }
-                add(PS_LM + (l - c.lmb), (int)(base | (18u << 6) | (18u << 1)));
-            }
-            for (int k = 0; k < c.ln; k++) {
-                const int t = line_t[c.lb + k];
-                if (t < 0) continue;
-                const unsigned base = (unsigned)(c.pn * prec + k * LINE_REC) << 11;
-                const int o = t / 6;
-                add(PS_TILE + o * 16 + o, (int)(base | 1u));
-                add(PS_G + o, (int)(base | (6u << 6) | 1u));
-            }
-        };
-        auto vis_dest = [&](int sl, int &kind, int &o0, int &o1, int &la, int &lb) {
-            if (sl < PS_G) { const int oa = sl >> 4, ob = sl & 15; kind = DK_TILE; o0 = 6 * oa; o1 = 6 * ob; la = 6; lb = oa == ob ? 0 : 6; }
-            else if (sl < PS_LM) { kind = DK_G; o0 = 6 * (sl - PS_G); o1 = 0; la = 6; lb = 1; }
-            else if (sl < PS_HCL) { kind = DK_HLL; o0 = c.lmb + (sl - PS_LM); o1 = 0; la = 2; lb = 1; }
-            else {
-                const int q = sp0 + (sl - PS_HCL);      // global slot index: its landmark by binary search in slotptr
-                const int l = (int)(std::upper_bound(slotptr.begin() + c.lmb, slotptr.begin() + c.lmb + c.lmn + 1, q) - slotptr.begin()) - 1;
-                kind = DK_HCL; o0 = e_off[l] + 6 * (q - slotptr[l]); o1 = 0; la = 6; lb = 1;
-            }
-        };
-        if (!fast_prog(nslot, vis_walk, vis_dest, vprog, vp, wu_v, wu_max)) { set_error("gather program field overflow"); return TCV_ERR_TOO_LARGE; }
-        auto sch_walk = [&](auto add) {
-            for (int l = c.lmb; l < c.lmb + c.lmn; l++) {
-                const int *sl_t = slot_t.data() + slotptr[l];
-                const int nsl = slotptr[l + 1] - slotptr[l];
-                const unsigned hdr = ((unsigned)(e_off[l] - e_off[c.lmb]) << 18) | ((unsigned)nsl << 12);
-                for (int a2 = 0; a2 < nsl; a2++) {
-                    const int oa = sl_t[a2] / 6;
-                    add(PS_TILE + oa * 16 + oa, (int)(hdr | ((unsigned)a2 << 6) | (unsigned)a2));
-                    add(PS_G + oa, (int)(hdr | (63u << 6) | (unsigned)a2));
-                    for (int b2 = 0; b2 < a2; b2++) {
-                        const int ob = sl_t[b2] / 6;
-                        if (sl_t[a2] > sl_t[b2]) add(PS_TILE + oa * 16 + ob, (int)(hdr | ((unsigned)a2 << 6) | (unsigned)b2));
-                        else add(PS_TILE + ob * 16 + oa, (int)(hdr | ((unsigned)b2 << 6) | (unsigned)a2));
-                    }
-                }
-            }
-        };
-        auto sch_dest = [&](int sl, int &kind, int &o0, int &o1, int &la, int &lb) {
-            if (sl < PS_G) { const int oa = sl >> 4, ob = sl & 15; kind = DK_TILE; o0 = 6 * oa; o1 = 6 * ob; la = 6; lb = oa == ob ? 0 : 6; }
-            else { kind = DK_RC; o0 = 6 * (sl - PS_G); o1 = 0; la = 6; lb = 1; }
-        };
-        if (!fast_prog(PS_LM, sch_walk, sch_dest, sprog, sp, wu_s, wu_max)) { set_error("gather program field overflow"); return TCV_ERR_TOO_LARGE; }
-        return TCV_OK;
+    auto sch_dest = [](int sl, int &kind, int &o0, int &o1, int &la, int &lb) {
+        if (sl < PS_G) tile_dest(sl, kind, o0, o1, la, lb);
+        else { kind = DK_RC; o0 = 6 * (sl - PS_G); o1 = 0; la = 6; lb = 1; }
     };
-    // the fast path indexes blocks by ordinal = tangent offset / 6: every slot of the pose part is 6 wide (Td: its 6-wide gather slot) and
-    // there are at most 16 of them (npp <= 88); anything else takes the generic path
-    const bool fast_ok = !ref_path && npp <= 90;
-    // gather programs of a chunk list; measures the staging / area doubles the largest chunk needs
-    auto emit_all = [&](const std::vector<VChunk> &vch, int stage_chk, int area_chk, std::vector<int> &vprog, std::vector<int> &sprog,
-                        std::vector<int> &vchunk_tab, int &max_stage, int &max_area) -> int {
-        vprog.clear(); sprog.clear(); vchunk_tab.clear(); max_stage = 0; max_area = 0;
-        for (auto &c : vch) {
-            while (vprog.size() & 3) vprog.push_back(0);        // every program starts 16-byte aligned (vector loads on the device)
-            while (sprog.size() & 3) sprog.push_back(0);
-            const int voff = (int)vprog.size(), soff = (int)sprog.size();
-            ProgOut vp, sp;
-            if (fast_ok) { const int rcp = chunk_progs_fast(c, vprog, sprog, vp, sp); if (rcp != TCV_OK) return rcp; }
-            else {
-                RowProg rv, rs;
-                const int rcp = chunk_progs_ref(c, rv, rs);
-                if (rcp != TCV_OK) return rcp;
-                vprog.insert(vprog.end(), rv.units.begin(), rv.units.end()); vprog.insert(vprog.end(), rv.items.begin(), rv.items.end());
-                sprog.insert(sprog.end(), rs.units.begin(), rs.units.end()); sprog.insert(sprog.end(), rs.items.begin(), rs.items.end());
-                vp.n_units = rv.n_units; vp.n_wave_units = rv.n_wave_units; vp.n_items = (int)rv.items.size();
-                sp.n_units = rs.n_units; sp.n_wave_units = rs.n_wave_units; sp.n_items = (int)rs.items.size();
-            }
-            if (getenv("TCV_DEBUG_UNITS")) {
-                auto dump = [](const char *nm, const ProgOut &rp, const int *un) {
-                    fprintf(stderr, "[pack] %s: %d units (%d wave units), items per unit (descending):", nm, rp.n_units, rp.n_wave_units);
-                    for (int u = 0; u < rp.n_units; u += (u < 16 ? 1 : 16)) fprintf(stderr, " %d", un[3 * u] & 0xfffff);
-                    fprintf(stderr, "\n");
-                };
-                dump("visual", vp, vprog.data() + voff); dump("schur", sp, sprog.data() + soff);
-            }
-            const int recs = (c.pn * prec + c.ln * LINE_REC + 1) & ~1;
-            const int st_need = std::max(recs + (3 * vp.n_units + vp.n_items + 1) / 2 + 2, (3 * sp.n_units + sp.n_items + 1) / 2 + 2);
-            const int ar_need = (e_off[c.lmb + c.lmn] - e_off[c.lmb]) + 3 * c.lmn + 8;
-            max_stage = std::max(max_stage, st_need); max_area = std::max(max_area, ar_need);
-            if (stage_chk >= 0 && (st_need > stage_chk || ar_need > area_chk)) {
-                set_error("gather program does not fit the LDS staging area"); return TCV_ERR_TOO_LARGE;
-            }
-            const int tab[16] = {c.pb, c.pn, c.lb, c.ln, voff, vp.n_units, vp.n_wave_units, vp.n_items,
-                                 c.lmb, c.lmn, e_off[c.lmb], e_off[c.lmb + c.lmn] - e_off[c.lmb],
-                                 soff, sp.n_units, sp.n_wave_units, sp.n_items};
-            vchunk_tab.insert(vchunk_tab.end(), tab, tab + 16);
+    if (!fast_prog(PS_LM, sch_walk, sch_dest, sprog, sp)) { set_error("gather program field overflow"); return TCV_ERR_TOO_LARGE; }
+    return TCV_OK;
+}
+// gather programs of a chunk list into B.pr; measures the staging / area doubles the largest chunk needs.  stage_chk >= 0: a chunk that
+// needs more than stage_chk / area_chk is an error
+int emit_all(PlanBuild &B, const std::vector<VChunk> &vch, int stage_chk, int area_chk, int &max_stage, int &max_area) {
+    std::vector<int> &vprog = B.pr.vprog, &sprog = B.pr.sprog, &vchunk_tab = B.pr.vchunk_tab;
+    const std::vector<int> &e_off = B.e_off;
+    vprog.clear(); sprog.clear(); vchunk_tab.clear(); max_stage = 0; max_area = 0;
+    for (auto &c : vch) {
+        while (vprog.size() & 3) vprog.push_back(0);        // every program starts 16-byte aligned (vector loads on the device)
+        while (sprog.size() & 3) sprog.push_back(0);
+        const int voff = (int)vprog.size(), soff = (int)sprog.size();
+        ProgOut vp, sp;
+        if (int rc = B.fast_ok() ? chunk_progs_fast(B, c, vprog, sprog, vp, sp) : chunk_progs_ref(B, c, vprog, sprog, vp, sp)) return rc;
+        const int recs = (c.pn * B.prec + c.ln * LINE_REC + 1) & ~1;
+        const int st_need = std::max(recs + (3 * vp.n_units + vp.n_items + 1) / 2 + 2, (3 * sp.n_units + sp.n_items + 1) / 2 + 2);
+        const int ar_need = (e_off[c.lmb + c.lmn] - e_off[c.lmb]) + 3 * c.lmn + 8;
+        max_stage = std::max(max_stage, st_need); max_area = std::max(max_area, ar_need);
+        if (stage_chk >= 0 && (st_need > stage_chk || ar_need > area_chk)) {
+            set_error("gather program does not fit the LDS staging area"); return TCV_ERR_TOO_LARGE;
         }
-        return TCV_OK;
-    };
-    lap("landmark slots");
-    static thread_local std::vector<int> vprog, sprog, vchunk_tab;      // (reused: a plan per window per frame)
-    if (use_chain) {
-        // chain layout: the LDS pool (staging | landmark coupling area) is small, so the landmarks are dealt evenly to the
-        // smallest number k of chunks whose EXACT programs fit; the line factors are spread over the chunks
-        bool found = false;
-        // lower bound on k from the records alone, then jump by the measured overshoot: two exact trials instead of k
-        const int kmax = std::max(1, std::min(L, 48));
-        int k = std::max(1, (nproj * prec + nline * LINE_REC + c_pool - 1) / std::max(1, c_pool));
-        if (const char *ek = getenv("TCV_VIS_CHUNKS")) k = std::max(k, atoi(ek));      // tuning experiments
-        k = std::max(k, std::min(coop_chunks, kmax));
-        for (; k <= kmax && !found;) {
-            // point factors: an even split, except that a boundary a few factors above a multiple of 64 is pulled down to it -- one lane
-            // evaluates one factor, so 64 + 68 + 68 factors cost five wavefront passes of the evaluation and 64 + 64 + 72 cost four.  Line
-            // factors: dealt so that the chunks' record volumes even out (the chunk with more point factors gets fewer lines).
-            std::vector<VChunk> cand;
-            int l = 0, lines_left = nline, lb_next = 0;
-            const long long rec_even = ((long long)nproj * prec + (long long)nline * LINE_REC) / k;
-            for (int c = 0; c < k; c++) {
-                VChunk cur{lmptr[l], 0, lb_next, 0, l, 0};
-                int target = (int)((long long)(c + 1) * nproj / k);
-                if (target % 64 <= 8 && target >= 64) target -= target % 64;
-                while (l < L && (c == k - 1 || lmptr[l + 1] <= target || cur.lmn == 0)) { cur.pn += lmptr[l + 1] - lmptr[l]; cur.lmn++; l++; }
-                int ln_c = c == k - 1 ? lines_left : (int)std::max<long long>(0, std::min<long long>(lines_left, (rec_even - (long long)cur.pn * prec + LINE_REC / 2) / LINE_REC));
-                cur.ln = ln_c; lb_next += ln_c; lines_left -= ln_c;
-                cand.push_back(cur);
-            }
-            int ms = 0, ma = 0;
-            if (coop_chunks > 0 && k < kmax) {      // one lane per point factor: a cooperative chunk holds at most one pass of a 256-thread helper
-                bool wide = false;
-                for (auto &c : cand) wide = wide || c.pn > 256;
-                if (wide) { k++; continue; }
-            }
-            if (emit_all(cand, -1, -1, vprog, sprog, vchunk_tab, ms, ma) != TCV_OK) { k++; continue; }
-            ma = (ma + 1) & ~1;
-            if (getenv("TCV_DEBUG_PACK")) fprintf(stderr, "[pack] k %d ms %d ma %d pool %d\n", k, ms, ma, c_pool);
-            if (ms + ma <= c_pool) { found = true; vch = cand; area_cap = ma; stage_cap = c_pool - ma; }
-            else k = std::max(k + 1, std::min(kmax, (int)(((long long)k * (ms + ma) + c_pool - 1) / c_pool)));      // need(k) ~ a / k + b, b > 0: never overshoots the smallest k
-        }
-        if (!found) {      // the visual half does not fit the chain layout's pool: the dense layout (its camera half, its slot offsets are the same)
-            use_chain = false;
-            if (!dense_fits) { set_error("window too large for the fused solver (LDS; its speed-bias blocks do not form a chain either)"); return TCV_ERR_TOO_LARGE; }
-            const int rc = cam_for(false);
-            if (rc != TCV_OK) return rc;
-            area_cap = LDS_DOUBLES - ntiles * 256 - 2 * nxl - (3 * camw + 176) - 64;
-            stage_cap = (ntiles - pp_tiles) * 256;
-        }
+        const int tab[16] = {c.pb, c.pn, c.lb, c.ln, voff, vp.n_units, vp.n_wave_units, vp.n_items,
+                             c.lmb, c.lmn, e_off[c.lmb], e_off[c.lmb + c.lmn] - e_off[c.lmb],
+                             soff, sp.n_units, sp.n_wave_units, sp.n_items};
+        vchunk_tab.insert(vchunk_tab.end(), tab, tab + 16);
     }
-    if (!use_chain) {
-        // build_chunks sizes the chunks by an estimate of the VISUAL program; the exact programs (emit_all) may need more -- the Schur program of
-        // ragged tracks (many camera-block pairs per landmark) does: the chunks are then cut for a smaller budget until the exact programs fit
-        int cap_try = stage_cap, rc = TCV_OK;
-        std::string first_msg;
-        for (int attempt = 0; attempt < 12; attempt++) {
-            const int rcb = build_chunks(cap_try, area_cap, vch);
-            if (rcb != TCV_OK) { if (attempt == 0) return rcb; rc = TCV_ERR_TOO_LARGE; break; }      // (a single landmark no longer fits the reduced budget)
-            int ms = 0, ma = 0;
-            rc = emit_all(vch, stage_cap, area_cap, vprog, sprog, vchunk_tab, ms, ma);
-            if (rc != TCV_ERR_TOO_LARGE) break;
-            if (first_msg.empty()) first_msg = tcv_last_error();
-            cap_try = cap_try * 4 / 5;
-        }
-        if (rc != TCV_OK) { if (!first_msg.empty()) set_error(first_msg); return rc; }
-    }
-    lap("chunks + gather programs");
-    set_error("");
+    return TCV_OK;
+}
 
-    // ---- the plan: header = the camera half's fields + the window's own, int pool = [camera half | visual half]
+// ---- 7. the fit loops
+// chain layout: the LDS pool (staging | landmark coupling area) is small, so the landmarks are dealt evenly to the smallest number k of
+// chunks whose EXACT programs fit, and the pool is split by what they need.  No such k: the dense layout (its slot offsets are the same).
+int fit_chain(PlanBuild &B) {
+    static const bool dbg_k = getenv("TCV_DEBUG_PACK") != nullptr;
+    const int c_pool = B.c_pool;
+    // lower bound on k from the records alone, then jump by the measured overshoot: two exact trials instead of k
+    const int kmax = std::max(1, std::min(B.L, 48));
+    int k = std::max(1, (B.nproj * B.prec + B.nline * LINE_REC + c_pool - 1) / std::max(1, c_pool));
+    k = std::max(k, std::min(B.coop_chunks, kmax));
+    while (k <= kmax) {
+        std::vector<VChunk> cand;
+        chain_chunks(B, k, cand);
+        if (B.coop_chunks > 0 && k < kmax) {      // one lane per point factor: a cooperative chunk holds at most one pass of a 256-thread helper
+            bool wide = false;
+            for (auto &c : cand) wide = wide || c.pn > 256;
+            if (wide) { k++; continue; }
+        }
+        int ms = 0, ma = 0;
+        if (emit_all(B, cand, -1, -1, ms, ma) != TCV_OK) { k++; continue; }
+        ma = (ma + 1) & ~1;
+        if (dbg_k) fprintf(stderr, "[pack] k %d ms %d ma %d pool %d\n", k, ms, ma, c_pool);
+        if (ms + ma <= c_pool) { B.vch.swap(cand); B.area_cap = ma; B.stage_cap = c_pool - ma; return TCV_OK; }
+        k = std::max(k + 1, std::min(kmax, (int)(((long long)k * (ms + ma) + c_pool - 1) / c_pool)));      // need(k) ~ a / k + b, b > 0: never overshoots the smallest k
+    }
+    return use_dense_layout(B);
+}
+// dense layout: dense_chunks sizes the chunks by an estimate of the VISUAL program; the exact programs (emit_all) may need more -- the Schur
+// program of ragged tracks (many camera-block pairs per landmark) does: the chunks are then cut for a smaller budget until the exact programs fit
+int fit_dense(PlanBuild &B) {
+    int cap_try = B.stage_cap, rc = TCV_OK;
+    std::string first_msg;
+    for (int attempt = 0; attempt < 12; attempt++) {
+        const int rcb = dense_chunks(B, cap_try, B.area_cap, B.vch);
+        if (rcb != TCV_OK) { if (attempt == 0) return rcb; rc = TCV_ERR_TOO_LARGE; break; }      // (a single landmark no longer fits the reduced budget)
+        int ms = 0, ma = 0;
+        rc = emit_all(B, B.vch, B.stage_cap, B.area_cap, ms, ma);
+        if (rc != TCV_ERR_TOO_LARGE) break;
+        if (first_msg.empty()) first_msg = tcv_last_error();
+        cap_try = cap_try * 4 / 5;
+    }
+    if (rc != TCV_OK && !first_msg.empty()) set_error(first_msg);
+    return rc;
+}
+
+// ---- 8. the plan: header = the camera half's fields + the window's own, int pool = [camera half | visual half]
+void assemble_plan(PlanBuild &B) {
+    const tcv_problem &p = B.p;
+    Packed &out = B.out;
+    const std::vector<int> &vprog = B.pr.vprog, &sprog = B.pr.sprog, &vchunk_tab = B.pr.vchunk_tab, &slotptr = B.slotptr, &slot_t = B.slot_t, &e_off = B.e_off;
+    const int L = B.L, nproj = B.nproj, nline = B.nline;
     PlanHdr &H = out.hdr;
-    H = cam->hdr;
+    H = B.cam->hdr;
     H.nland = L; H.n_proj = nproj; H.n_line = nline;
     H.hcl_total = e_off[L];
-    H.lds_area = area_cap;
-    H.c_stage_cap = stage_cap; H.c_area_cap = area_cap; H.c_pool = c_pool;
-    H.n_vis_chunk = (int)vch.size();
+    H.lds_area = B.area_cap;
+    H.c_stage_cap = B.stage_cap; H.c_area_cap = B.area_cap; H.c_pool = B.c_pool;
+    H.n_vis_chunk = (int)B.vch.size();
     PlanInts &I = out.ints;
     I.clear();
-    I.reserve(cam->ints.size() + 4 * (size_t)nproj + nline + 3 * (size_t)L + slot_t.size() + vchunk_tab.size() + vprog.size() + sprog.size() + 32);
-    I.insert(I.end(), cam->ints.begin(), cam->ints.end());
-    auto mark = [&]() { return (int)I.size(); };
+    I.reserve(B.cam->ints.size() + 4 * (size_t)nproj + nline + 3 * (size_t)L + slot_t.size() + vchunk_tab.size() + vprog.size() + sprog.size() + 32);
+    I.insert(I.end(), B.cam->ints.begin(), B.cam->ints.end());
+    auto mark = [&I]() { return (int)I.size(); };
     H.o_proj = mark();
     for (int k = 0; k < nproj; k++) {
-        const ProjFac &f = p.proj[order[k]];
-        for (int s = 0; s < 3; s++) I.push_back(cam_of[f.b[s]]);
-        I.push_back(lm_of[f.b[3]]);
+        const ProjFac &f = p.proj[out.proj_order[k]];
+        for (int s = 0; s < 3; s++) I.push_back(B.cam_of[f.b[s]]);
+        I.push_back(B.lm_of[f.b[3]]);
     }
     H.o_line = mark();
-    for (auto &f : p.line) I.push_back(cam_of[f.b]);
+    for (auto &f : p.line) I.push_back(B.cam_of[f.b]);
     H.o_lm = mark();
     for (int l = 0; l < L; l++) { I.push_back(e_off[l]); I.push_back(slotptr[l + 1] - slotptr[l]); }
     H.o_lmslotptr = mark();
@@ -1335,29 +1184,53 @@ static int pack_plan(const tcv_problem &p, Packed &out, int mode, int chain_lds,
     H.o_sunit = H.o_sdest; H.n_sunit = (int)sprog.size(); H.o_sitem = H.o_sdest; H.n_sitem = 0;
     while ((I.size() & 3) != 0) I.push_back(0);          // plans are concatenated: keep every plan 16-byte aligned
     H.plan_ints = (int)I.size();
-    out.cam_loff = cam->loff;
-    lap("plan assembly");
+    out.cam_loff = B.cs.loff;
+}
+}  // namespace
+
+static int pack_plan(const tcv_problem &p, Packed &out, int mode, int chain_lds, int coop_chunks) {
+    PlanBuild B{p, out, mode, chain_lds, coop_chunks};
+    if (int rc = classify_blocks(B)) return rc;
+    if (int rc = camera_budgets(B)) return rc;
+    if (int rc = choose_cam(B)) return rc;
+    B.lap("classification + camera half");
+    if (int rc = landmark_slots(B)) return rc;
+    B.lap("landmark slots");
+    if (B.use_chain) { if (int rc = fit_chain(B)) return rc; }      // (may turn to the dense layout: B.use_chain false, its chunks still to make)
+    if (!B.use_chain) { if (int rc = fit_dense(B)) return rc; }
+    B.lap("chunks + gather programs");
+    set_error("");
+    assemble_plan(B);
+    B.lap("plan assembly");
     return TCV_OK;
 }
 
 // data half: the window's doubles in the layout the plan expects (offsets depend on the counts only).  The sink either counts
-// (dst == nullptr) or writes: a batch first sizes every window, then all windows are written straight into one upload buffer.
-namespace {
-struct Sink {
-    double *dst;
-    size_t n = 0;
-    explicit Sink(double *d) : dst(d) {}
-    void put(const double *s, size_t k) { if (dst) std::memcpy(dst + n, s, k * sizeof(double)); n += k; }
-    void put1(double v) { if (dst) dst[n] = v; n++; }
-    void zeros(size_t k) { if (dst) std::memset(dst + n, 0, k * sizeof(double)); n += k; }
-};
-}  // namespace
+// (no destination) or writes: a batch first sizes every window, then all windows are written straight into one upload buffer.
+// The three record layouts the marginalisation packer (tcv_marg.hip pack_marg) writes too:
+void put_imu_const(Sink &D, const tcv_imu_preintegration &q) {
+    D.put(q.delta_p, 3); D.put(q.delta_q, 4); D.put(q.delta_v, 3); D.put(q.linearized_ba, 3); D.put(q.linearized_bg, 3); D.put1(q.sum_dt);
+    const int rc[5][2] = {{0, 9}, {0, 12}, {3, 12}, {6, 9}, {6, 12}};   // dp_dba dp_dbg dq_dbg dv_dba dv_dbg (imu_factor.h:61-79)
+    for (auto &b : rc) for (int i = 0; i < 3; i++) D.put(q.jacobian + (b[0] + i) * 15 + b[1], 3);
+    D.put(q.covariance, 225);
+}
+void put_prior_region(Sink &D, const tcv_prior &pr, int k0) {
+    const int n = pr.n, nr = n - k0;
+    for (int j = 0; j < n; j++) D.put(pr.J0.data() + (size_t)n * j + k0, nr);
+    D.put(pr.r0.data() + k0, nr);
+    D.put(pr.x0.data(), pr.x0.size());
+}
+int put_proj_record(Sink &D, const ProjFac &f, const ProjFac &first) {
+    if (&f != &first && (f.sqrt_info != first.sqrt_info || f.loss_a != first.loss_a)) { set_error("projection factors must share sqrt_info and loss"); return TCV_ERR_UNSUPPORTED; }
+    D.put(f.pts, 6);
+    if (f.btd >= 0) D.put(f.aux, 8);
+    return TCV_OK;
+}
 
 static int pack_data_to(const tcv_problem &p, Packed &out, const double *imu_sqrt, Sink &D) {
     const PlanHdr &H = out.hdr;
     const int nblk = (int)out.cam_block.size(), L = (int)out.lm_block.size();
     const std::vector<int> &order = out.proj_order;
-    const bool with_td = (H.flags & 1) != 0;
     const tcv_prior *pr = p.prior.empty() ? nullptr : p.prior[0].prior;
     WinHdr &W = out.win;
     const int plan_id = W.plan;
@@ -1381,20 +1254,12 @@ static int pack_data_to(const tcv_problem &p, Packed &out, const double *imu_sqr
         if (imu_on_device) break;
         if (f.dev) { if (int rc = tcv_preint_host(f.dev)) return rc; }
         const tcv_imu_preintegration &q = f.dev ? f.dev->pod : f.pre;
-        D.put(q.delta_p, 3); D.put(q.delta_q, 4); D.put(q.delta_v, 3); D.put(q.linearized_ba, 3); D.put(q.linearized_bg, 3); D.put1(q.sum_dt);
-        const int rc[5][2] = {{0, 9}, {0, 12}, {3, 12}, {6, 9}, {6, 12}};   // dp_dba dp_dbg dq_dbg dv_dba dv_dbg (imu_factor.h:61-79)
-        for (auto &b : rc) for (int i = 0; i < 3; i++) D.put(q.jacobian + (b[0] + i) * 15 + b[1], 3);
-        D.put(q.covariance, 225);
+        put_imu_const(D, q);
     }
     W.d_proj = (int)D.n;
-    double psi = 0, pla = 0;
-    for (size_t k = 0; k < order.size(); k++) {
-        const ProjFac &f = p.proj[order[k]];
-        if (k == 0) { psi = f.sqrt_info; pla = f.loss_a; }
-        else if (f.sqrt_info != psi || f.loss_a != pla) { set_error("projection factors must share sqrt_info and loss"); return TCV_ERR_UNSUPPORTED; }
-        D.put(f.pts, 6);
-        if (with_td) D.put(f.aux, 8);
-    }
+    for (size_t k = 0; k < order.size(); k++)
+        if (int rc = put_proj_record(D, p.proj[order[k]], p.proj[order[0]])) return rc;
+    const double psi = order.empty() ? 0.0 : p.proj[order[0]].sqrt_info, pla = order.empty() ? 0.0 : p.proj[order[0]].loss_a;
     W.d_line = (int)D.n;
     double lla = 0;
     for (size_t k = 0; k < p.line.size(); k++) {
@@ -1432,11 +1297,9 @@ static int pack_data_to(const tcv_problem &p, Packed &out, const double *imu_sqr
         out.dev_prior_doubles = nr * n + nr + pr->xsize;
     } else if (pr) {      // the rows of the thresholded eigenvalues (exact zeros in J0 and r0) are dropped, tcv_packed.h
         if (int rc = tcv_prior_host(pr)) return rc;
-        const int n = pr->n, k0 = prior_keep_zero_rows() ? 0 : prior_zero_rows(pr->J0.data(), pr->r0.data(), n), nr = n - k0;
+        const int k0 = prior_keep_zero_rows() ? 0 : prior_zero_rows(pr->J0.data(), pr->r0.data(), pr->n);
         W.prior_k0 = k0;
-        for (int j = 0; j < n; j++) D.put(pr->J0.data() + (size_t)n * j + k0, nr);
-        D.put(pr->r0.data() + k0, nr);
-        D.put(pr->x0.data(), pr->x0.size());
+        put_prior_region(D, *pr, k0);
     }
     W.d_misc = (int)D.n;
     D.put(p.G, 3); D.put1(psi); D.put1(pla); D.put1(lla); D.put1(p.td_TR); D.put1(p.td_ROW); D.put1(p.line_exact ? 1.0 : 0.0);
@@ -1446,15 +1309,6 @@ static int pack_data_to(const tcv_problem &p, Packed &out, const double *imu_sqr
     W.n_doubles = (int)D.n;
     if (D.dst) for (size_t i = 0; i < D.n; i++) { const double v = D.dst[i]; if (!(v == v) || v > 1e300 || v < -1e300) { set_error("NaN/Inf in window data"); return TCV_ERR_NUMERIC; } }
     return TCV_OK;
-}
-
-static int pack_data(const tcv_problem &p, Packed &out, const double *imu_sqrt) {
-    Sink cnt(nullptr);
-    int rc = pack_data_to(p, out, imu_sqrt, cnt);
-    if (rc != TCV_OK) return rc;
-    out.doubles.resize(cnt.n);
-    Sink w(out.doubles.data());
-    return pack_data_to(p, out, imu_sqrt, w);
 }
 
 int pack_problem_data(const tcv_problem &p, Packed &out, const double *imu_sqrt, double *dst) {
@@ -1493,7 +1347,7 @@ struct KeyHash { size_t operator()(const PlanKey &k) const { return k.h; } };
 //  * A structure enters the cache at its SECOND appearance: every shard remembers the hashes of its last 64 misses; a miss whose hash is
 //    not among them builds its plan for the caller alone (no template, no eviction, the int pool goes back to the block pool with the
 //    batch, still warm), a miss that is builds it again and keeps it.  A bench / streaming loop pays one extra build per structure, a live
-//    estimator none of the bookkeeping.  TCV_PLAN_CACHE_EAGER=1: insert at first sight (the behaviour up to round 5).
+//    estimator none of the bookkeeping.
 struct CacheEntry { PlanKey key; std::shared_ptr<const PlanTemplate> tmpl; };
 enum { CACHE_SHARDS = 16, CACHE_SHARD_ENTRIES = 24, CACHE_RECENT = 64 };
 struct CacheShard {
@@ -1566,12 +1420,9 @@ int pack_problem(const tcv_problem &p, Packed &out, const double *imu_sqrt, int 
     PlanKey key;
     std::shared_ptr<const PlanTemplate> T;
     std::memset(&out.win, 0, sizeof out.win);
-    static const bool dbg_t = getenv("TCV_DEBUG_PACK2") != nullptr;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) { if (dbg_t) { const auto t = std::chrono::steady_clock::now(); pack_lap_add(what, std::chrono::duration<double, std::micro>(t - t_prev).count()); t_prev = std::chrono::steady_clock::now(); } };
-    bool keep = false;      // the structure has been seen before (or TCV_PLAN_CACHE_EAGER): its plan goes into the cache
+    Lap lap;
+    bool keep = false;      // the structure has been seen before: its plan goes into the cache
     if (!no_cache) {
-        static const bool eager = getenv("TCV_PLAN_CACHE_EAGER") != nullptr;
         structure_key(p, mode, c_lds, coop_chunks, key);
         CacheShard &S = shard_of(key);
         std::lock_guard<std::mutex> g(S.mu);
@@ -1579,7 +1430,6 @@ int pack_problem(const tcv_problem &p, Packed &out, const double *imu_sqrt, int 
         if (it != S.map.end()) { S.lru.splice(S.lru.begin(), S.lru, it->second); T = it->second->tmpl; g_hits.fetch_add(1, std::memory_order_relaxed); }
         else {
             g_misses.fetch_add(1, std::memory_order_relaxed);
-            keep = eager;
             for (int i = 0; i < CACHE_RECENT && !keep; i++) keep = S.recent[i] == key.h;
             if (!keep) { S.recent[S.recent_next] = key.h; S.recent_next = (S.recent_next + 1) % CACHE_RECENT; }
         }
@@ -1615,13 +1465,13 @@ int pack_problem(const tcv_problem &p, Packed &out, const double *imu_sqrt, int 
         }
     }
     lap("template + cache insert");
-    if (plan_only) {      // size only: the caller writes the data with pack_problem_data once every window of its batch has an offset
-        Sink cnt(nullptr);
-        const int rcd = pack_data_to(p, out, imu_sqrt, cnt);
-        lap("data size");
-        return rcd;
-    }
-    return pack_data(p, out, imu_sqrt);
+    Sink cnt(nullptr);
+    const int rcd = pack_data_to(p, out, imu_sqrt, cnt);
+    lap("data size");
+    if (rcd != TCV_OK || plan_only) return rcd;      // size only: the caller writes the data with pack_problem_data once every window of its batch has an offset
+    out.doubles.resize(cnt.n);
+    Sink w(out.doubles.data());
+    return pack_data_to(p, out, imu_sqrt, w);
 }
 
 }  // namespace tcv

@@ -22,22 +22,6 @@ enum { CAM_W = 176, CAM_MAX = 184 };      // camera tangent dims the fused solve
 enum { TILE = 16, TILE_ELEMS = 256 };
 enum { LDS_DOUBLES = 20480 };  // 160 KiB per workgroup on gfx950
 int chain_lds_doubles();       // LDS doubles of a chain-mode workgroup (two per CU); tcv_pack.cpp
-// Host threads a batch-level operation may start: min(want, cores the process is GRANTED / batch-level operations running right now).
-// The grant is the cgroup CPU quota (cpu.max) or the affinity mask, not the machine's thread count: four callers packing 512 windows each on
-// sixteen threads under a 16-core quota used to run 64 threads into the scheduler's throttling.  tcv_pack.cpp
-struct HostOp { HostOp(); ~HostOp(); int threads(int want) const; };
-int host_threads(int want);      // the same share for code that runs inside somebody's HostOp (does not count as an operation of its own)
-}  // namespace tcv
-#include <functional>
-namespace tcv {
-// fn(t) for t in [0, nth): index claiming by the calling thread and by persistent worker threads (created once, tcv_pack.cpp); returns
-// when all have finished.  nth <= 1: plain call.
-void parallel_run(int nth, const std::function<void(int)> &fn);
-// items 0 .. n - 1 claimed ONE AT A TIME by up to nth threads (the caller among them): fn(item, slot), slot < nth unique per thread.  A
-// worker that wakes up late finds fewer items instead of a fixed share nobody else may touch (a strided split of 64 windows over 8 threads
-// waited a whole share -- 0.36 ms -- for the last two workers).
-void parallel_items(int n, int nth, const std::function<void(int, int)> &fn);
-void async_run(std::function<void()> fn);      // fn() on a worker thread, some time later; nobody waits (here and now if the process has no worker)
 bool prior_keep_zero_rows();   // developer A/B switch TCV_PRIOR_FULL (re-read by every tcv_batch_create / tcv_solve); tcv_pack.cpp
 void prior_refresh_switch();
 enum { MAX_TRACE = 64 };

@@ -30,3 +30,21 @@ def add_relocalisation(win, f=4, seed=0, sigma_px=1.0 / 460.0):
     out = dict(win)
     out["relo"] = dict(pose=pose, frame_i=np.array(frame_i, int), landmark=np.array(landmark, int), pts_i=np.array(pts_i).reshape(-1, 3), pts_j=np.array(pts_j).reshape(-1, 3))
     return out
+
+
+def hip_relo_window(tcv, w):
+    """the window of add_relocalisation through the C-ABI: (tcv.Window, the relocalisation pose's array -- the caller keeps it alive)"""
+    W = tcv.Window(w)
+    rl = w["relo"]
+    relo = tcv.f64(rl["pose"]).copy()
+    L = tcv.lib()
+    tcv.check(L.tcv_problem_add_parameter_block(W.h, tcv.dptr(relo), 7, tcv.TCV_PARAM_POSE))       # :1857-1858
+    pr = w["proj"]
+    keep = []
+    for k in range(len(rl["frame_i"])):
+        pi, pj = tcv.f64(rl["pts_i"][k]).copy(), tcv.f64(rl["pts_j"][k]).copy()
+        keep.append((pi, pj))
+        tcv.check(L.tcv_problem_add_projection_factor(W.h, tcv.dptr(pi), tcv.dptr(pj), float(pr["sqrt_info"]), float(pr["loss_a"]),
+                                                      W.block_ptr("pose", int(rl["frame_i"][k])), tcv.dptr(relo), tcv.dptr(W.ex), W.block_ptr("lam", int(rl["landmark"][k]))))      # :1878-1880
+    W._relo_keep = keep
+    return W, relo

@@ -2,34 +2,15 @@
 ProjectionFactor per matched landmark on (para_Pose[start], relo_Pose, para_Ex_Pose[0], para_Feature[idx]).  The camera side of the
 window grows to 177 tangent dims (12 x 6 + 6 + 11 x 9): the chain layout holds it (pose system 78 + 1 wide, still five tile rows; the
 vectors over the camera tangent space are 184 wide for such a plan, PlanHdr::camw).  HIP path vs the NumPy oracle."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import np_oracle as NO
 import synth
-from relo_util import add_relocalisation
+from relo_util import add_relocalisation, hip_relo_window
 from util import golden_windows, rel
 
 pytestmark = pytest.mark.gpu
-
-
-def hip_relo_window(tcv, w):
-    W = tcv.Window(w)
-    rl = w["relo"]
-    relo = tcv.f64(rl["pose"]).copy()
-    L = tcv.lib()
-    tcv.check(L.tcv_problem_add_parameter_block(W.h, tcv.dptr(relo), 7, tcv.TCV_PARAM_POSE))       # :1857-1858
-    pr = w["proj"]
-    keep = []
-    for k in range(len(rl["frame_i"])):
-        pi, pj = tcv.f64(rl["pts_i"][k]).copy(), tcv.f64(rl["pts_j"][k]).copy()
-        keep.append((pi, pj))
-        tcv.check(L.tcv_problem_add_projection_factor(W.h, tcv.dptr(pi), tcv.dptr(pj), float(pr["sqrt_info"]), float(pr["loss_a"]),
-                                                      W.block_ptr("pose", int(rl["frame_i"][k])), tcv.dptr(relo), tcv.dptr(W.ex), W.block_ptr("lam", int(rl["landmark"][k]))))      # :1878-1880
-    W._relo_keep = keep
-    return W, relo
 
 
 @pytest.mark.parametrize("which", ["golden_with_prior_and_lines", "synthetic_points_only"])

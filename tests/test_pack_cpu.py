@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import synth
+from relo_util import add_relocalisation, hip_relo_window
 from util import golden_windows, sub_window
 
 
@@ -89,7 +90,21 @@ def _replay_like_windows():
         wins.append({k: v for k, v in w.items() if k != "prior"})
     wins.append(synth.window_at(synth.make_windows(600, 1, n_landmarks=200), 0))
     wins += [sub_window(synth.window_at(synth.make_windows(400, 1), 0), f) for f in (3, 6)]
+    # ProjectionTdFactor windows (the four-column factor, Td's gather slot) and relocalisation windows (the 184-wide camera vectors); the
+    # latter are those of tests/test_gpu_relo.py, refused alike by both builders in the dense layout
+    wins.append(synth.with_time_offset(synth.window_at(synth.make_windows(916, 1), 0), 916))
+    wins.append(synth.with_time_offset(main, 917))
+    wins.append(add_relocalisation(main, f=4, seed=1))
+    wins.append(add_relocalisation(dict(synth.window_at(synth.make_windows(9300, 1, with_lines=False), 0), prior=None), f=6, seed=2))
     return wins
+
+
+def _window(tcv, w):
+    """tcv.Window of one of _replay_like_windows()"""
+    if "relo" not in w:
+        return tcv.Window(w)
+    W, W._relo_pose = hip_relo_window(tcv, w)
+    return W
 
 
 def test_fast_packer_builds_the_reference_plans_int_by_int(tcv):
@@ -107,7 +122,7 @@ def test_fast_packer_builds_the_reference_plans_int_by_int(tcv):
             for variant in (0, 1):
                 L.tcv_set_solver_variant(variant)
                 for i, w in enumerate(wins):
-                    W = tcv.Window(w)
+                    W = _window(tcv, w)
 
                     def plan():      # (a window that does not fit a layout must fail the same way on both paths)
                         try:
@@ -180,8 +195,8 @@ def test_a_structure_enters_the_plan_cache_at_its_second_appearance(tcv):
 
 
 def test_items_of_a_parallel_section_are_each_run_once(tcv):
-    """tcv_problems_pack_bench packs its windows through the worker pool's one-at-a-time claim (parallel_items) and through the fixed-share
-    split: every window ends up packed (a return code per window), on 1 .. 8 threads, frames of 5"""
+    """tcv_problems_pack_bench packs its windows through the worker pool's one-at-a-time claim (parallel_items):
+    every window ends up packed (a return code per window), on 1 .. 8 threads, frames of 5"""
     import ctypes as C
     import os
     L = tcv.lib()
