@@ -13,7 +13,9 @@ trust-region decisions are borderline may legitimately take another branch; such
 has to agree.  Mutations produce ill-posed windows too (a pose seen by one feature and no IMU factor, landmarks seen once at no parallax, two
 frames without a prior): there the answer is set by rounding in directions only the trust region's mu D^2 holds.  The checker measures
 that on the ORACLE ALONE -- the same window with its states moved by 1e-13 relative, three draws -- and allows the device 30x the oracle's
-own movement where that exceeds 1e-6 (`ok~`: listed with the measured sensitivity).
+own movement where that exceeds 1e-6 (`ok~`: listed with the measured sensitivity).  First step and states are held to that rule as a
+whole AND within every parameter family (positions, rotations, velocities, accelerometer and gyro biases, extrinsic translation and
+rotation, inverse depths), each family relative to the oracle's own magnitude in it and priced by the oracle's own movement in it.
 
     python tests/dev/fuzz_solve.py [cases] [first seed]
 """
@@ -26,10 +28,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, os.path.join(ROOT, "tc-viml_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import np_oracle as NO      # noqa: E402
 import orc      # noqa: E402
 import synth    # noqa: E402
 import tcv      # noqa: E402
-from util import fro, golden_windows, rel, sub_window      # noqa: E402
+from util import fro, fro_by_family, golden_windows, rel, rel_by_family, state_families, sub_window, tangent_families      # noqa: E402
 
 TOL = 1e-6
 
@@ -133,9 +136,15 @@ def make_case(rng, seed):
 
 
 def oracle_sensitivity(w_orc, exc, so0, st0):
-    """how far the oracle's own first step / final cost / states move when the window's states move by 1e-13 relative"""
+    """how far the oracle's own first step / final cost / states move when the window's states move by 1e-13 relative; `first_family` and
+    `state_family`: the same within every parameter family (util.tangent_families / util.state_families); `tangent`: the index sets"""
     f0 = np.array(so0.first_delta[:so0.n_local])
-    sens = dict(first=0.0, cost=0.0, pose=0.0, sb=0.0, ex=0.0, lam=0.0)
+    sens = dict(first=0.0, cost=0.0, pose=0.0, sb=0.0, ex=0.0, lam=0.0, first_family={}, state_family={},
+                tangent=tangent_families(NO.Problem(w_orc, ex_constant=exc)))
+
+    def worst(into, d):
+        for name, v in d.items():
+            into[name] = max(into.get(name, 0.0), v)
     for rep in range(3):
         r2 = np.random.Generator(np.random.PCG64(977 + rep))
         w2 = dict(w_orc)
@@ -146,10 +155,12 @@ def oracle_sensitivity(w_orc, exc, so0, st0):
         f1 = np.array(so.first_delta[:so.n_local])
         if len(f0):
             sens["first"] = max(sens["first"], fro(f1, f0))
+            worst(sens["first_family"], fro_by_family(f1, f0, sens["tangent"]))
         sens["cost"] = max(sens["cost"], abs(so.final_cost - so0.final_cost) / max(so0.final_cost, 1e-12))
         st = O.states()
         for key in ("pose", "sb", "ex", "lam"):
             sens[key] = max(sens[key], rel(st[key], st0[key]))
+        worst(sens["state_family"], rel_by_family(state_families(st), state_families(st0)))
     return sens
 
 
@@ -164,6 +175,12 @@ def compare(W, b, s, k, O, so, sens):
         if not d1 < 30 * sens["first"]:
             return "FIRST STEP", f"first step differs {d1:.2e} (oracle moves {sens['first']:.1e})"
         soft.append(f"first step {d1:.1e} / oracle {sens['first']:.1e}")
+    for name, d in (fro_by_family(fg, fo, sens["tangent"]) if len(fo) else {}).items():
+        m = sens["first_family"].get(name, 0.0)
+        if not d < TOL:
+            if not d < 30 * m:
+                return "FIRST STEP", f"first step differs in {name} {d:.2e} (oracle moves {m:.1e})"
+            soft.append(f"first step {name} {d:.1e} / oracle {m:.1e}")
     n = so.num_iterations
     same = s.num_iterations == n and s.termination == so.termination and \
         [s.dogleg_case[i] for i in range(1, n)] == [so.dogleg_case[i] for i in range(1, n)] and [s.step_ok[i] for i in range(1, n)] == [so.step_ok[i] for i in range(1, n)]
@@ -181,6 +198,12 @@ def compare(W, b, s, k, O, so, sens):
             if not r < 30 * sens[key]:
                 return "STATE", f"{key} differs {r:.2e} (oracle moves {sens[key]:.1e})"
             soft.append(f"{key} {r:.1e} / oracle {sens[key]:.1e}")
+    for name, r in rel_by_family(state_families(sg), state_families(st)).items():
+        m = sens["state_family"].get(name, 0.0)
+        if not r < TOL:
+            if not r < 30 * m:
+                return "STATE", f"{name} differs {r:.2e} (oracle moves {m:.1e})"
+            soft.append(f"{name} {r:.1e} / oracle {m:.1e}")
     return ("ok~", "; ".join(soft)) if soft else ("ok", "")
 
 

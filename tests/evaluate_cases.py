@@ -51,11 +51,13 @@ def oracle_state(P, W, relo=None):
 
 def oracle_evaluate(w, x=None, ex_constant=False):
     """dict(cost, family_cost (4), residuals, block_costs, gradient) of np_oracle.Problem(w) at x (default: the window's own states), in the
-    product's order"""
+    product's order; scale = |J|'|r| (the magnitude each gradient entry is summed from); row_family / block_family: the factor family
+    (index into FACTOR_FAMILIES) of every residual row / residual block"""
     P = NO.Problem(w, ex_constant=ex_constant)
     x = P.x0() if x is None else x
     J, r, cost = P.linearize(x)
     g = J.T @ r
+    scale = np.abs(J).T @ np.abs(r)
     fam_of = {"prior": 0, "imu": 1, "proj": 2, "proj_td": 2, "proj_relo": 2, "line": 3}
     rank = {"prior": 0, "imu": 1, "proj": 2, "proj_td": 2, "proj_relo": 3, "line": 4}
     rows, blocks, fam, o = [], [], np.zeros(4), 0
@@ -66,7 +68,53 @@ def oracle_evaluate(w, x=None, ex_constant=False):
         o += len(rf)
     rows.sort(key=lambda t: (t[0], t[1])); blocks.sort(key=lambda t: (t[0], t[1]))
     idx = np.concatenate([t[2] for t in rows]) if rows else np.zeros(0, int)
-    return dict(cost=cost, family_cost=fam, residuals=r[idx], block_costs=np.array([t[2] for t in blocks]), gradient=g, problem=P)
+    row_family = np.concatenate([np.full(len(t[2]), t[0]) for t in rows]) if rows else np.zeros(0, int)
+    return dict(cost=cost, family_cost=fam, residuals=r[idx], block_costs=np.array([t[2] for t in blocks]), gradient=g, problem=P,
+                scale=scale, row_family=row_family, block_family=np.array([t[0] for t in blocks], dtype=int))
+
+
+FACTOR_FAMILIES = ("prior", "imu", "point", "relocalisation point", "line")          # (the `rank` of oracle_evaluate)
+
+
+def factor_families(family):
+    """name -> indices of the rows / blocks of each factor family, for util.rel_by_family"""
+    return {name: np.nonzero(family == k)[0] for k, name in enumerate(FACTOR_FAMILIES) if np.any(family == k)}
+
+
+def gradient_error_by_family(g, o):
+    """name -> max_i |g - g_ref|_i / scale_i within each tangent family of the oracle's problem, scale = |J|'|r|: each product J_ki r_k is
+    good to the factor evaluators' gate, so their sum is good to that gate times sum_k |J_ki| |r_k|.  Where the scale is exactly zero (a
+    block no factor touches) the entry has to be exactly zero (inf otherwise)."""
+    from util import tangent_families
+    g = np.asarray(g, dtype=float)
+    d, s = np.abs(g - o["gradient"]), o["scale"]
+    out = {}
+    for name, ix in tangent_families(o["problem"]).items():
+        if len(ix) == 0:
+            continue
+        z = s[ix] == 0
+        if np.any(g[ix][z] != 0):
+            out[name] = float("inf")
+            continue
+        out[name] = float((d[ix][~z] / s[ix][~z]).max()) if np.any(~z) else 0.0
+    return out
+
+
+def oracle_gradient_movement(w, x, o, ex_constant=False):
+    """name -> how far the NumPy oracle's OWN gradient moves, in the units of gradient_error_by_family, when the states x move by 1e-13
+    relative (poses, speed-biases, inverse depths; three draws: the measure tests/dev/fuzz_solve.py oracle_sensitivity prices ill-posed
+    windows with).  Near a minimum the residuals are small differences of large terms, so |J|'|r| shrinks while what a rounding of the
+    states does to J'r does not."""
+    out = {}
+    for rep in range(3):
+        rng = np.random.Generator(np.random.PCG64(977 + rep))
+        x2 = dict(x)
+        for key in ("pose", "sb", "lam"):
+            a = np.asarray(x[key], dtype=float)
+            x2[key] = a * (1 + 1e-13 * rng.standard_normal(a.shape))
+        for name, v in gradient_error_by_family(oracle_evaluate(w, x2, ex_constant=ex_constant)["gradient"], o).items():
+            out[name] = max(out.get(name, 0.0), v)
+    return out
 
 
 def directional_error(cost_at, g, plus, x, d, eps=1e-6):

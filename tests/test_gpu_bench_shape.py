@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import synth
-from util import fro, rel
+from util import fro, rel, rel_by_family, state_families
 
 pytestmark = pytest.mark.gpu
 
@@ -37,6 +37,7 @@ def test_benchmark_launch_shape_vs_oracle(gpu):
     st = batch.marg_status()
     assert list(st) == [0] * B, {int(k): int((st == k).sum()) for k in np.unique(st)}      # no window on the eigen safety net
     worst = dict(cost=0.0, pose=0.0, sb=0.0, lam=0.0, A=0.0, b=0.0)
+    worst_family = {}          # the same states within every parameter family, each relative to the oracle's own magnitude there
     diff_trace = []
     for k in range(B):
         O = orc.Window(wins[k]); so = O.solve(bench.SOLVER_ITERATIONS, True); x = O.states()
@@ -51,6 +52,9 @@ def test_benchmark_launch_shape_vs_oracle(gpu):
         worst["cost"] = max(worst["cost"], abs(s[k].final_cost - so.final_cost) / so.final_cost)
         worst["pose"] = max(worst["pose"], rel(Wm[k].pose, po)); worst["sb"] = max(worst["sb"], rel(Wm[k].sb, sb))
         worst["lam"] = max(worst["lam"], rel(Wm[k].lam, x["lam"]))
+        for name, v in rel_by_family(state_families(dict(pose=Wm[k].pose, sb=Wm[k].sb, ex=Wm[k].ex, lam=Wm[k].lam)),
+                                     state_families(dict(pose=po, sb=sb, ex=x["ex"], lam=x["lam"]))).items():
+            worst_family[name] = max(worst_family.get(name, 0.0), v)
         w2 = dict(wins[k], pose=po, speedbias=sb, ex_pose=x["ex"], lam=x["lam"])
         pref, dbg = orc.Window(w2).marginalize_old()
         P = batch.prior(k)
@@ -64,6 +68,8 @@ def test_benchmark_launch_shape_vs_oracle(gpu):
     # inverse depths 2.7e-7, A' 3.6e-7, b' 2.8e-7); north_star: 1e-6 on the final cost and the step
     assert worst["cost"] < 5e-7 and worst["pose"] < 2e-7 and worst["sb"] < 4e-7 and worst["lam"] < 3e-6, worst
     assert worst["A"] < 4e-6 and worst["b"] < 3e-6, worst
+    print("benchmark shape, worst relative error of the states per family: %s" % {k: float("%.3g" % v) for k, v in worst_family.items()})
+    assert all(v < 1e-6 for v in worst_family.values()), worst_family
 
 
 def test_plain_line_and_dumped_outputs_of_the_timed_path(gpu, tmp_path):

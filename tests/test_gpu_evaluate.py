@@ -1,7 +1,11 @@
 """Problem::Evaluate on the device (tcv_batch_evaluate / tcv_problem_evaluate, tc-viml_amd/csrc/tcv_eval.hip) against the two oracles as
 they stand -- np_oracle.Problem.linearize (J, r, cost: gradient J'r) and orc.Window.linearize_dense (g, cost) --, the exact checks
 (defined cost sum, run-to-run and batch-size independence bit for bit, no effect on what follows), consistency with the solver's
-summary, the one-problem entry point, the C++ veneer and the leak check.  Gate: the project's TOL = 1e-6 (rel / fro of tests/util.py).
+summary, the one-problem entry point, the C++ veneer and the leak check.  Gate: the project's TOL = 1e-6 (rel / fro of tests/util.py), on the
+whole vectors and, for residuals and block costs, within each factor family; every gradient entry within GRAD_TOL = 1e-10 of (|J|'|r|)_i, the
+sum it is formed from (a landmark entry is 1e-6 of the largest gradient entry: the whole-vector gate does not see it; tests/test_families_cpu.py).
+At solved states the residuals are small differences of large terms and a family beyond GRAD_TOL is held to 30 x the oracle's own movement
+under 1e-13 state noise (profiles/family_parity.txt: the gyro-bias entries, 2.7e-10).
 
 Measured on an MI355X (profiles/evaluate_parity.txt; test_zz_report prints the worst figure per quantity): against the NumPy oracle cost
 9.6e-16, residuals 1.8e-15, block costs 1.4e-15, gradient 1.2e-15; against the C oracle gradient 1.3e-15; the two oracles against each other
@@ -17,11 +21,13 @@ import pytest
 import np_oracle as NO
 import orc
 import synth
-from evaluate_cases import cases, directional_error, hip_window, no_loss, oracle_evaluate, oracle_state
-from util import fro, golden_windows, rel, sub_window
+from evaluate_cases import (cases, directional_error, factor_families, gradient_error_by_family, hip_window, no_loss, oracle_evaluate, oracle_gradient_movement,
+                            oracle_state)
+from util import fro, golden_windows, rel, rel_by_family, sub_window
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-6
+GRAD_TOL = 1e-10          # per gradient entry, in units of (|J|'|r|)_i: the gate of the factor evaluators (tests/test_gpu_factors.py TOL)
 WORST = {}
 
 
@@ -40,13 +46,28 @@ def evaluate_one(gpu, W, **kw):
     return b, b.evaluation(0)
 
 
-def check_vs_oracle(ev, o, tag):
+def check_vs_oracle(ev, o, tag, movement=None):
+    """movement: None, or a function returning name -> the oracle's own movement of the gradient in that family under 1e-13 state noise
+    (evaluate_cases.oracle_gradient_movement); a family beyond GRAD_TOL is then held to 30 x that movement, the allowance of
+    tests/dev/fuzz_solve.py for reference-measured floors, and listed by test_zz_report"""
     assert note(tag + " cost", rel(ev["cost"], o["cost"])) < TOL
     assert note(tag + " family cost", rel(ev["family_cost"], o["family_cost"])) < TOL
     assert len(ev["residuals"]) == len(o["residuals"]) and note(tag + " residuals", both(ev["residuals"], o["residuals"])) < TOL
     assert len(ev["block_costs"]) == len(o["block_costs"]) and note(tag + " block costs", both(ev["block_costs"], o["block_costs"])) < TOL
     assert len(ev["gradient"]) == len(o["gradient"]) and note(tag + " gradient", both(ev["gradient"], o["gradient"])) < TOL
     assert note(tag + " gradient max-norm", rel(ev["gradient_max_norm"], np.abs(o["gradient"]).max())) < TOL
+    # the same per family: every gradient entry in units of what it is summed from, residuals and block costs within each factor family
+    moved = None
+    for fam, v in gradient_error_by_family(ev["gradient"], o).items():
+        if note(tag + " gradient / |J|'|r|, " + fam, v) <= GRAD_TOL:
+            continue
+        assert movement is not None, (tag, fam, v)
+        moved = movement() if moved is None else moved
+        note(tag + " gradient / |J|'|r|, %s beyond %.0e: the oracle's own movement" % (fam, GRAD_TOL), moved[fam])
+        assert v < 30.0 * moved[fam], (tag, fam, v, moved[fam])
+    for what, key in (("residuals", "row_family"), ("block costs", "block_family")):
+        for fam, v in rel_by_family(ev[what.replace(" ", "_")], o[what.replace(" ", "_")], factor_families(o[key])).items():
+            assert note(tag + " %s, %s factors" % (what, fam), v) < TOL, (tag, what, fam, v)
 
 
 @pytest.fixture(params=["chain", "dense", "cooperative"])
@@ -71,11 +92,14 @@ def test_parity_against_both_oracles(gpu, setting):
         d = b.evaluation_dims(0)
         assert d["num_residuals"] == gpu.lib().tcv_problem_num_residuals(W.h) and d["num_residual_blocks"] == gpu.lib().tcv_problem_num_residual_blocks(W.h)
         assert d["num_local"] == gpu.lib().tcv_problem_num_effective_parameters(W.h)
-        check_vs_oracle(ev, oracle_evaluate(w, ex_constant=exc), "numpy oracle:")
+        o = oracle_evaluate(w, ex_constant=exc)
+        check_vs_oracle(ev, o, "numpy oracle:")
         if not any(w.get(k) is not None for k in ("td", "relo")) and not w["line"].get("exact_jacobian"):
             H, g, cost, n, nc = orc.Window(w, ex_constant=exc).linearize_dense()
             assert note("C oracle: cost", rel(ev["cost"], cost)) < TOL and len(g) == len(ev["gradient"])
             assert note("C oracle: gradient", both(ev["gradient"], g)) < TOL
+            for fam, v in gradient_error_by_family(ev["gradient"], dict(o, gradient=g)).items():
+                assert note("C oracle: gradient / |J|'|r|, " + fam, v) <= GRAD_TOL, (name, fam, v)
         # apply_loss_function = 0 against the oracle on the window without its loss functions
         b.evaluate(apply_loss_function=False, residuals=True, gradient=True, block_costs=True)
         check_vs_oracle(b.evaluation(0), oracle_evaluate(no_loss(w), ex_constant=exc), "numpy oracle, no loss:")
@@ -189,8 +213,9 @@ def test_consistency_with_the_solver_and_the_gauge_fixed_states(gpu):
             assert note("solver: initial_cost", rel(c0[k], s[k].initial_cost)) < TOL
             if not fused:
                 assert note("solver: final_cost", rel(c1[k], s[k].final_cost)) < TOL
-            P = NO.Problem(w)
-            check_vs_oracle(b.evaluation(k), oracle_evaluate(w, oracle_state(P, W[k])), "numpy oracle at the %s states:" % ("gauge-fixed" if fused else "solved"))
+            x = oracle_state(NO.Problem(w), W[k])
+            o = oracle_evaluate(w, x)
+            check_vs_oracle(b.evaluation(k), o, "numpy oracle at the %s states:" % ("gauge-fixed" if fused else "solved"), lambda: oracle_gradient_movement(w, x, o))
 
 
 def test_problem_evaluate_at_the_callers_current_values(gpu):
@@ -213,6 +238,8 @@ def test_problem_evaluate_at_the_callers_current_values(gpu):
     assert note("problem_evaluate: cost", rel(pe["cost"], oe["cost"])) < TOL
     assert note("problem_evaluate: residuals", both(pe["residuals"], oe["residuals"])) < TOL
     assert note("problem_evaluate: gradient", both(pe["gradient"], oe["gradient"])) < TOL
+    for fam, v in gradient_error_by_family(pe["gradient"], oe).items():
+        assert note("problem_evaluate: gradient / |J|'|r|, " + fam, v) <= GRAD_TOL, (fam, v)
     for k, v in solved.items():
         assert np.array_equal(v, W.states()[k])
     W.evaluate(apply_loss_function=False)
@@ -317,4 +344,4 @@ def test_ceres_shim_problem_evaluate(gpu, tmp_path):
 
 def test_zz_report():
     for k in sorted(WORST):
-        print("worst %-60s %.3e" % (k, WORST[k]))
+        print("worst %-100s %.3e" % (k, WORST[k]))

@@ -14,7 +14,7 @@ import pytest
 
 import orc
 import synth
-from util import fro, golden_windows, rel
+from util import fmt_families, fro, golden_windows, rel, rel_by_family, state_families
 
 pytestmark = pytest.mark.gpu
 
@@ -127,6 +127,9 @@ def test_prior_round_trip_and_chained_solve(gpu):
     assert [s.dogleg_case[i] for i in range(1, n2)] == [so2.dogleg_case[i] for i in range(1, n2)]
     assert abs(s.final_cost - so2.final_cost) < 1e-7 * so2.final_cost
     assert rel(Wn.pose, O2.states()["pose"]) < 1e-7 and rel(Wn.sb, O2.states()["sb"]) < 1e-6
+    byf = rel_by_family(state_families(Wn.states()), state_families(O2.states()))          # ... within every parameter family
+    print("chained solve on the GPU-made prior, states per family:", fmt_families(byf))
+    assert all(v < 1e-6 for v in byf.values()), byf
 
 
 def test_margin_second_new_prior_only(gpu):

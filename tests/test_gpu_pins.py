@@ -3,7 +3,9 @@ first step, finite-difference Jacobians from the residual formulas, the SciPy mi
 import numpy as np
 import pytest
 
-from util import fro, golden_windows, imu_pre, load
+import np_oracle as NO
+import orc
+from util import fmt_families, fro, fro_by_family, golden_windows, imu_pre, load, prior_diagonal_blocks, prior_families, tangent_families
 
 pytestmark = pytest.mark.gpu
 
@@ -30,6 +32,11 @@ def test_first_step_matches_the_50_digit_solution(gpu, variant):
             err = fro(b.first_step(0), P["mp_" + p + "delta"])
             print(p, "layout", variant, "first step vs 50-digit solution: %.2e" % err)
             assert err < 1e-7
+            # the same gate within every parameter family: the bias and inverse-depth entries are 1e-5 .. 1e-2 of the step's norm
+            byf = fro_by_family(b.first_step(0), P["mp_" + p + "delta"], tangent_families(NO.Problem(w)))
+            print(p, "layout", variant, "first step vs 50-digit solution per family:", fmt_families(byf))
+            for name, v in byf.items():
+                assert v < 1e-7, (p, variant, name, v)
             assert s.dogleg_case[1] == int(P["mp_" + p + "case"])
     finally:
         gpu.check(gpu.lib().tcv_set_solver_variant(0))
@@ -90,6 +97,13 @@ def test_marginalisation_schur_step_against_50_digits(gpu, monkeypatch):
     z = load("marg_pin.npz")
     pre, main, _ = golden_windows()
     for w, p in ((pre, "pre_"), (main, "main_")):
+        # per family (b', and the diagonal blocks of A' pooled by family) the gate is today's number for the route; where the C oracle
+        # (cyclic Jacobi) is itself further from the pin than that -- the accelerometer-bias block of A' -- 30 x the oracle's distance
+        po, dbg = orc.Window(w).marginalize_old()
+        fam = prior_families(po)
+        pin_A, pin_b = prior_diagonal_blocks(z["mg_" + p + "A"], po), z["mg_" + p + "b"]
+        oa, ob = fro_by_family(prior_diagonal_blocks(dbg["A_schur"], po), pin_A), fro_by_family(dbg["b_schur"], pin_b, fam)
+        print("50-digit pin %sC oracle per family: A' blocks %s | b' %s" % (p, fmt_families(oa), fmt_families(ob)))
         for mode in ("chol", "eig"):
             if mode == "eig":
                 monkeypatch.setenv("TCV_MARG_EIG_MM", "1")
@@ -108,4 +122,12 @@ def test_marginalisation_schur_step_against_50_digits(gpu, monkeypatch):
             # Jacobians at these unsolved states; b' 6.9e-12 / 1.7e-8 (pre), 4.7e-13 / 3.5e-10 (main): the Cholesky route is four orders
             # closer to the exact Schur step than the eigen route, which in turn is three orders closer than LAPACK's eigh (1.6e-5 / 1.4e-6)
             assert ea < 1e-5 and eb < (1e-10 if mode == "chol" else 1e-6)
+            assert d["sizes"] == po["sizes"] and d["idx"] == po["idx"]
+            da, db = fro_by_family(prior_diagonal_blocks(As, po), pin_A), fro_by_family(bs, pin_b, fam)
+            print("50-digit pin %s%s per family: A' blocks %s | b' %s" % (p, mode, fmt_families(da), fmt_families(db)))
+            for dev, orc_, base in ((da, oa, 1e-5), (db, ob, 1e-10 if mode == "chol" else 1e-6)):
+                assert sorted(dev) == sorted(orc_)
+                for name, v in dev.items():
+                    gate = base if orc_[name] <= base else 30.0 * orc_[name]
+                    assert v < gate, (p, mode, name, v, gate, orc_[name])
     monkeypatch.delenv("TCV_MARG_EIG_MM", raising=False)

@@ -21,6 +21,97 @@ def fro(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
+# ---- parity per parameter family: every block of small magnitude (biases, inverse depths, extrinsic translation, td) is measured against
+# its own reference magnitude, not against the largest block of the vector it is stored in
+_STATE_PARTS = {"pose": (("p", 0, 3), ("q", 3, 7)), "sb": (("v", 0, 3), ("ba", 3, 6), ("bg", 6, 9)), "ex": (("p", 0, 3), ("q", 3, 7)),
+                "relo": (("p", 0, 3), ("q", 3, 7))}
+_TANGENT_PARTS = {"pose": (("p", 0, 3), ("th", 3, 6)), "sb": (("v", 0, 3), ("ba", 3, 6), ("bg", 6, 9)), "ex": (("ex_p", 0, 3), ("ex_th", 3, 6)),
+                  "td": (("td", 0, 1),), "relo": (("relo_p", 0, 3), ("relo_th", 3, 6)), "lam": (("lam", 0, 1),)}
+
+
+def state_families(states):
+    """name -> array: pose.p, pose.q, sb.v, sb.ba, sb.bg, ex.p, ex.q, lam, and td, relo.p, relo.q when the states hold them"""
+    out = {}
+    for key in ("pose", "sb", "ex", "relo"):
+        if states.get(key) is None:
+            continue
+        a = np.asarray(states[key], dtype=float)
+        for name, lo, hi in _STATE_PARTS[key]:
+            out[key + "." + name] = a[..., lo:hi]
+    if states.get("lam") is not None:
+        out["lam"] = np.asarray(states["lam"], dtype=float)
+    if states.get("td") is not None:
+        out["td"] = np.atleast_1d(np.asarray(states["td"], dtype=float))
+    return out
+
+
+def _index_families(entries):
+    """entries: (block name, tangent offset) -> name -> sorted index array"""
+    fam = {}
+    for nm, lo in entries:
+        for name, a, b in _TANGENT_PARTS[nm]:
+            fam.setdefault(name, []).extend(range(lo + a, lo + b))
+    return {k: np.array(v, dtype=int) for k, v in fam.items()}
+
+
+def tangent_families(problem):
+    """name -> indices into a tangent vector of an np_oracle.Problem (gradient, first step): p, th, v, ba, bg pooled over the frames,
+    ex_p, ex_th, td, relo_p, relo_th, lam.  The layout is the problem's own (blocks, loff); a constant block has no entries."""
+    return _index_families([(nm, problem.loff[(nm, i)]) for (nm, i, g) in problem.blocks if problem.loff[(nm, i)] >= 0])
+
+
+def prior_families(prior):
+    """the same over the kept blocks of a prior (blocks, idx): indices into b', r0 and the rows and columns of A'"""
+    return _index_families([(nm, int(lo)) for (nm, i), lo in zip(prior["blocks"], prior["idx"])])
+
+
+def prior_diagonal_blocks(A, prior):
+    """name -> the diagonal blocks of A' (n x n) that belong to one family, pooled over the kept blocks and flattened"""
+    A = np.asarray(A, dtype=float)
+    out = {}
+    for (nm, i), lo in zip(prior["blocks"], prior["idx"]):
+        for name, a, b in _TANGENT_PARTS[nm]:
+            out.setdefault(name, []).append(A[lo + a:lo + b, lo + a:lo + b].ravel())
+    return {k: np.concatenate(v) for k, v in out.items()}
+
+
+def _by_family(a, b, fam, dist):
+    if fam is None:
+        assert sorted(a) == sorted(b), (sorted(a), sorted(b))
+        pairs = [(k, a[k], b[k]) for k in b]
+    else:
+        a = np.asarray(a, dtype=float); b = np.asarray(b, dtype=float)
+        assert a.shape == b.shape, (a.shape, b.shape)
+        pairs = [(k, a[ix], b[ix]) for k, ix in fam.items()]
+    out = {}
+    for k, x, y in pairs:
+        x = np.asarray(x, dtype=float); y = np.asarray(y, dtype=float)
+        assert x.shape == y.shape, (k, x.shape, y.shape)
+        if y.size == 0:
+            continue
+        if not np.any(y):          # nothing to be relative to: exact zeros are expected
+            out[k] = 0.0 if not np.any(x) else float("inf")
+            continue
+        out[k] = dist(x, y)
+    return out
+
+
+def rel_by_family(a, b, fam=None):
+    """name -> max |a - b| / max |b| within each family, b the reference.  a, b: vectors with `fam` name -> indices (tangent_families,
+    prior_families), or two dicts name -> array (state_families, prior_diagonal_blocks).  An empty family is left out; where the
+    reference is exactly zero the other side has to be exactly zero (inf otherwise)."""
+    return _by_family(a, b, fam, lambda x, y: float(np.abs(x - y).max() / np.abs(y).max()))
+
+
+def fro_by_family(a, b, fam=None):
+    """the same with |a - b|_2 / |b|_2"""
+    return _by_family(a, b, fam, lambda x, y: float(np.linalg.norm(x - y) / np.linalg.norm(y)))
+
+
+def fmt_families(d):
+    return " ".join("%s %.1e" % (k, v) for k, v in d.items())
+
+
 def load(name):
     return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
 
