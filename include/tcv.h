@@ -80,7 +80,13 @@ typedef struct {
 #define TCV_MAX_TRACE 64
 /* ceres::Solver::Summary subset (estimator.cpp:1899-1902 reads iterations.size()) + parity trace.
  * max_num_iterations is honoured whatever its size (sensor.yaml ships 100); the per-iteration arrays below keep the
- * FIRST TCV_MAX_TRACE entries of the trace, num_iterations keeps counting beyond them. */
+ * FIRST TCV_MAX_TRACE entries of the trace, num_iterations keeps counting beyond them.
+ * An INVALID step (the linear solve failed up to mu = 1, or model_cost_change <= 0) is recorded as dogleg_case = -1, step_norm = 0,
+ * rho = 0, cost_candidate = 0, step_ok = 0, with the radius and the mu it was tried at and the model_cost_change that failed; the
+ * oracles (oracle/) record the dogleg case they selected and its step_norm there instead.  No test compares the two: no finite window
+ * of the suite reaches an invalid step (mu never leaves 1e-8).
+ * The record of a parameter- or function-tolerance stop (termination 2, 3: the last one) holds the candidate's cost_candidate, rho and
+ * step_norm with step_ok = 0 and the cost before it: that candidate is neither accepted nor rejected. */
 typedef struct {
     int num_iterations;   /* = summary.iterations.size(): iteration 0 + accepted + rejected steps (may exceed TCV_MAX_TRACE) */
     int termination;      /* 0 NO_CONVERGENCE 1 gradient 2 parameter 3 function 4 radius 5 FAILURE */

@@ -597,6 +597,9 @@ CERES_DEFAULTS = dict(
     function_tolerance=1e-6, parameter_tolerance=1e-8, gradient_tolerance=1e-10,
     min_trust_region_radius=1e-32, max_num_consecutive_invalid_steps=5,
 )
+# summary["termination"] -> the termination code of the C oracle (orc_summary) and the device (TcvSolverSummary, include/tcv.h)
+TERMINATION_CODE = {"NO_CONVERGENCE": 0, "CONVERGENCE_GRADIENT": 1, "CONVERGENCE_PARAMETER": 2, "CONVERGENCE_FUNCTION": 3,
+                    "CONVERGENCE_RADIUS": 4, "FAILURE": 5}
 
 
 def solve(prob: Problem, max_num_iterations=8, fixed_iterations=False, imu_sqrt=None, trace=None, ceres_defaults=None):
@@ -618,13 +621,19 @@ def solve(prob: Problem, max_num_iterations=8, fixed_iterations=False, imu_sqrt=
         scale = np.ones_like(cn)
     J = J * scale
     grad_unscaled = (J / scale).T @ r
-    summary = dict(initial_cost=cost, iterations=[dict(it=0, cost=cost, step_ok=True)], termination="NO_CONVERGENCE")
+    # every record carries the three quantities the convergence tests read (recordings only: nothing below depends on them): dx_norm and
+    # x_norm as the parameter test of that iteration sees them, gradient_max_norm as the NEXT gradient test sees it (the unscaled
+    # gradient at the state the iteration leaves behind)
+    gmax = float(np.max(np.abs(grad_unscaled)))
+    x_norm = np.linalg.norm(prob.ambient(x))
+    summary = dict(initial_cost=cost, iterations=[dict(it=0, cost=cost, step_ok=True, dx_norm=0.0, x_norm=float(x_norm), gradient_max_norm=gmax)],
+                   termination="NO_CONVERGENCE")
     if not fixed_iterations and np.max(np.abs(grad_unscaled)) <= C["gradient_tolerance"]:
         summary["termination"] = "CONVERGENCE_GRADIENT"; summary["final_cost"] = cost
+        summary["termination_code"] = TERMINATION_CODE[summary["termination"]]
         return x, summary
     radius, mu, reuse, invalid = C["initial_trust_region_radius"], C["min_mu"], False, 0
     min_mu, max_mu, mu_inc = C["min_mu"], C["max_mu"], C["mu_increase_factor"]
-    x_norm = np.linalg.norm(prob.ambient(x))
     it = 0
     diag = grad = gn = None
     alpha = 0.0
@@ -632,7 +641,7 @@ def solve(prob: Problem, max_num_iterations=8, fixed_iterations=False, imu_sqrt=
         if it >= max_num_iterations:
             break
         it += 1
-        rec = dict(it=it)
+        rec = dict(it=it, dx_norm=0.0, x_norm=float(x_norm), gradient_max_norm=gmax)
         # ---- DoglegStrategy::ComputeStep
         step_valid_ls = True
         if not reuse:
@@ -693,6 +702,7 @@ def solve(prob: Problem, max_num_iterations=8, fixed_iterations=False, imu_sqrt=
         rec.update(model_cost_change=model_cost_change, cost_candidate=cost_c, radius=radius,
                    step_norm_dogleg=step_norm, delta=delta.copy())
         dxn = np.linalg.norm(prob.ambient(x) - prob.ambient(x_c))
+        rec["dx_norm"] = float(dxn)
         if not fixed_iterations and dxn <= C["parameter_tolerance"] * (x_norm + C["parameter_tolerance"]):
             rec["cost"] = cost; summary["iterations"].append(rec)
             summary["termination"] = "CONVERGENCE_PARAMETER"
@@ -711,6 +721,7 @@ def solve(prob: Problem, max_num_iterations=8, fixed_iterations=False, imu_sqrt=
             grad_unscaled = J.T @ r
             J = J * scale
             rec["step_ok"] = True
+            gmax = float(np.max(np.abs(grad_unscaled))); rec["gradient_max_norm"] = gmax
             if rho < C["decrease_threshold"]:
                 radius *= 0.5
             if rho > C["increase_threshold"]:
@@ -734,6 +745,7 @@ def solve(prob: Problem, max_num_iterations=8, fixed_iterations=False, imu_sqrt=
             break
     summary["final_cost"] = cost
     summary["scale"] = scale
+    summary["termination_code"] = TERMINATION_CODE[summary["termination"]]
     return x, summary
 
 

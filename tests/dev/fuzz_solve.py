@@ -17,7 +17,15 @@ own movement where that exceeds 1e-6 (`ok~`: listed with the measured sensitivit
 whole AND within every parameter family (positions, rotations, velocities, accelerometer and gyro biases, extrinsic translation and
 rotation, inverse depths), each family relative to the oracle's own magnitude in it and priced by the oracle's own movement in it.
 
-    python tests/dev/fuzz_solve.py [cases] [first seed]
+A `trace` verdict is not free: it is excused only when the ORACLE'S OWN trace (iterations, termination, dogleg cases, accepts) changes in at
+least one of twelve draws of that 1e-13 noise (`oracle_trace_moves`, drawn lazily) -- otherwise it counts as a mismatch --, and at most
+TRACE_CAP = 5 % of the cases of any setting may be `trace` at all (a cap, not a measurement: the oracle's own trace moved in 1 of 120 windows
+under three draws, the device's recorded share is at most 2 %, profiles/r05_fuzz_solve.txt, r06_fuzz_solve.txt).
+
+With `convergence` as the third argument every solve -- device and oracle -- runs (50, to convergence) with the Ceres tolerances instead of
+(8, fixed); the sensitivity solves are then run lazily, only for a case that exceeds a gate.
+
+    python tests/dev/fuzz_solve.py [cases] [first seed] [convergence]
 """
 import os
 import sys
@@ -35,6 +43,8 @@ import tcv      # noqa: E402
 from util import fro, fro_by_family, golden_windows, rel, rel_by_family, state_families, sub_window, tangent_families      # noqa: E402
 
 TOL = 1e-6
+TRACE_CAP = 0.05            # the share of `trace` verdicts any setting may have
+TRACE_DRAWS = 12            # draws of 1e-13 noise in which the oracle's own trace has to move for a `trace` verdict to be excused
 
 
 def take(d, keep, n):
@@ -135,7 +145,47 @@ def make_case(rng, seed):
     return w_hip, w_orc, exc, " ".join(notes)
 
 
-def oracle_sensitivity(w_orc, exc, so0, st0):
+def perturbed(w_orc, rep):
+    """the window with its states moved by 1e-13 relative, draw `rep`"""
+    r2 = np.random.Generator(np.random.PCG64(977 + rep))
+    w2 = dict(w_orc)
+    for key in ("lam", "pose", "speedbias"):
+        a = np.asarray(w_orc[key], dtype=float)
+        w2[key] = a * (1 + 1e-13 * r2.standard_normal(a.shape))
+    return w2
+
+
+def trace_of(s):
+    n = min(s.num_iterations, len(s.step_ok))
+    return (s.num_iterations, s.termination, [s.dogleg_case[i] for i in range(1, n)], [s.step_ok[i] for i in range(1, n)])
+
+
+def oracle_trace_moves(w_orc, exc, so0, iters=8, fixed=True, draws=TRACE_DRAWS):
+    """does the oracle's own trace change under 1e-13 state noise?  Stops at the first draw in which it does."""
+    t0 = trace_of(so0)
+    for rep in range(draws):
+        if trace_of(orc.Window(perturbed(w_orc, rep), ex_constant=exc).solve(iters, fixed)) != t0:
+            return True
+    return False
+
+
+class LazySensitivity:
+    """oracle_sensitivity when first asked for (convergence mode: three more oracle solves to convergence per case, needed only where a
+    gate is exceeded); `tangent`, which every comparison reads, does not need them"""
+
+    def __init__(self, w_orc, exc, so0, st0, iters, fixed):
+        self.args, self.d = (w_orc, exc, so0, st0, iters, fixed), None
+        self.tangent = tangent_families(NO.Problem(w_orc, ex_constant=exc))
+
+    def __getitem__(self, key):
+        if key == "tangent":
+            return self.tangent
+        if self.d is None:
+            self.d = oracle_sensitivity(*self.args)
+        return self.d[key]
+
+
+def oracle_sensitivity(w_orc, exc, so0, st0, iters=8, fixed=True):
     """how far the oracle's own first step / final cost / states move when the window's states move by 1e-13 relative; `first_family` and
     `state_family`: the same within every parameter family (util.tangent_families / util.state_families); `tangent`: the index sets"""
     f0 = np.array(so0.first_delta[:so0.n_local])
@@ -146,12 +196,7 @@ def oracle_sensitivity(w_orc, exc, so0, st0):
         for name, v in d.items():
             into[name] = max(into.get(name, 0.0), v)
     for rep in range(3):
-        r2 = np.random.Generator(np.random.PCG64(977 + rep))
-        w2 = dict(w_orc)
-        for key in ("lam", "pose", "speedbias"):
-            a = np.asarray(w_orc[key], dtype=float)
-            w2[key] = a * (1 + 1e-13 * r2.standard_normal(a.shape))
-        O = orc.Window(w2, ex_constant=exc); so = O.solve(8, True)
+        O = orc.Window(perturbed(w_orc, rep), ex_constant=exc); so = O.solve(iters, fixed)
         f1 = np.array(so.first_delta[:so.n_local])
         if len(f0):
             sens["first"] = max(sens["first"], fro(f1, f0))
@@ -176,16 +221,16 @@ def compare(W, b, s, k, O, so, sens):
             return "FIRST STEP", f"first step differs {d1:.2e} (oracle moves {sens['first']:.1e})"
         soft.append(f"first step {d1:.1e} / oracle {sens['first']:.1e}")
     for name, d in (fro_by_family(fg, fo, sens["tangent"]) if len(fo) else {}).items():
-        m = sens["first_family"].get(name, 0.0)
         if not d < TOL:
+            m = sens["first_family"].get(name, 0.0)
             if not d < 30 * m:
                 return "FIRST STEP", f"first step differs in {name} {d:.2e} (oracle moves {m:.1e})"
             soft.append(f"first step {name} {d:.1e} / oracle {m:.1e}")
-    n = so.num_iterations
-    same = s.num_iterations == n and s.termination == so.termination and \
+    n = min(so.num_iterations, len(s.step_ok))
+    same = s.num_iterations == so.num_iterations and s.termination == so.termination and \
         [s.dogleg_case[i] for i in range(1, n)] == [so.dogleg_case[i] for i in range(1, n)] and [s.step_ok[i] for i in range(1, n)] == [so.step_ok[i] for i in range(1, n)]
     if not same:
-        return "trace", f"iterations {s.num_iterations} vs {n}"
+        return "trace", f"iterations {s.num_iterations} vs {so.num_iterations}"
     dc = abs(s.final_cost - so.final_cost) / max(so.final_cost, 1e-12)      # (a zero-residual window: absolute below 1e-12)
     if not dc <= TOL:
         if not dc < 30 * sens["cost"]:
@@ -199,15 +244,15 @@ def compare(W, b, s, k, O, so, sens):
                 return "STATE", f"{key} differs {r:.2e} (oracle moves {sens[key]:.1e})"
             soft.append(f"{key} {r:.1e} / oracle {sens[key]:.1e}")
     for name, r in rel_by_family(state_families(sg), state_families(st)).items():
-        m = sens["state_family"].get(name, 0.0)
         if not r < TOL:
+            m = sens["state_family"].get(name, 0.0)
             if not r < 30 * m:
                 return "STATE", f"{name} differs {r:.2e} (oracle moves {m:.1e})"
             soft.append(f"{name} {r:.1e} / oracle {m:.1e}")
     return ("ok~", "; ".join(soft)) if soft else ("ok", "")
 
 
-def gpu_run(w, exc, copies, coop_off=False, dense=False, mfma=True):
+def gpu_run(w, exc, copies, coop_off=False, dense=False, mfma=True, iters=8, fixed=True, threads=256, workgroups_per_window=0):
     L = tcv.lib()
     old = os.environ.get("TCV_COOP_H")
     if coop_off:
@@ -217,7 +262,7 @@ def gpu_run(w, exc, copies, coop_off=False, dense=False, mfma=True):
     try:
         Ws = [tcv.Window(w, estimate_extrinsic=not exc) for _ in range(copies)]
         b = tcv.Batch(Ws)
-        b.solve(tcv.default_options(8, True, mfma, 256, True))
+        b.solve(tcv.default_options(iters, fixed, mfma, threads, True, workgroups_per_window))
         b.synchronize(); b.download_states()
         return Ws, b, b.summaries()
     finally:
@@ -233,34 +278,47 @@ def gpu_run(w, exc, copies, coop_off=False, dense=False, mfma=True):
 def main():
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
     seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    convergence = len(sys.argv) > 3 and sys.argv[3] == "convergence"
+    iters, fixed = (50, False) if convergence else (8, True)
     tally = {}
     bad = []
     kept = []
+    moves = {}
+
+    def judge(seed, note, name, verdict, detail, w_orc, exc, so):
+        """counts a verdict; a `trace` the oracle's own trace does not excuse is a mismatch"""
+        if verdict == "trace":
+            if seed not in moves:
+                moves[seed] = oracle_trace_moves(w_orc, exc, so, iters, fixed)
+            if not moves[seed]:
+                verdict, detail = "TRACE", detail + f": the oracle's own trace holds in {TRACE_DRAWS} draws of 1e-13 noise"
+        tally[(name, verdict)] = tally.get((name, verdict), 0) + 1
+        if verdict in ("FIRST STEP", "STATE", "ERROR", "TRACE"):
+            bad.append((seed, note, name, verdict, detail))
+        return verdict, detail
     for c in range(cases):
         seed = seed0 + c
         rng = np.random.Generator(np.random.PCG64(seed))
         w_hip, w_orc, exc, note = make_case(rng, seed)
         try:
             O = orc.Window(w_orc, ex_constant=exc)
-            so = O.solve(8, True)
-            sens = oracle_sensitivity(w_orc, exc, so, O.states())
+            so = O.solve(iters, fixed)
+            sens = LazySensitivity(w_orc, exc, so, O.states(), iters, fixed) if convergence else oracle_sensitivity(w_orc, exc, so, O.states())
         except Exception as e:      # noqa: BLE001
             print(f"case {seed} [{note}]: oracle refused: {e}")
             continue
-        kept.append((seed, note, w_hip, exc, O, so, sens))
+        kept.append((seed, note, w_hip, exc, O, so, sens, w_orc))
         row = []
         for name, kw in (("lone", dict(copies=1)), ("single", dict(copies=1, coop_off=True)), ("packed", dict(copies=257)), ("dense", dict(copies=1, dense=True))):
             try:
-                Ws, b, s = gpu_run(w_hip, exc, **kw)
+                Ws, b, s = gpu_run(w_hip, exc, iters=iters, fixed=fixed, **kw)
                 k = len(Ws) - 1
                 verdict, detail = compare(Ws[k], b, s[k], k, O, so, sens)
                 lay = b.plan_stats()["layout"]
             except Exception as e:      # noqa: BLE001
                 verdict, detail, lay = "ERROR", str(e)[:120], "?"
-            tally[(name, verdict)] = tally.get((name, verdict), 0) + 1
+            verdict, detail = judge(seed, note, name, verdict, detail, w_orc, exc, so)
             row.append(f"{name}:{verdict}" + (f"({detail})" if detail else "") + f"[{lay}]")
-            if verdict in ("FIRST STEP", "STATE", "ERROR"):
-                bad.append((seed, note, name, verdict, detail))
         np_, nl_, nlm = len(w_hip["proj"]["landmark"]), len(w_hip["line"]["frame"]), len(w_hip["lam"])
         print(f"case {seed} [{note}; {np_} point, {nl_} line factors, {nlm} landmarks, prior {'yes' if w_hip.get('prior') is not None else 'no'}]: " + "  ".join(row), flush=True)
     # the same windows six at a time in ONE batch (a lock-step frame: different structures side by side, the helpers sized by the largest
@@ -268,20 +326,24 @@ def main():
     for g0 in range(0, len(kept), 6):
         grp = kept[g0:g0 + 6]
         try:
-            Ws = [tcv.Window(w, estimate_extrinsic=not exc) for (_, _, w, exc, _, _, _) in grp]
+            Ws = [tcv.Window(w, estimate_extrinsic=not exc) for (_, _, w, exc, _, _, _, _) in grp]
             b = tcv.Batch(Ws)
-            b.solve(tcv.default_options(8, True, True, 256, True)); b.synchronize(); b.download_states()
+            b.solve(tcv.default_options(iters, fixed, True, 256, True)); b.synchronize(); b.download_states()
             ss = b.summaries()
-            for k, (seed, note, w, exc, O, so, sens) in enumerate(grp):
+            for k, (seed, note, w, exc, O, so, sens, w_orc) in enumerate(grp):
                 verdict, detail = compare(Ws[k], b, ss[k], k, O, so, sens)
-                tally[("mixed", verdict)] = tally.get(("mixed", verdict), 0) + 1
-                if verdict in ("FIRST STEP", "STATE", "ERROR"):
-                    bad.append((seed, note, "mixed", verdict, detail))
+                judge(seed, note, "mixed", verdict, detail, w_orc, exc, so)
             print(f"mixed batch of seeds {[g[0] for g in grp]}: layout {b.plan_stats()['layout']}, plans {b.plan_stats()['num_plans']}, cooperative {b.cooperative()}", flush=True)
         except Exception as e:      # noqa: BLE001
             tally[("mixed", "ERROR")] = tally.get(("mixed", "ERROR"), 0) + 1
             bad.append((grp[0][0], "batch", "mixed", "ERROR", str(e)[:160]))
-    print("\ntally:", {f"{a}/{b}": n for (a, b), n in sorted(tally.items())})
+    for name in sorted(set(a for (a, _) in tally)):      # the cap on `trace` verdicts, excused or not, per setting
+        total = sum(n for (a, _), n in tally.items() if a == name)
+        traces = tally.get((name, "trace"), 0) + tally.get((name, "TRACE"), 0)
+        if traces > TRACE_CAP * total:
+            bad.append((seed0, "all cases", name, "TRACE CAP", f"{traces} of {total} cases took another trace than the oracle (cap {TRACE_CAP:.0%})"))
+    print("\nmode:", f"({iters}, {'fixed' if fixed else 'to convergence'})")
+    print("tally:", {f"{a}/{b}": n for (a, b), n in sorted(tally.items())})
     print("mismatches:", len(bad))
     for x in bad:
         print("  ", x)

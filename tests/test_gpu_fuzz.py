@@ -31,6 +31,14 @@ def test_window_structures_solved_four_ways_and_in_mixed_batches(gpu):
     assert run("fuzz_solve", 120, 10) == 0
 
 
+def test_window_structures_solved_to_convergence(gpu):
+    """the same structures with the convergence tests on, (50, to convergence) on the device and in the oracle: the function and parameter
+    tolerances and the iteration limit decide where a solve ends (the oracle alone over seeds 10 .. 129: 90 / 1 / 29).  In both modes a
+    `trace` verdict counts as a mismatch unless the oracle's own trace moves under 1e-13 noise, and at most 5 % of a setting's cases may
+    be `trace` (tests/dev/fuzz_solve.py)."""
+    assert run("fuzz_solve", 24, 10, "convergence") == 0
+
+
 def test_marginalisation_of_the_fuzz_structures(gpu):
     assert run("fuzz_marg", 150, 0) == 0
 
