@@ -90,7 +90,7 @@ int tcv_estimators_begin_frames(tcv_estimator *const *e, int n, const tcv_frame_
  * are applied; the marginalisation (whose result, the next prior, never leaves the device) is launched behind them and runs while the
  * caller finishes this frame and starts the next.  Its status is read at the estimator's NEXT tcv_estimators_optimize: a window that was
  * solved on the prior of a failed marginalisation is not applied and reports TCV_ERR_NUMERIC from tcv_estimator_finish_frame -- one frame
- * later than a failure of the solve itself.  (TCV_EST_MARG_WAIT=1 in the environment: wait for it inside the call, as until round 4.)
+ * later than a failure of the solve itself.
  * Thread safety: estimators are independent objects; different host threads may drive different estimator lists, on the same or on
  * different devices (every call issues its copies and kernels on the calling thread's own stream: the threads overlap on the device). */
 int tcv_estimators_optimize(tcv_estimator *const *e, int n);

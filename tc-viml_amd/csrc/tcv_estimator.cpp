@@ -22,11 +22,12 @@
 #include <vector>
 
 #include "../../include/tcv_estimator.h"
-namespace tcv { hipStream_t util_stream(); hipStream_t aux_stream(); }      // (tcv_capi.hip: the calling thread's utility stream and its second stream)
-#include <functional>
 #include "tcv_hostpool.h"      // parallel_items, async_run, HostOp: the persistent host worker threads
 
-namespace tcv { void set_error(const std::string &s); }
+namespace tcv {
+hipStream_t util_stream(); hipStream_t aux_stream();      // (tcv_capi.hip: the calling thread's utility stream and its second stream)
+void set_error(const std::string &s);
+}
 int tcv_marg_layout_n(const tcv_batch *b, int window);      // (tcv_marg.hip: n of the prior a window's attached marginalisation problem makes, known before the kernel runs)
 
 namespace {
@@ -125,9 +126,6 @@ struct ImuBuf {
 
 }  // namespace
 
-// A lock-step frame whose marginalisation was left running when tcv_estimators_optimize returned (device-resident state): its batch,
-// shared by the estimators of the frame; each asks for the status of its own window at its next frame (or lets go of it when
-// it is reset / destroyed), the last one to let go destroys the batch.
 // kernel-time accounting of the lock-step frames (tcv_estimators_kernel_profile): HIP-event durations of the solve and marginalisation
 // launches, the windows they held and those windows' ALGORITHMIC bytes x linearisations -- what bench.py --mode replay
 // prices against the HBM roofline
@@ -135,14 +133,17 @@ std::mutex g_kmu;
 double g_kern[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // solve ms, solve launches, marginalisation ms, marginalisation launches, windows, bytes x linearisations, linearisations, marginalised windows
 void kern_add(int slot, double v) { std::lock_guard<std::mutex> g(g_kmu); g_kern[slot] += v; }
 
+// A lock-step frame whose marginalisation was left running when tcv_estimators_optimize returned (device-resident state): its batch,
+// shared by the estimators of the frame; each asks for the status of its own window at its next frame (or lets go of it when
+// it is reset / destroyed), the last one to let go destroys the batch.
 struct EstInflight {
     tcv_batch *b = nullptr;
     int n_marg = 0;
-    // deferred launch (the default): the frame that solved the batch returns WITHOUT launching its marginalisation; the first of its
-    // estimators to come back for its next frame launches it -- behind that frame's 2D-3D association, whose device round trip would
+    // deferred launch (frames of many windows): the frame that solved the batch returns WITHOUT launching its marginalisation; the first of
+    // its estimators to come back for its next frame launches it -- behind that frame's 2D-3D association, whose device round trip would
     // otherwise queue behind the marginalisation kernel on the thread's stream (0.3 - 0.5 ms of a lock-step frame, whatever the number
     // of windows) -- and every estimator takes its own prior handle.  The kernel then runs while the host builds that frame's windows.
-    bool deferred = false, launched = false;
+    bool launched = false;
     int launch_rc = TCV_OK;
     std::string launch_msg;
     std::vector<tcv_prior *> handles;      // per window of the batch: the new prior, until its estimator takes it
@@ -204,7 +205,7 @@ struct tcv_estimator {
     WindowTap tap;
     std::shared_ptr<EstInflight> prev;       // the frame whose marginalisation produced `prior` and may still be running; prev_k: this estimator's window in it
     int prev_k = -1;
-    std::shared_ptr<EstInflight> pend;       // the frame whose marginalisation has not been launched yet (EstInflight::deferred): its prior is taken at the start of the next tcv_estimators_optimize
+    std::shared_ptr<EstInflight> pend;       // the frame whose marginalisation has not been launched yet (EstInflight::launch): its prior is taken at the start of the next tcv_estimators_optimize
     int pend_k = -1, pend_flag = MARGIN_OLD;
     V3 Ps[W + 1], Vs[W + 1], Bas[W + 1], Bgs[W + 1];
     M3 Rs[W + 1];
@@ -787,36 +788,47 @@ double g_prof_cpu[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 bool prof_cpu_on() { static const bool on = getenv("TCV_DEBUG_EST_CPU") != nullptr; return on; }
 double cpu_now_s() { timespec ts; clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 void prof_cpu_add(int slot, double v) { std::lock_guard<std::mutex> g(g_mu); g_prof_cpu[slot] += v; }
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// the time marks of a frame: add(slot) books what has passed since the last mark on a profile slot, wall and (TCV_DEBUG_EST_CPU) process CPU
+struct Lap {
+    double t = now_s(), c = prof_cpu_on() ? cpu_now_s() : 0.0;
+    void add(int slot) {
+        const double t1 = now_s(); prof_add(slot, t1 - t); t = t1;
+        if (prof_cpu_on()) { const double c1 = cpu_now_s(); prof_cpu_add(slot, c1 - c); c = c1; }
+    }
+    void mark_cpu() { if (prof_cpu_on()) c = cpu_now_s(); }      // (what the process burns between _begin and _end is not the frame's)
+};
 // per-estimator host work of a lock-step frame (association bookkeeping, triangulation, window and problem construction) on the packer's
 // persistent worker threads: the estimators are independent objects, every task touches its own
 void for_each_estimator(int n, const std::function<void(int)> &fn) {
-    // TCV_EST_SERIAL_MAX = m (experiment, default 0): up to m estimators per call the tasks run on the caller.  A task is 10 - 20 us and a fork / join
-    // ~50 us, so at four windows per call the association sections are faster alone (0.18 against 0.22 ms) -- but the problems then all come
-    // out of the CALLER's malloc arena while the worker threads free last frame's behind its back, and their construction goes from 0.06 to
-    // 0.13 ms (0.07 -> 0.3 ms at eight per call): 8 streams the same, 16 streams 6.4 K -> 5.6 K windows/s (profiles/r05_replay_host_workers.txt)
-    static const int serial_max = [] { const char *e = getenv("TCV_EST_SERIAL_MAX"); return e ? atoi(e) : 0; }();
-    if (n <= serial_max) { for (int i = 0; i < n; i++) fn(i); return; }
     tcv::HostOp op;
     const int nth = op.threads(n);
     if (nth <= 1) { for (int i = 0; i < n; i++) fn(i); return; }
     tcv::parallel_items(n, nth, [&](int i, int) { fn(i); });
 }
+// the same for tasks that can fail: every task's code and, where it failed, the error text of the thread it ran on (the text is per thread)
+struct TaskRc { int rc = TCV_OK; std::string msg; };
+std::vector<TaskRc> for_each_estimator_rc(int n, const std::function<int(int)> &fn, bool on_caller = false) {
+    std::vector<TaskRc> r(n);
+    auto one = [&](int i) { r[i].rc = fn(i); if (r[i].rc != TCV_OK) r[i].msg = tcv_last_error(); };
+    if (on_caller) for (int i = 0; i < n; i++) one(i); else for_each_estimator(n, one);
+    return r;
+}
+// the first failure in index order, its text on the calling thread; rcs_out (one int per task), when given, takes every code
+int first_failure(const std::vector<TaskRc> &r, int *rcs_out = nullptr) {
+    if (rcs_out) for (size_t i = 0; i < r.size(); i++) rcs_out[i] = r[i].rc;
+    for (const TaskRc &t : r) if (t.rc != TCV_OK) { tcv::set_error(t.msg); return t.rc; }
+    return TCV_OK;
+}
 }  // namespace
-static inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 extern "C" int tcv_estimators_begin_frames(tcv_estimator *const *es, int n, const tcv_frame_input *in, int *ready, int *rc_out) {
     if (!es || n <= 0 || !in || !ready) { tcv::set_error("estimators_begin_frames: bad argument"); return TCV_ERR_INVALID; }
     for (int i = 0; i < n; i++) for (int j = 0; j < i; j++) if (es[i] == es[j]) { tcv::set_error("estimators_begin_frames: the same estimator twice"); return TCV_ERR_INVALID; }
-    std::vector<int> rcs(n, TCV_OK);
-    std::vector<std::string> msgs(n);
-    for_each_estimator(n, [&](int i) {
+    return first_failure(for_each_estimator_rc(n, [&](int i) {
         const tcv_frame_input &f = in[i];
         ready[i] = 0;
-        rcs[i] = tcv_estimator_begin_frame(es[i], f.n_imu, f.acc, f.gyr, f.n_points, f.point_ids, f.points, f.n_lines, f.line_ids, f.lines, f.truth, &ready[i]);
-        if (rcs[i] != TCV_OK) msgs[i] = tcv_last_error();      // (the text is per thread)
-    });
-    if (rc_out) for (int i = 0; i < n; i++) rc_out[i] = rcs[i];
-    for (int i = 0; i < n; i++) if (rcs[i] != TCV_OK) { tcv::set_error(msgs[i]); return rcs[i]; }
-    return TCV_OK;
+        return tcv_estimator_begin_frame(es[i], f.n_imu, f.acc, f.gyr, f.n_points, f.point_ids, f.points, f.n_lines, f.line_ids, f.lines, f.truth, &ready[i]);
+    }), rc_out);
 }
 extern "C" int tcv_estimators_kernel_profile(double *out8) {
     if (!out8) return TCV_ERR_INVALID;
@@ -835,77 +847,86 @@ extern "C" int tcv_estimators_profile(double *out8) {
     return TCV_OK;
 }
 
-struct OptGroup {
-    std::vector<int> idx;
-    std::vector<char> dm;             // per window of the group: it marginalises
+// ---- a lock-step frame in two halves (tcv_estimators_optimize_begin / _end): everything up to the last command on the device, and the wait
+// for the states with what follows.  The ticket is the frame's record: what the first half leaves for the second.
+//
+// One device batch per frame: the windows that marginalise (MARGIN_OLD, or MARGIN_SECOND_NEW with para_Pose[WINDOW_SIZE - 1] in the prior,
+// estimator.cpp:2049-2050) carry a marginalisation problem, the others a NULL entry (tcv_batch_create).
+// Every kernel of the frame goes on the CALLING THREAD's utility stream -- the stream tcv_batch_create's uploads, the device-to-device
+// splices and the downloads of this thread use anyway: host threads that drive their own estimators overlap on the device (a stream pair
+// shared by the threads of a device, as until round 4, serialises their kernels: 8 streams on 4 host threads 1 000 against 2 400 windows/s),
+// and with one stream per thread no small copy of one thread waits behind another thread's 2 ms solve kernel on a shared hardware queue.
+//
+// The new prior of a window reaches its estimator in one of two ways (host_priors):
+//  - on the device (the default).  last_marginalization_info stays there (estimator.h:176-177: the reference keeps it alive between frames,
+//    too): the new priors are handles on the batch's result buffer, the next frame's tcv_batch_create splices them device-to-device.  The
+//    host then needs nothing of the marginalisation but its status: the frame is over once the solve and the gauge fix are done and the
+//    states are applied; the marginalisation is launched behind them and runs while the caller finishes the frame and starts the next one
+//    (tcv_batch_get_priors_device_async).  Its status is read at each estimator's NEXT frame, after that frame's solve: a window solved
+//    on a prior whose marginalisation failed is not applied and reports the failure (finish_frame), one frame late.  Faster at every batch
+//    size once every host thread launches on its own stream (512-window passes: 171 K against 117 K windows/s; eight replay streams on two
+//    host threads: 2 370 - 2 480 against 2 250 - 2 280 windows/s).
+//  - TCV_EST_HOST_PRIORS=1: round 3's host round trip (62 KB down, 46 KB up per window), the reference of tests/test_gpu_resident.py --
+//    same bits.  The batch is created with its marginalisation problems, the call waits for solve and marginalisation and copies every
+//    window's prior to the host.
+struct tcv_opt_ticket {
+    std::vector<tcv_estimator *> es;
+    std::vector<char> dm;             // per window: it marginalises
     bool any_marg = false;
     std::vector<tcv_problem *> P, M;
     std::vector<double *const *> drops;
     std::vector<int> ndrop;
     std::vector<tcv_solver_summary> sum;
     std::vector<tcv_prior *> newp;
-    std::vector<int> est_rc;          // per estimator: TCV_ERR_NUMERIC when its own marginalisation failed
+    std::vector<int> est_rc;          // per estimator: TCV_ERR_NUMERIC when its own window failed
     std::string est_msg;
     tcv_batch *b = nullptr;
-    int rc = TCV_OK;
-    bool deferred = false;            // the marginalisation of this frame is launched by its estimators' next frame (EstInflight)
-    bool dl_begun = false, marg_launched = false;      // the copy of the states / the marginalisation were enqueued behind the solve (marg_off_path)
+    int rc = TCV_OK;                  // the first failure of the batch as a whole: carried to _end, which applies nothing then
+    hipStream_t stream = nullptr;
+    bool host_priors = false;         // the two hand-over modes above
+    bool defer = false;               // the marginalisation of this frame is launched by its estimators' next frame (EstInflight)
+    bool dl_begun = false;            // the copy of the states was enqueued behind the solve: _end waits for it
+    Lap lap;
+    int n() const { return (int)es.size(); }
+    ~tcv_opt_ticket() {
+        if (b) tcv_batch_destroy(b);
+        for (auto *p : P) if (p) tcv_problem_destroy(p);
+        for (auto *p : M) if (p) tcv_problem_destroy(p);
+        for (auto *p : newp) if (p) tcv_prior_destroy(p);
+    }
 };
 
-struct OptRun {
-    std::vector<tcv_estimator *> esv;
-    int n = 0;
-    OptGroup G[2];
-    hipStream_t g_streams[2] = {nullptr, nullptr};
-    bool host_priors = false, marg_off_path = false, marg_aux = false;
-    int defer_from = 12, rc_all = TCV_OK;
-    double t_mark = 0.0, t_begin0 = 0.0, t_end0 = 0.0;
-    ~OptRun() { for (auto &g : G) { if (g.b) tcv_batch_destroy(g.b); for (auto *p : g.P) if (p) tcv_problem_destroy(p); for (auto *p : g.M) if (p) tcv_problem_destroy(p); for (auto *p : g.newp) if (p) tcv_prior_destroy(p); } }
-};
-// ---- a lock-step frame in two halves (tcv_estimators_optimize_begin / _end): everything up to the last command on the device, and the wait for the
-// states with what follows.  OptRun carries what the second half needs.
-static int optimize_begin(OptRun &R) {
-    tcv_estimator *const *es = R.esv.data();
-    const int n = R.n;
-    typedef OptGroup Group;
-    double &t_mark = R.t_mark;
-    t_mark = now_s();
-    R.t_begin0 = t_mark;
-    double c_mark = prof_cpu_on() ? cpu_now_s() : 0.0;
-    auto lap = [&](int slot) { const double t = now_s(); prof_add(slot, t - t_mark); t_mark = t; if (prof_cpu_on()) { const double c = cpu_now_s(); prof_cpu_add(slot, c - c_mark); c_mark = c; } };
-    prof_add(7, 1);
-    for (int i = 0; i < n; i++) if (!es[i] || es[i]->phase != 1) { tcv::set_error("estimators_optimize: an estimator has no full window waiting (begin_frame must report ready)"); return TCV_ERR_INVALID; }
-    for (int i = 0; i < n; i++) for (int j = 0; j < i; j++) if (es[i] == es[j]) { tcv::set_error("estimators_optimize: the same estimator twice"); return TCV_ERR_INVALID; }
-    // solveOdometry up to the solver call: association, triangulation, vector2double + graph.  The association's device round trip comes
-    // first and the pre-integration of the new IMU buffers is issued behind it (nobody on the host waits for that kernel: its results are
-    // spliced into the batch on the device), so the kernel runs while the host builds the windows and problems.
-    std::vector<AssocJob> jobs(n);
-    {
-        static const bool dbg1 = getenv("TCV_DEBUG_EST") != nullptr;      // developer: where this lap goes
-        const double ta0 = now_s();
-        std::vector<tcv_match_lines_args> calls;
-        {      // (per estimator: poses, the detections of its line tracks, its field-of-view sets -- independent objects, the worker threads share them)
-            std::vector<int> rcs(n, TCV_OK);
-            std::vector<std::string> msgs(n);
-            bool warm = true;
-            for (int i = 0; i < n; i++) if (es[i]->assoc && !es[i]->fov_ready) warm = false;      // (the first frame's own device call per estimator stays on this thread)
-            auto one = [&](int i) { if (es[i]->assoc) { rcs[i] = assoc_prepare(es[i], jobs[i]); if (rcs[i] != TCV_OK) msgs[i] = tcv_last_error(); } };
-            if (warm) for_each_estimator(n, one); else for (int i = 0; i < n; i++) one(i);
-            for (int i = 0; i < n; i++) if (rcs[i] != TCV_OK) { tcv::set_error(msgs[i]); return rcs[i]; }
-            for (int i = 0; i < n; i++) if (es[i]->assoc && jobs[i].call) calls.push_back(jobs[i].args);
-        }
-        const double ta1 = now_s();
-        if (!calls.empty()) { const int rc = tcv_match_lines_batch((int)calls.size(), calls.data()); if (rc != TCV_OK) return rc; }
-        if (dbg1) fprintf(stderr, "[est] n %d: association prepare %.3f ms, device round trip (%d calls) %.3f ms\n", n, 1e3 * (ta1 - ta0), (int)calls.size(), 1e3 * (now_s() - ta1));
-    }
-    lap(1);
-    // the previous frame's marginalisations (deferred: see EstInflight) go on the device NOW, behind the association's round trip, and every
-    // estimator takes the prior it will build this frame's window on (getParameterBlocks, marginalization_factor.cpp:301-321)
-    for (int i = 0; i < n; i++) {
-        tcv_estimator *e = es[i];
+namespace {
+int check_ready(const tcv_opt_ticket &T) {
+    const int n = T.n();
+    for (int i = 0; i < n; i++) if (!T.es[i] || T.es[i]->phase != 1) { tcv::set_error("estimators_optimize: an estimator has no full window waiting (begin_frame must report ready)"); return TCV_ERR_INVALID; }
+    for (int i = 0; i < n; i++) for (int j = 0; j < i; j++) if (T.es[i] == T.es[j]) { tcv::set_error("estimators_optimize: the same estimator twice"); return TCV_ERR_INVALID; }
+    return TCV_OK;
+}
+// 2D-3D association, first half: per estimator its poses, the detections of its line tracks and its field-of-view sets (independent objects,
+// the worker threads share them), then ONE device round trip for all of them
+int associate(const tcv_opt_ticket &T, std::vector<AssocJob> &jobs) {
+    static const bool dbg = getenv("TCV_DEBUG_EST") != nullptr;      // developer: where this lap goes
+    const int n = T.n();
+    const double ta0 = now_s();
+    bool warm = true;
+    for (tcv_estimator *e : T.es) if (e->assoc && !e->fov_ready) warm = false;      // (the first frame's own device call per estimator stays on this thread)
+    const int rcp = first_failure(for_each_estimator_rc(n, [&](int i) { return T.es[i]->assoc ? assoc_prepare(T.es[i], jobs[i]) : TCV_OK; }, !warm));
+    if (rcp != TCV_OK) return rcp;
+    std::vector<tcv_match_lines_args> calls;
+    for (int i = 0; i < n; i++) if (T.es[i]->assoc && jobs[i].call) calls.push_back(jobs[i].args);
+    const double ta1 = now_s();
+    if (!calls.empty()) { const int rc = tcv_match_lines_batch((int)calls.size(), calls.data()); if (rc != TCV_OK) return rc; }
+    if (dbg) fprintf(stderr, "[est] n %d: association prepare %.3f ms, device round trip (%d calls) %.3f ms\n", n, 1e3 * (ta1 - ta0), (int)calls.size(), 1e3 * (now_s() - ta1));
+    return TCV_OK;
+}
+// the previous frame's marginalisations (deferred: see EstInflight) go on the device NOW, behind the association's round trip, and every
+// estimator takes the prior it will build this frame's window on (getParameterBlocks, marginalization_factor.cpp:301-321)
+int launch_pending_marginalizations(const tcv_opt_ticket &T) {
+    for (tcv_estimator *e : T.es) {
         if (!e->pend) continue;
         std::shared_ptr<EstInflight> fl = e->pend;
-        const int rcl = fl->launch((void *)tcv::util_stream());
+        const int rcl = fl->launch((void *)T.stream);
         if (rcl != TCV_OK) {
             // the launch failed for the whole batch of the previous frame (EstInflight::launch keeps the verdict): every estimator of that batch loses
             // its new prior -- and only those: nothing is sticky, the rest of THIS call's estimators go on, and the affected ones report the failure
@@ -923,381 +944,327 @@ static int optimize_begin(OptRun &R) {
         e->prev = fl; e->prev_k = e->pend_k;
         e->pend.reset(); e->pend_k = -1;
     }
-    // one pre-integration call for every stale IMU buffer of every estimator
-    {
-        std::vector<int> first, count;
-        std::vector<double> samples, init;
-        std::vector<std::pair<int, int>> who;
-        for (int i = 0; i < n; i++)
-            for (int j = 1; j <= W; j++) {
-                tcv_estimator *e = es[i];
-                if (e->pre_valid[j]) continue;
-                const ImuBuf &b = e->bufs[j];
-                if (!b.valid) { tcv::set_error("estimators_optimize: missing IMU buffer"); return TCV_ERR_INVALID; }
-                who.push_back({i, j});
-                first.push_back((int)samples.size() / 7); count.push_back((int)b.acc.size());
-                for (size_t k = 0; k < b.acc.size(); k++) { samples.push_back(e->cfg.imu_dt); samples.insert(samples.end(), b.acc[k].begin(), b.acc[k].end()); samples.insert(samples.end(), b.gyr[k].begin(), b.gyr[k].end()); }
-                init.insert(init.end(), b.acc0.begin(), b.acc0.end()); init.insert(init.end(), b.gyr0.begin(), b.gyr0.end());
-                init.insert(init.end(), b.ba.begin(), b.ba.end()); init.insert(init.end(), b.bg.begin(), b.bg.end());
-            }
-        if (!who.empty()) {
-            const tcv_estimator_config &c = es[0]->cfg;
-            const double noise[4] = {c.acc_n, c.gyr_n, c.acc_w, c.gyr_w};
-            if (samples.empty()) samples.push_back(0.0);
-            // pre_integrations[] stay on the device (the reference keeps them alive between frames, too): a handle per buffer, sum_dt on the
-            // host; nobody waits for the kernel (tcv_preintegrate_device).  TCV_EST_HOST_PREINT=1: round 3's round trip (3.7 KB down per buffer,
-            // 2.3 KB up per factor and window), same bits
-            if (getenv("TCV_EST_HOST_PREINT") || getenv("TCV_EST_HOST_STATE")) {
-                std::vector<tcv_imu_preintegration> out(who.size());
-                const int rc = tcv_preintegrate((int)who.size(), first.data(), count.data(), samples.data(), (int)samples.size() / 7, init.data(), noise, out.data());
-                if (rc != TCV_OK) return rc;
-                for (size_t k = 0; k < who.size(); k++) { tcv_estimator *e = es[who[k].first]; e->pre[who[k].second] = out[k]; e->preh[who[k].second].reset(); e->pre_valid[who[k].second] = true; }
-            } else {
-                std::vector<tcv_preint *> hd(who.size(), nullptr);
-                const int rc = tcv_preintegrate_device((int)who.size(), first.data(), count.data(), samples.data(), (int)samples.size() / 7, init.data(), noise, hd.data());
-                if (rc != TCV_OK) return rc;
-                for (size_t k = 0; k < who.size(); k++) {
-                    tcv_estimator *e = es[who[k].first];
-                    const int j = who[k].second;
-                    e->preh[j] = std::shared_ptr<tcv_preint>(hd[k], tcv_preint_destroy);
-                    std::memset(&e->pre[j], 0, sizeof e->pre[j]);
-                    e->pre[j].sum_dt = tcv_preint_sum_dt(hd[k]);
-                    e->pre_valid[j] = true;
-                }
-            }
+    return TCV_OK;
+}
+// one pre-integration call for every stale IMU buffer of every estimator
+int preintegrate_stale(const tcv_opt_ticket &T) {
+    std::vector<int> first, count;
+    std::vector<double> samples, init;
+    std::vector<std::pair<tcv_estimator *, int>> who;
+    for (tcv_estimator *e : T.es)
+        for (int j = 1; j <= W; j++) {
+            if (e->pre_valid[j]) continue;
+            const ImuBuf &b = e->bufs[j];
+            if (!b.valid) { tcv::set_error("estimators_optimize: missing IMU buffer"); return TCV_ERR_INVALID; }
+            who.push_back({e, j});
+            first.push_back((int)samples.size() / 7); count.push_back((int)b.acc.size());
+            for (size_t k = 0; k < b.acc.size(); k++) { samples.push_back(e->cfg.imu_dt); samples.insert(samples.end(), b.acc[k].begin(), b.acc[k].end()); samples.insert(samples.end(), b.gyr[k].begin(), b.gyr[k].end()); }
+            init.insert(init.end(), b.acc0.begin(), b.acc0.end()); init.insert(init.end(), b.gyr0.begin(), b.gyr0.end());
+            init.insert(init.end(), b.ba.begin(), b.ba.end()); init.insert(init.end(), b.bg.begin(), b.bg.end());
         }
+    if (who.empty()) return TCV_OK;
+    const tcv_estimator_config &c = T.es[0]->cfg;
+    const double noise[4] = {c.acc_n, c.gyr_n, c.acc_w, c.gyr_w};
+    if (samples.empty()) samples.push_back(0.0);
+    // pre_integrations[] stay on the device (the reference keeps them alive between frames, too): a handle per buffer, sum_dt on the
+    // host; nobody waits for the kernel (tcv_preintegrate_device).  TCV_EST_HOST_PREINT=1: round 3's round trip (3.7 KB down per buffer,
+    // 2.3 KB up per factor and window), the reference of tests/test_gpu_resident.py -- same bits
+    if (getenv("TCV_EST_HOST_PREINT")) {
+        std::vector<tcv_imu_preintegration> out(who.size());
+        const int rc = tcv_preintegrate((int)who.size(), first.data(), count.data(), samples.data(), (int)samples.size() / 7, init.data(), noise, out.data());
+        if (rc != TCV_OK) return rc;
+        for (size_t k = 0; k < who.size(); k++) { tcv_estimator *e = who[k].first; e->pre[who[k].second] = out[k]; e->preh[who[k].second].reset(); e->pre_valid[who[k].second] = true; }
+        return TCV_OK;
     }
-    lap(0);
-    {
-        for_each_estimator(n, [&](int i) {
-            tcv_estimator *e = es[i];
-            if (e->assoc) assoc_finish(e, jobs[i]);
-            triangulate(e);
-            build_window(e);
-        });
-        for (int i = 0; i < n; i++) if (es[i]->tap.on) { const int rc = tap_window(es[i]); if (rc != TCV_OK) return rc; }
+    std::vector<tcv_preint *> hd(who.size(), nullptr);
+    const int rc = tcv_preintegrate_device((int)who.size(), first.data(), count.data(), samples.data(), (int)samples.size() / 7, init.data(), noise, hd.data());
+    if (rc != TCV_OK) return rc;
+    for (size_t k = 0; k < who.size(); k++) {
+        tcv_estimator *e = who[k].first;
+        const int j = who[k].second;
+        e->preh[j] = std::shared_ptr<tcv_preint>(hd[k], tcv_preint_destroy);
+        std::memset(&e->pre[j], 0, sizeof e->pre[j]);
+        e->pre[j].sum_dt = tcv_preint_sum_dt(hd[k]);
+        e->pre_valid[j] = true;
     }
-    lap(1);
-    // One device batch per frame: the windows that marginalise (MARGIN_OLD, or MARGIN_SECOND_NEW with para_Pose[WINDOW_SIZE - 1] in the prior,
-    // estimator.cpp:2049-2050) carry a marginalisation problem, the others a NULL entry (tcv_batch_create).  TCV_EST_TWO_BATCHES=1: round 3's
-    // split into a batch that marginalises and one that only solves (two tcv_batch_create calls, two launches side by side) -- same bits.
-    static const bool two_batches = getenv("TCV_EST_TWO_BATCHES") != nullptr;
-    std::vector<char> do_marg(n);
+    return TCV_OK;
+}
+// association, second half, and solveOdometry up to the solver call: triangulation, vector2double + graph
+int build_windows(const tcv_opt_ticket &T, std::vector<AssocJob> &jobs) {
+    for_each_estimator(T.n(), [&](int i) {
+        tcv_estimator *e = T.es[i];
+        if (e->assoc) assoc_finish(e, jobs[i]);
+        triangulate(e);
+        build_window(e);
+    });
+    for (tcv_estimator *e : T.es) if (e->tap.on) { const int rc = tap_window(e); if (rc != TCV_OK) return rc; }
+    return TCV_OK;
+}
+// the marginalisation problem of window k and the blocks it drops: both hand-over modes build it here, on a worker thread
+int build_marg_problem(tcv_opt_ticket &T, int k) {
+    tcv_estimator *e = T.es[k];
+    tcv_window_desc d;
+    build_marg(e, e->marg_flag);
+    fill_desc(e, d, true, e->marg_flag);
+    const int rc = tcv_problem_from_window(&d, &T.M[k]);
+    T.drops[k] = e->m_drop.data(); T.ndrop[k] = (int)e->m_drop.size();
+    return rc;
+}
+// every window's problem.  Host priors: a marginalising window's second problem in the same task; priors on the device: the batch is created
+// without them, they are built and attached while the solve runs (attach_marginalization)
+void build_problems(tcv_opt_ticket &T) {
+    T.rc = first_failure(for_each_estimator_rc(T.n(), [&](int k) {
+        tcv_estimator *e = T.es[k];
+        tcv_window_desc d;
+        fill_desc(e, d, false, e->marg_flag);
+        const int rc = tcv_problem_from_window(&d, &T.P[k]);
+        return rc == TCV_OK && T.dm[k] && T.host_priors ? build_marg_problem(T, k) : rc;
+    }));
+}
+void create_batch(tcv_opt_ticket &T) {
+    if (T.rc != TCV_OK) return;
+    const bool with_marg = T.any_marg && T.host_priors;
+    T.rc = tcv_batch_create(&T.b, T.P.data(), with_marg ? T.M.data() : nullptr, with_marg ? T.drops.data() : nullptr, with_marg ? T.ndrop.data() : nullptr, T.n());
+}
+void enqueue_solve(tcv_opt_ticket &T) {
+    if (T.rc != TCV_OK) return;
+    const tcv_estimator_config &c = T.es[0]->cfg;
+    tcv_solver_options o;
+    tcv_solver_options_default(&o);
+    o.max_num_iterations = c.num_iterations; o.fixed_iterations = c.fixed_iterations;
+    if (c.solver_time > 0.0 && !o.fixed_iterations) {      // estimator.cpp:1894-1897 (one budget per batch: include/tcv_estimator.h)
+        bool any_old = false;
+        for (const tcv_estimator *e : T.es) any_old = any_old || e->marg_flag == MARGIN_OLD;
+        o.max_solver_time_in_seconds = c.solver_time * (any_old ? 4.0 / 5.0 : 1.0);
+    }
+    void *st = (void *)T.stream;
+    // double2vector() in the solve kernel's epilogue (the tcv_batch_gauge_fix below is then a no-op): one launch and its gap less per frame;
+    // bit for bit the stand-alone kernel's result (tests/test_gpu_gauge.py)
+    T.rc = tcv_batch_set_fused_gauge_fix(T.b, 1);
+    if (T.rc == TCV_OK) T.rc = tcv_batch_solve(T.b, &o, st);
+    if (T.rc == TCV_OK) T.rc = tcv_batch_gauge_fix(T.b, st);
+    if (T.host_priors) { if (T.rc == TCV_OK && T.any_marg) T.rc = tcv_batch_marginalize(T.b, st); return; }
+    // the copy of the states (and of the summary heads) goes on the stream right behind the gauge fix -- BEFORE the upload of the marginalisation
+    // problems attached next, which used to sit between them (a lock-step frame's GPU timeline: 10 us of upload, a fill and their launch gaps,
+    // ~35 us before the states left; tools/gpu_calls.md#r05_gpu_z43)
+    if (T.rc == TCV_OK) { T.rc = tcv_batch_download_states_begin(T.b, st); T.dl_begun = T.rc == TCV_OK; }
+}
+// the solve is on the device: the marginalisation problems of the frame, their packing and upload meanwhile
+void attach_marginalization(tcv_opt_ticket &T) {
+    if (T.rc != TCV_OK || !T.any_marg) return;
+    T.rc = first_failure(for_each_estimator_rc(T.n(), [&](int k) { return T.dm[k] ? build_marg_problem(T, k) : TCV_OK; }));
+    if (T.rc == TCV_OK) T.rc = tcv_batch_attach_marginalization(T.b, T.M.data(), T.drops.data(), T.ndrop.data());
+}
+// A frame of a few windows enqueues its marginalisation NOW, while the solve runs, with its no-wait prior handles: the kernel starts the moment
+// the states have left instead of a host round trip (wake-up, unpacking, launch) later, which the next frame's association would wait out.
+// It runs on the thread's SECOND stream (ordered behind the copy of the states by an event): the next frame's association round trip on
+// the main stream then does not queue behind the kernel (0.45 -> 0.2 ms of a 2.4 ms frame: 8 streams on one host thread 3 200 -> 3 700
+// windows/s; on two host threads only if the runtime has a hardware queue per stream, GPU_MAX_HW_QUEUES >= 8: 3 400 -> 3 750; otherwise
+// no change).
+void enqueue_eager_marginalization(tcv_opt_ticket &T) {
+    if (T.rc != TCV_OK || !T.any_marg) return;
+    T.rc = tcv_batch_marginalize(T.b, (void *)tcv::aux_stream());
+    if (T.rc == TCV_OK) T.rc = tcv_batch_get_priors_device_async(T.b, T.newp.data(), T.n());
+}
+
+// Errors up to the tap (bad arguments, association, the pending frame's prior, pre-integration) return from here and leave no ticket; from
+// problem construction on they are carried in T.rc to optimize_end, which consumes the ticket.
+int optimize_begin(tcv_opt_ticket &T) {
+    const int n = T.n();
+    T.stream = tcv::util_stream();
+    prof_add(7, 1);
+    if (const int rc = check_ready(T)) return rc;
+    // The association's device round trip comes first and the pre-integration of the new IMU buffers is issued behind it (nobody on the host
+    // waits for that kernel: its results are spliced into the batch on the device), so the kernel runs while the host builds the windows and problems.
+    std::vector<AssocJob> jobs(n);
+    if (const int rc = associate(T, jobs)) return rc;
+    T.lap.add(1);
+    if (const int rc = launch_pending_marginalizations(T)) return rc;
+    if (const int rc = preintegrate_stale(T)) return rc;
+    T.lap.add(0);
+    if (const int rc = build_windows(T, jobs)) return rc;
+    T.lap.add(1);
+
+    T.dm.resize(n);
     for (int i = 0; i < n; i++) {
+        const tcv_estimator *e = T.es[i];
         bool has = false;
-        for (auto &b : es[i]->prior_blocks) if (b.first == 0 && b.second == W - 1) has = true;
-        do_marg[i] = es[i]->marg_flag == MARGIN_OLD || (es[i]->prior && has);
+        for (auto &b : e->prior_blocks) if (b.first == 0 && b.second == W - 1) has = true;
+        T.dm[i] = e->marg_flag == MARGIN_OLD || (e->prior && has);
+        T.any_marg = T.any_marg || T.dm[i];
     }
-    // The two batches of a frame are independent: both are created first, then their kernels are launched on two HIP streams and run
-    // side by side (a lock-step frame is latency bound: a handful of windows on a handful of CUs), then both are collected.
-    OptGroup (&G)[2] = R.G;
-    // Every kernel of the frame goes on the CALLING THREAD's utility stream -- the stream tcv_batch_create's uploads, the device-to-device
-    // splices and the downloads of this thread use anyway: host threads that drive their own estimators overlap on the device (a stream pair
-    // shared by the threads of a device, as until round 4, serialises their kernels: 8 streams on 4 host threads 1 000 against 2 400 windows/s),
-    // and with one stream per thread no small copy of one thread waits behind another thread's 2 ms solve kernel on a shared hardware queue.
-    // (TCV_EST_TWO_BATCHES: the two batches of a frame then run one after the other.)
-    hipStream_t (&g_streams)[2] = R.g_streams;
-    g_streams[0] = g_streams[1] = tcv::util_stream();
-    // last_marginalization_info stays on the device (estimator.h:176-177: the reference keeps it alive between frames, too): the new
-    // priors are handles on the batch's result buffer, the next frame's tcv_batch_create splices them device-to-device.
-    // TCV_EST_HOST_PRIORS=1: round 3's host round trip (62 KB down, 46 KB up per window), the A/B partner -- same bits.
-    // Faster at every batch size once every host thread launches on its own stream (512-window passes: 171 K against 117 K windows/s; eight
-    // replay streams on two host threads: 2 370 - 2 480 against 2 250 - 2 280 windows/s).  TCV_EST_HOST_STATE=1 (both) / TCV_EST_HOST_PRIORS=1 /
-    // TCV_EST_HOST_PREINT=1 take the host round trip.
-    const bool host_priors = getenv("TCV_EST_HOST_PRIORS") != nullptr || getenv("TCV_EST_HOST_STATE") != nullptr;
-    // With the priors on the device the host needs nothing of the marginalisation but its status: the call returns once the solve and the
-    // gauge fix are done and the states are applied; the marginalisation is launched behind them and runs while the caller finishes the
-    // frame and starts the next one (tcv_batch_get_priors_device_async).  Its status is read at each estimator's NEXT frame, after that
-    // frame's solve: a window solved on a prior whose marginalisation failed is not applied and reports the failure (finish_frame), one
-    // frame late.  TCV_EST_MARG_WAIT=1: wait for it as before (same bits).
-    const bool marg_off_path = !host_priors && !two_batches && getenv("TCV_EST_MARG_WAIT") == nullptr;
-    int &rc_all = R.rc_all;
-    rc_all = TCV_OK;
-    for (int group = 1; group >= 0; group--) {
-        Group &g = G[group];
-        for (int i = 0; i < n; i++) if ((two_batches ? (int)do_marg[i] : 1) == group) { g.idx.push_back(i); g.dm.push_back(do_marg[i]); g.any_marg = g.any_marg || do_marg[i]; }
-        if (g.idx.empty()) continue;
-        const int nb = (int)g.idx.size();
-        g.P.assign(nb, nullptr); g.M.assign(nb, nullptr); g.drops.assign(nb, nullptr); g.ndrop.assign(nb, 0);
-        {
-            std::vector<int> rcs(nb, TCV_OK);
-            std::vector<std::string> msgs(nb);
-            for_each_estimator(nb, [&](int k) {      // (the error text is per thread: a worker's is carried over)
-                tcv_estimator *e = es[g.idx[k]];
-                tcv_window_desc d;
-                fill_desc(e, d, false, e->marg_flag);
-                rcs[k] = tcv_problem_from_window(&d, &g.P[k]);
-                if (rcs[k] == TCV_OK && g.dm[k] && !marg_off_path) {
-                    build_marg(e, e->marg_flag);
-                    fill_desc(e, d, true, e->marg_flag);
-                    rcs[k] = tcv_problem_from_window(&d, &g.M[k]);
-                    g.drops[k] = e->m_drop.data(); g.ndrop[k] = (int)e->m_drop.size();
-                }
-                if (rcs[k] != TCV_OK) msgs[k] = tcv_last_error();
-            });
-            for (int k = 0; k < nb && g.rc == TCV_OK; k++) if (rcs[k] != TCV_OK) { g.rc = rcs[k]; tcv::set_error(msgs[k]); }
-        }
-        lap(2);
-        // (marg_off_path: the batch is created without its marginalisation problems -- they are built and attached below, while the solve runs)
-        const bool with_marg = g.any_marg && !marg_off_path;
-        if (g.rc == TCV_OK) g.rc = tcv_batch_create(&g.b, g.P.data(), with_marg ? g.M.data() : nullptr, with_marg ? g.drops.data() : nullptr, with_marg ? g.ndrop.data() : nullptr, nb);
-        lap(3);
-    }
-    for (int group = 1; group >= 0; group--) {
-        Group &g = G[group];
-        if (g.idx.empty() || g.rc != TCV_OK) continue;
-        tcv_solver_options o;
-        tcv_solver_options_default(&o);
-        o.max_num_iterations = es[0]->cfg.num_iterations; o.fixed_iterations = es[0]->cfg.fixed_iterations;
-        if (es[0]->cfg.solver_time > 0.0 && !o.fixed_iterations) {      // estimator.cpp:1894-1897 (one budget per batch: include/tcv_estimator.h)
-            bool any_old = false;
-            for (int i : g.idx) any_old = any_old || es[i]->marg_flag == MARGIN_OLD;
-            o.max_solver_time_in_seconds = es[0]->cfg.solver_time * (any_old ? 4.0 / 5.0 : 1.0);
-        }
-        void *st = (void *)g_streams[group];
-        // double2vector() in the solve kernel's epilogue (the tcv_batch_gauge_fix below is then a no-op): one launch and its gap less per frame.
-        // TCV_EST_SEPARATE_GAUGE=1: the stand-alone kernel, as up to round 5 (same bits)
-        static const bool separate_gauge = getenv("TCV_EST_SEPARATE_GAUGE") != nullptr;
-        if (!separate_gauge) g.rc = tcv_batch_set_fused_gauge_fix(g.b, 1);
-        if (g.rc == TCV_OK) g.rc = tcv_batch_solve(g.b, &o, st);
-        if (g.rc == TCV_OK) g.rc = tcv_batch_gauge_fix(g.b, st);
-        if (g.rc == TCV_OK && g.any_marg && !marg_off_path) g.rc = tcv_batch_marginalize(g.b, st);
-        // the copy of the states (and of the summary heads) goes on the stream right behind the gauge fix -- BEFORE the upload of the marginalisation
-        // problems attached below, which used to sit between them (a lock-step frame's GPU timeline: 10 us of upload, a fill and their launch gaps,
-        // ~35 us before the states left; tools/gpu_calls.md#r05_gpu_z43)
-        if (g.rc == TCV_OK && marg_off_path) { g.rc = tcv_batch_download_states_begin(g.b, st); g.dl_begun = g.rc == TCV_OK; }
-    }
-    if (marg_off_path) {      // the solve is on the device: the marginalisation problems of the frame, their packing and upload meanwhile
-        for (int group = 1; group >= 0; group--) {
-            Group &g = G[group];
-            if (g.idx.empty() || g.rc != TCV_OK || !g.any_marg) continue;
-            const int nb = (int)g.idx.size();
-            std::vector<int> rcs(nb, TCV_OK);
-            std::vector<std::string> msgs(nb);
-            for_each_estimator(nb, [&](int k) {
-                if (!g.dm[k]) return;
-                tcv_estimator *e = es[g.idx[k]];
-                tcv_window_desc d;
-                build_marg(e, e->marg_flag);
-                fill_desc(e, d, true, e->marg_flag);
-                rcs[k] = tcv_problem_from_window(&d, &g.M[k]);
-                g.drops[k] = e->m_drop.data(); g.ndrop[k] = (int)e->m_drop.size();
-                if (rcs[k] != TCV_OK) msgs[k] = tcv_last_error();
-            });
-            for (int k = 0; k < nb && g.rc == TCV_OK; k++) if (rcs[k] != TCV_OK) { g.rc = rcs[k]; tcv::set_error(msgs[k]); }
-            if (g.rc == TCV_OK) g.rc = tcv_batch_attach_marginalization(g.b, g.M.data(), g.drops.data(), g.ndrop.data());
-        }
-    }
+    T.P.assign(n, nullptr); T.M.assign(n, nullptr); T.drops.assign(n, nullptr); T.ndrop.assign(n, 0); T.newp.assign(n, nullptr);
+    T.host_priors = getenv("TCV_EST_HOST_PRIORS") != nullptr;
     // Deferred marginalisation (EstInflight::launch) for frames of many windows, whose host side is long enough to hide the kernel behind the NEXT
     // frame's window construction: 128 streams on two host threads 17.4 K against 15.7 K windows/s.  A frame of a few windows enqueues it here,
     // right behind the copy of its states -- deferred, its 0.45 ms would end up in front of the next frame's upload (8 streams: 3 050 against
     // 3 250 windows/s).  TCV_EST_MARG_DEFER=n: defer from n windows per call on (0: never, 1: always).
     const char *e_defer = getenv("TCV_EST_MARG_DEFER");      // (read per call: the tests switch it)
     const int defer_from = e_defer ? atoi(e_defer) : 12;
-    // the marginalisation of a frame of few windows runs on the thread's SECOND stream (ordered behind the copy of the states by an event): the next
-    // frame's association round trip on the main stream then does not queue behind the kernel (0.45 -> 0.2 ms of a 2.4 ms frame: 8 streams on one
-    // host thread 3 200 -> 3 700 windows/s; on two host threads only if the runtime has a hardware queue per stream, GPU_MAX_HW_QUEUES >= 8:
-    // 3 400 -> 3 750; otherwise no change).  TCV_EST_MARG_AUX=0: on the main stream, as until round 5.
-    static const bool marg_aux = !(getenv("TCV_EST_MARG_AUX") && atoi(getenv("TCV_EST_MARG_AUX")) == 0);
-    if (marg_off_path) {
-        // everything the frame still needs from the device goes on the stream NOW, while the solve runs: the copy of the states (and of the
-        // summary heads), and behind it the marginalisation with its no-wait prior handles -- the kernel starts the moment the states have
-        // left instead of a host round trip (wake-up, unpacking, launch) later, which the next frame's association would wait out
-        for (int group = 1; group >= 0; group--) {
-            Group &g = G[group];
-            if (g.idx.empty() || g.rc != TCV_OK) continue;
-            const int nb = (int)g.idx.size();
-            void *st = (void *)g_streams[group];
-            if (!g.dl_begun) { g.rc = tcv_batch_download_states_begin(g.b, st); g.dl_begun = g.rc == TCV_OK; }
-            g.newp.assign(nb, nullptr);
-            const bool eager = defer_from <= 0 || nb < defer_from;
-            if (g.rc == TCV_OK && g.any_marg && eager) {
-                // (TCV_EST_MARG_AUX=1: on the thread's SECOND stream, ordered behind the copy of the states by an event -- the next frame's
-                // association round trip on the main stream then does not queue behind the kernel)
-                g.rc = tcv_batch_marginalize(g.b, marg_aux ? (void *)tcv::aux_stream() : st);
-                if (g.rc == TCV_OK) g.rc = tcv_batch_get_priors_device_async(g.b, g.newp.data(), nb);
-                g.marg_launched = g.rc == TCV_OK;
-            }
-        }
+    T.defer = !T.host_priors && defer_from > 0 && n >= defer_from;
+
+    build_problems(T);
+    T.lap.add(2);
+    create_batch(T);
+    T.lap.add(3);
+    enqueue_solve(T);
+    if (!T.host_priors) {
+        attach_marginalization(T);
+        if (!T.defer) enqueue_eager_marginalization(T);
     }
-    R.host_priors = host_priors; R.marg_off_path = marg_off_path; R.defer_from = defer_from; R.marg_aux = marg_aux;
-    if (getenv("TCV_DEBUG_PIPE")) fprintf(stderr, "[pipe] %p begin  n %d  %.3f -> %.3f ms\n", (void *)tcv::util_stream(), n, 1e3 * (R.t_begin0 - 1.7e9 * 0), 1e3 * now_s());
     return TCV_OK;
 }
 
-static int optimize_end(OptRun &R) {
-    R.t_end0 = now_s();
-    tcv_estimator *const *es = R.esv.data();
-    typedef OptGroup Group;
-    double &t_mark = R.t_mark;
-    double c_mark = prof_cpu_on() ? cpu_now_s() : 0.0;
-    auto lap = [&](int slot) { const double t = now_s(); prof_add(slot, t - t_mark); t_mark = t; if (prof_cpu_on()) { const double c = cpu_now_s(); prof_cpu_add(slot, c - c_mark); c_mark = c; } };
-    OptGroup (&G)[2] = R.G;
-    hipStream_t (&g_streams)[2] = R.g_streams;
-    int &rc_all = R.rc_all;
-    const bool host_priors = R.host_priors, marg_off_path = R.marg_off_path, marg_aux = R.marg_aux;
-    const int defer_from = R.defer_from;
-    for (int group = 1; group >= 0; group--) {
-        Group &g = G[group];
-        if (g.idx.empty()) continue;
-        const int nb = (int)g.idx.size();
-        g.sum.resize(nb);
-        if (g.dl_begun) {      // waits for the copy (an event behind the solve and the gauge fix), not for the marginalisation behind it
-            std::vector<int> its(nb, 0), tms(nb, 0);
-            std::vector<double> fcs(nb, 0.0);
-            const int rcd = tcv_batch_download_states_end(g.b, its.data(), tms.data(), fcs.data());
-            if (g.rc == TCV_OK) g.rc = rcd;
-            for (int k = 0; k < nb; k++) { std::memset(&g.sum[k], 0, sizeof g.sum[k]); g.sum[k].num_iterations = its[k]; g.sum[k].termination = tms[k]; g.sum[k].final_cost = fcs[k]; }
-        } else if (g.rc == TCV_OK) g.rc = tcv_batch_synchronize(g.b);
-        double ms = 0;
-        if (g.rc == TCV_OK && tcv_batch_stats(g.b, nullptr, &ms, nullptr) == TCV_OK && ms > 0) { kern_add(0, ms); kern_add(1, 1); }
-        if (getenv("TCV_DEBUG_PIPE")) fprintf(stderr, "[pipe] %p end    n %d  entered %.3f  states at %.3f ms (solve kernel %.3f ms)\n", (void *)tcv::util_stream(), nb, 1e3 * R.t_end0, 1e3 * now_s(), ms);
+// the states and the three summary numbers of every window, through tcv_batch_download_states_end or _brief
+int download_states(tcv_opt_ticket &T, int (*download)(tcv_batch *, int *, int *, double *)) {
+    const int n = T.n();
+    std::vector<int> its(n, 0), tms(n, 0);
+    std::vector<double> fcs(n, 0.0);
+    const int rc = download(T.b, its.data(), tms.data(), fcs.data());
+    for (int k = 0; k < n; k++) { T.sum[k].num_iterations = its[k]; T.sum[k].termination = tms[k]; T.sum[k].final_cost = fcs[k]; }
+    return rc;
+}
+void wait_for_states(tcv_opt_ticket &T) {
+    T.sum.assign(T.n(), tcv_solver_summary());
+    if (T.dl_begun) {      // waits for the copy (an event behind the solve and the gauge fix), not for the marginalisation behind it
+        const int rcd = download_states(T, tcv_batch_download_states_end);
+        if (T.rc == TCV_OK) T.rc = rcd;
+    } else if (T.rc == TCV_OK) T.rc = tcv_batch_synchronize(T.b);      // (host priors: solve and marginalisation)
+    double ms = 0;
+    if (T.rc == TCV_OK && tcv_batch_stats(T.b, nullptr, &ms, nullptr) == TCV_OK && ms > 0) { kern_add(0, ms); kern_add(1, 1); }
+}
+// host priors: states + the three summary numbers in one device round trip, then the priors of the whole batch as one blob
+void download_to_host(tcv_opt_ticket &T) {
+    if (T.rc == TCV_OK) T.rc = download_states(T, tcv_batch_download_states_brief);
+    if (T.rc == TCV_OK && T.any_marg) T.rc = tcv_batch_download_priors_compact(T.b);
+}
+// what became of each window: est_rc / est_msg.  A failed window fails alone -- the other estimators of the lock-step batch are applied,
+// this one reports the failure from tcv_estimator_finish_frame
+void judge_windows(tcv_opt_ticket &T) {
+    const int n = T.n();
+    T.est_rc.assign(n, TCV_OK);
+    if (T.rc != TCV_OK) return;
+    double bytes = 0, lin = 0;      // algorithmic bytes of the frame's windows x linearisations (the initial one + one per iteration)
+    for (int k = 0; k < n; k++) {
+        const tcv_estimator *e = T.es[k];
+        const double L = (double)e->sel.size(), pn = e->prior ? (double)e->stats.prior_n : 0.0, nl = (double)std::max(1, T.sum[k].num_iterations);      // (ceres numbering: iteration 0 is the initial linearisation)
+        const double per = 8.0 * ((77 + 99 + 7 + L) + 287.0 * e->w_imu.size() + 6.0 * e->w_pi.size() + 9.0 * e->w_lf.size() + 21 + (pn > 0 ? pn * pn + pn + 86 : 0))
+                           + 4.0 * (4.0 * e->w_imu.size() + 4.0 * e->w_pi.size() + e->w_lf.size()) + 8.0 * ((171 + L) + 1);
+        bytes += per * nl; lin += nl;
     }
-    lap(4);
-    for (int group = 1; group >= 0; group--) {
-        Group &g = G[group];
-        if (g.idx.empty()) continue;
-        const int nb = (int)g.idx.size();
-        if ((int)g.newp.size() != nb) g.newp.assign(nb, nullptr);
-        static const bool dbg_dl = getenv("TCV_DEBUG_EST") != nullptr;      // developer: where the "downloads" lap goes
-        const double td0 = now_s();
-        if (!g.dl_begun) {      // (the variants that wait for the marginalisation inside the call: states + the three summary numbers, one device round trip)
-            std::vector<int> its(nb, 0), tms(nb, 0);
-            std::vector<double> fcs(nb, 0.0);
-            if (g.rc == TCV_OK) g.rc = tcv_batch_download_states_brief(g.b, its.data(), tms.data(), fcs.data());
-            for (int k = 0; k < nb; k++) { std::memset(&g.sum[k], 0, sizeof g.sum[k]); g.sum[k].num_iterations = its[k]; g.sum[k].termination = tms[k]; g.sum[k].final_cost = fcs[k]; }
+    kern_add(4, n); kern_add(5, bytes); kern_add(6, lin);
+    for (int k = 0; k < n; k++) {
+        // ceres::Solve's FAILURE (no valid step / a cooperative group that timed out): the window's states are not applied
+        if (T.sum[k].termination == 5 || !(T.sum[k].final_cost == T.sum[k].final_cost)) { T.est_rc[k] = TCV_ERR_NUMERIC; T.est_msg = "solver failure (no valid step, NaN cost or workgroup time-out)"; }
+        tcv_estimator *e = T.es[k];
+        if (e->pend_failed != TCV_OK) {
+            T.est_rc[k] = e->pend_failed; T.est_msg = "the previous frame's marginalisation could not be launched (" + e->pend_msg + "): this window was solved without its prior";
+            e->pend_failed = TCV_OK; e->pend_msg.clear();
         }
-        const double td1 = now_s();
-        const double td2 = td1;
-        bool have_dev = false;
-        const bool marg_eager = defer_from <= 0 || nb < defer_from;
-        const bool defer_marg = g.rc == TCV_OK && g.any_marg && marg_off_path && !marg_eager;
-        if (defer_marg) have_dev = true;      // (nothing to fetch now: EstInflight::launch at the estimators' next frame)
-        if (g.marg_launched) have_dev = true; // (enqueued behind the copy of the states, above; the handles are in g.newp)
-        else if (g.rc == TCV_OK && g.any_marg && marg_off_path && marg_eager) {      // TCV_EST_MARG_AUX=1: on the thread's second stream, now that the states are on the host
-            // (one host thread 2 570 - 2 720 against 2 590 windows/s, two host threads 2 490 - 2 550 against 2 940: two streams per thread share
-            // the runtime's four hardware queues again)
-            g.rc = tcv_batch_marginalize(g.b, marg_aux ? (void *)tcv::aux_stream() : (void *)g_streams[group]);
-            if (g.rc == TCV_OK) g.rc = tcv_batch_get_priors_device_async(g.b, g.newp.data(), nb);
-            have_dev = g.rc == TCV_OK;
+        // the marginalisation that made this window's prior was still running when the previous frame returned: its verdict now (it
+        // finished before this frame's solve started)
+        if (e->prev) {
+            const int stp = e->prev->status_of(e->prev_k);
+            if (stp != 0 && stp != 2) { T.est_rc[k] = TCV_ERR_NUMERIC; T.est_msg = "the previous frame's marginalisation failed (eigen-solver sweep cap or NaN): this window was solved on an invalid prior"; }
+            e->prev.reset(); e->prev_k = -1;      // (the last estimator of that frame to let go destroys its batch)
         }
-        if (g.rc == TCV_OK && g.any_marg && !host_priors && !marg_off_path) have_dev = tcv_batch_get_priors_device(g.b, g.newp.data(), nb) == TCV_OK;      // (a window that failed: the per-window path below says which)
-        if (g.rc == TCV_OK && g.any_marg && !have_dev) g.rc = tcv_batch_download_priors_compact(g.b);
-        g.est_rc.assign(nb, TCV_OK);
-        if (g.rc == TCV_OK) {      // algorithmic bytes of the frame's windows x linearisations (the initial one + one per iteration)
-            double bytes = 0, lin = 0;
-            for (int k = 0; k < nb; k++) {
-                const tcv_estimator *e = es[g.idx[k]];
-                const double L = (double)e->sel.size(), n = e->prior ? (double)e->stats.prior_n : 0.0, nl = (double)std::max(1, g.sum[k].num_iterations);      // (ceres numbering: iteration 0 is the initial linearisation)
-                const double per = 8.0 * ((77 + 99 + 7 + L) + 287.0 * e->w_imu.size() + 6.0 * e->w_pi.size() + 9.0 * e->w_lf.size() + 21 + (n > 0 ? n * n + n + 86 : 0))
-                                   + 4.0 * (4.0 * e->w_imu.size() + 4.0 * e->w_pi.size() + e->w_lf.size()) + 8.0 * ((171 + L) + 1);
-                bytes += per * nl; lin += nl;
-            }
-            kern_add(4, nb); kern_add(5, bytes); kern_add(6, lin);
-        }
-        if (g.rc == TCV_OK)
-            for (int k = 0; k < nb; k++) {     // ceres::Solve's FAILURE (no valid step / a cooperative group that timed out): the window's states are not applied
-                if (g.sum[k].termination == 5 || !(g.sum[k].final_cost == g.sum[k].final_cost)) { g.est_rc[k] = TCV_ERR_NUMERIC; g.est_msg = "solver failure (no valid step, NaN cost or workgroup time-out)"; }
-                // the marginalisation that made this window's prior was still running when the previous frame returned: its verdict now (it
-                // finished before this frame's solve started)
-                tcv_estimator *e = es[g.idx[k]];
-                if (e->pend_failed != TCV_OK) {
-                    g.est_rc[k] = e->pend_failed; g.est_msg = "the previous frame's marginalisation could not be launched (" + e->pend_msg + "): this window was solved without its prior";
-                    e->pend_failed = TCV_OK; e->pend_msg.clear();
-                }
-                if (e->prev) {
-                    const int stp = e->prev->status_of(e->prev_k);
-                    if (stp != 0 && stp != 2) { g.est_rc[k] = TCV_ERR_NUMERIC; g.est_msg = "the previous frame's marginalisation failed (eigen-solver sweep cap or NaN): this window was solved on an invalid prior"; }
-                    e->prev.reset(); e->prev_k = -1;      // (the last estimator of that frame to let go destroys its batch)
-                }
-            }
-        if (g.rc == TCV_OK && g.any_marg) {
-            std::vector<std::string> msgs(nb);
-            int cur_dev = 0;
-            (void)hipGetDevice(&cur_dev);
-            for_each_estimator(nb, [&](int k) {
-                // a window whose marginalisation did not converge (TCV_ERR_NUMERIC) fails alone: the other estimators of the lock-step
-                // batch are applied, this one reports the failure from tcv_estimator_finish_frame
-                if (g.est_rc[k] != TCV_OK) { if (g.newp[k]) { tcv_prior_destroy(g.newp[k]); g.newp[k] = nullptr; } return; }
-                if (have_dev || !g.dm[k]) return;
-                (void)hipSetDevice(cur_dev);      // (a worker thread's current device is its own: the fallback copy of a window must see the batch's)
-                g.est_rc[k] = tcv_batch_get_prior(g.b, k, &g.newp[k]);      // (host path: the window's prior out of the downloaded blob)
-                if (g.est_rc[k] != TCV_OK) msgs[k] = tcv_last_error();
-            });
-            for (int k = 0; k < nb; k++) {
-                if (g.est_rc[k] == TCV_OK || msgs[k].empty()) continue;
-                if (g.est_rc[k] != TCV_ERR_NUMERIC) { g.rc = g.est_rc[k]; tcv::set_error(msgs[k]); break; }
-                g.est_msg = msgs[k];
-            }
-        }
-        const double td3 = now_s();
-        if (g.rc == TCV_OK && g.any_marg && marg_off_path && have_dev) {      // the batch lives on until its marginalisation has been asked about
-            // (the batch alone: its problems were read for the last time by tcv_batch_download_states / tcv_batch_attach_marginalization and
-            // go now, like the old prior they point to)
-            auto fl = std::make_shared<EstInflight>();
-            fl->b = g.b;
-            fl->deferred = defer_marg;
-            for (int k = 0; k < nb; k++) fl->n_marg += g.dm[k] ? 1 : 0;
-            g.b = nullptr;
-            for (int k = 0; k < nb; k++)
-                if (g.dm[k] && g.est_rc[k] == TCV_OK) {
-                    tcv_estimator *e = es[g.idx[k]];
-                    if (defer_marg) { e->pend = fl; e->pend_k = k; e->pend_flag = e->marg_flag; const int pn = tcv_marg_layout_n(fl->b, k); if (pn >= 0) e->stats.prior_n = pn; }      // (the new prior's n is part of the attached problem's layout)
-                    else { e->prev = fl; e->prev_k = k; }
-                }
-            g.deferred = defer_marg;
-        }
-        if (g.b) { tcv_batch_destroy(g.b); g.b = nullptr; }      // (the ticket destroys what is left in it)
-        const double td4 = now_s();
-        {      // the frame's problems have been read for the last time: destroyed on a worker thread, behind the caller's back
-            auto dead = std::make_shared<std::vector<tcv_problem *>>();
-            dead->reserve(2 * (size_t)nb);
-            for (int k = 0; k < nb; k++) { if (g.P[k]) dead->push_back(g.P[k]); if (g.M[k]) dead->push_back(g.M[k]); g.P[k] = g.M[k] = nullptr; }
-            tcv::async_run([dead] { for (tcv_problem *q : *dead) tcv_problem_destroy(q); });
-        }
-        if (dbg_dl) fprintf(stderr, "[est] group %d n %d: states %.3f ms, summaries %.3f ms, priors %.3f ms, batch destroy %.3f ms, problems destroy %.3f ms\n", group, nb,
-                            1e3 * (td1 - td0), 1e3 * (td2 - td1), 1e3 * (td3 - td2), 1e3 * (td4 - td3), 1e3 * (now_s() - td4));
-        if (g.rc != TCV_OK && rc_all == TCV_OK) rc_all = g.rc;
+        if (T.est_rc[k] != TCV_OK && T.newp[k]) { tcv_prior_destroy(T.newp[k]); T.newp[k] = nullptr; }
     }
-    lap(5);
-    for (int group = 1; group >= 0; group--) {
-        Group &g = G[group];
-        if (g.idx.empty()) continue;
-        const int nb = (int)g.idx.size();
-        if (rc_all != TCV_OK) { for (auto *&p : g.newp) if (p) { tcv_prior_destroy(p); p = nullptr; } continue; }
-        for (int k = 0; k < nb; k++) {
-            tcv_estimator *e = es[g.idx[k]];
-            e->opt_failed = TCV_OK;
-            if (g.est_rc[k] != TCV_OK) {      // this estimator's window failed numerically: nothing is applied, finish_frame reports it
-                e->opt_failed = g.est_rc[k]; e->opt_msg = g.est_msg; e->phase = 2;
-                continue;
-            }
-            apply_states(e);
-            if (e->tap.on && e->tap.have) {
-                WindowTap &T = e->tap;
-                T.pose_out.assign(e->para_pose, e->para_pose + (W + 1) * 7); T.sb_out.assign(e->para_sb, e->para_sb + (W + 1) * 9);
-                T.ex_out.assign(e->para_ex, e->para_ex + 7); T.feat_out = e->para_feature;
-                T.iterations = g.sum[k].num_iterations; T.final_cost = g.sum[k].final_cost; T.applied = 1;
-            }
-            e->stats.marg_flag = e->marg_flag; e->stats.n_landmarks = (int)e->sel.size(); e->stats.n_proj = (int)e->w_pi.size(); e->stats.n_line = (int)e->w_lf.size();
-            e->stats.n_line_obs = e->n_line_obs_total; e->stats.iterations = g.sum[k].num_iterations; e->stats.termination = g.sum[k].termination; e->stats.final_cost = g.sum[k].final_cost;
-            if (g.dm[k] && g.deferred) { }      // (the new prior is taken at the start of the next frame; stats.prior_n was set with the hand-over above)
-            else if (g.dm[k]) {
-                const int rc = take_prior(e, g.newp[k], e->marg_flag);
-                if (rc != TCV_OK) {      // (take_prior keeps the old prior on failure: the new one and the ones not handed over yet are released)
-                    for (int k2 = k; k2 < nb; k2++) if (g.newp[k2]) { tcv_prior_destroy(g.newp[k2]); g.newp[k2] = nullptr; }
-                    rc_all = rc; break;
-                }
-                g.newp[k] = nullptr;
-            }
-            else e->stats.prior_n = e->prior ? e->stats.prior_n : 0;
-            e->phase = 2;
-        }
-        lap(6);
+}
+// host priors: every window's new prior out of the downloaded blob, on the workers.  A window whose marginalisation did not converge
+// (TCV_ERR_NUMERIC) fails alone; any other error fails the call
+void take_host_priors(tcv_opt_ticket &T) {
+    if (T.rc != TCV_OK || !T.any_marg) return;
+    int cur_dev = 0;
+    (void)hipGetDevice(&cur_dev);
+    const std::vector<TaskRc> r = for_each_estimator_rc(T.n(), [&](int k) {
+        if (T.est_rc[k] != TCV_OK || !T.dm[k]) return (int)TCV_OK;
+        (void)hipSetDevice(cur_dev);      // (a worker thread's current device is its own: the copy of a window must see the batch's)
+        return tcv_batch_get_prior(T.b, k, &T.newp[k]);
+    });
+    for (int k = 0; k < T.n(); k++) {
+        if (r[k].rc == TCV_OK) continue;
+        T.est_rc[k] = r[k].rc;
+        if (r[k].rc != TCV_ERR_NUMERIC) { T.rc = r[k].rc; tcv::set_error(r[k].msg); break; }
+        T.est_msg = r[k].msg;
     }
-    return rc_all;
+}
+// priors on the device: the batch lives on until its marginalisation has been asked about, shared by the estimators that marginalised
+// (the batch alone: its problems were read for the last time by tcv_batch_download_states / tcv_batch_attach_marginalization and go now,
+// like the old prior they point to)
+void hand_over_batch(tcv_opt_ticket &T) {
+    if (T.rc != TCV_OK || !T.any_marg) return;
+    const int n = T.n();
+    auto fl = std::make_shared<EstInflight>();
+    fl->b = T.b;
+    T.b = nullptr;
+    for (int k = 0; k < n; k++) fl->n_marg += T.dm[k] ? 1 : 0;
+    for (int k = 0; k < n; k++) {
+        if (!T.dm[k] || T.est_rc[k] != TCV_OK) continue;
+        tcv_estimator *e = T.es[k];
+        if (T.defer) { e->pend = fl; e->pend_k = k; e->pend_flag = e->marg_flag; const int pn = tcv_marg_layout_n(fl->b, k); if (pn >= 0) e->stats.prior_n = pn; }      // (the new prior's n is part of the attached problem's layout)
+        else { e->prev = fl; e->prev_k = k; }
+    }
+}
+// the frame's problems have been read for the last time: destroyed on a worker thread, behind the caller's back
+void retire_problems(tcv_opt_ticket &T) {
+    auto dead = std::make_shared<std::vector<tcv_problem *>>();
+    dead->reserve(2 * T.P.size());
+    for (size_t k = 0; k < T.P.size(); k++) { if (T.P[k]) dead->push_back(T.P[k]); if (T.M[k]) dead->push_back(T.M[k]); T.P[k] = T.M[k] = nullptr; }
+    tcv::async_run([dead] { for (tcv_problem *q : *dead) tcv_problem_destroy(q); });
+}
+// double2vector's host half, the statistics and the prior chaining of every window that did not fail
+int apply_windows(tcv_opt_ticket &T) {
+    for (int k = 0; k < T.n(); k++) {
+        tcv_estimator *e = T.es[k];
+        e->opt_failed = TCV_OK;
+        if (T.est_rc[k] != TCV_OK) {      // this estimator's window failed numerically: nothing is applied, finish_frame reports it
+            e->opt_failed = T.est_rc[k]; e->opt_msg = T.est_msg; e->phase = 2;
+            continue;
+        }
+        apply_states(e);
+        if (e->tap.on && e->tap.have) {
+            WindowTap &tap = e->tap;
+            tap.pose_out.assign(e->para_pose, e->para_pose + (W + 1) * 7); tap.sb_out.assign(e->para_sb, e->para_sb + (W + 1) * 9);
+            tap.ex_out.assign(e->para_ex, e->para_ex + 7); tap.feat_out = e->para_feature;
+            tap.iterations = T.sum[k].num_iterations; tap.final_cost = T.sum[k].final_cost; tap.applied = 1;
+        }
+        e->stats.marg_flag = e->marg_flag; e->stats.n_landmarks = (int)e->sel.size(); e->stats.n_proj = (int)e->w_pi.size(); e->stats.n_line = (int)e->w_lf.size();
+        e->stats.n_line_obs = e->n_line_obs_total; e->stats.iterations = T.sum[k].num_iterations; e->stats.termination = T.sum[k].termination; e->stats.final_cost = T.sum[k].final_cost;
+        if (!T.dm[k]) e->stats.prior_n = e->prior ? e->stats.prior_n : 0;
+        else if (!T.defer) {      // (deferred: the new prior is taken at the start of the next frame; stats.prior_n was set with the hand-over)
+            const int rc = take_prior(e, T.newp[k], e->marg_flag);
+            if (rc != TCV_OK) return rc;      // (take_prior keeps the old prior on failure: the ticket releases the new one and the ones not handed over yet)
+            T.newp[k] = nullptr;
+        }
+        e->phase = 2;
+    }
+    return TCV_OK;
 }
 
+int optimize_end(tcv_opt_ticket &T) {
+    static const bool dbg = getenv("TCV_DEBUG_EST") != nullptr;      // developer: where the "downloads" lap goes
+    T.lap.mark_cpu();
+    wait_for_states(T);
+    T.lap.add(4);
+    const double td0 = now_s();
+    if (T.host_priors) download_to_host(T);
+    const double td1 = now_s();
+    judge_windows(T);
+    if (T.host_priors) take_host_priors(T); else hand_over_batch(T);
+    const double td2 = now_s();
+    if (T.b) { tcv_batch_destroy(T.b); T.b = nullptr; }
+    const double td3 = now_s();
+    retire_problems(T);
+    if (dbg) fprintf(stderr, "[est] n %d: states %.3f ms, priors %.3f ms, batch destroy %.3f ms, problems destroy %.3f ms\n", T.n(),
+                     1e3 * (td1 - td0), 1e3 * (td2 - td1), 1e3 * (td3 - td2), 1e3 * (now_s() - td3));
+    T.lap.add(5);
+    if (T.rc != TCV_OK) return T.rc;      // (nothing is applied; the ticket releases the priors it still holds)
+    T.rc = apply_windows(T);
+    T.lap.add(6);
+    return T.rc;
+}
+}  // namespace
 
 // The frame in two calls, for callers that overlap the host side of one group of estimators with the device side of another (bench.py --mode
 // replay: every host thread alternates between two halves of its streams): _begin returns when the frame's last command is on the device,
@@ -1305,18 +1272,17 @@ static int optimize_end(OptRun &R) {
 // must not be touched; the ticket is consumed by _end (also on failure).
 extern "C" int tcv_estimators_optimize_begin(tcv_estimator *const *es, int n, tcv_opt_ticket **out) {
     if (!es || n <= 0 || !out) return TCV_ERR_INVALID;
-    OptRun *R = new OptRun();
-    R->esv.assign(es, es + n); R->n = n;
-    const int rc = optimize_begin(*R);
-    if (rc != TCV_OK) { delete R; *out = nullptr; return rc; }
-    *out = reinterpret_cast<tcv_opt_ticket *>(R);
-    return TCV_OK;
+    tcv_opt_ticket *T = new tcv_opt_ticket();
+    T->es.assign(es, es + n);
+    const int rc = optimize_begin(*T);
+    if (rc != TCV_OK) { delete T; T = nullptr; }
+    *out = T;
+    return rc;
 }
-extern "C" int tcv_estimators_optimize_end(tcv_opt_ticket *t) {
-    if (!t) return TCV_ERR_INVALID;
-    OptRun *R = reinterpret_cast<OptRun *>(t);
-    const int rc = optimize_end(*R);
-    delete R;
+extern "C" int tcv_estimators_optimize_end(tcv_opt_ticket *T) {
+    if (!T) return TCV_ERR_INVALID;
+    const int rc = optimize_end(*T);
+    delete T;
     return rc;
 }
 extern "C" int tcv_estimators_optimize(tcv_estimator *const *es, int n) {
@@ -1345,14 +1311,10 @@ extern "C" int tcv_estimator_finish_frame(tcv_estimator *e, double P[3], double 
 extern "C" int tcv_estimators_finish_frames(tcv_estimator *const *es, int n, double *P, double *q, double *V, int *rc, tcv_estimator_stats *stats) {
     if (!es || n <= 0 || !P || !q || !V || !rc) return TCV_ERR_INVALID;
     for (int i = 0; i < n; i++) for (int j = 0; j < i; j++) if (es[i] == es[j]) { tcv::set_error("estimators_finish_frames: the same estimator twice"); return TCV_ERR_INVALID; }
-    std::vector<std::string> msgs(n);
-    for_each_estimator(n, [&](int i) {
+    return first_failure(for_each_estimator_rc(n, [&](int i) {
         if (stats && es[i]) stats[i] = es[i]->stats;
-        rc[i] = tcv_estimator_finish_frame(es[i], P + 3 * i, q + 4 * i, V + 3 * i);
-        if (rc[i] != TCV_OK) msgs[i] = tcv_last_error();      // (the text is per thread)
-    });
-    for (int i = 0; i < n; i++) if (rc[i] != TCV_OK) { tcv::set_error(msgs[i]); return rc[i]; }
-    return TCV_OK;
+        return tcv_estimator_finish_frame(es[i], P + 3 * i, q + 4 * i, V + 3 * i);
+    }), rc);
 }
 extern "C" int tcv_estimator_set_window_tap(tcv_estimator *e, int on) {
     if (!e) return TCV_ERR_INVALID;

@@ -419,10 +419,16 @@ def test_deferred_marginalisation_is_launched_by_whichever_group_comes_back_firs
         assert np.array_equal(a, b) and np.array_equal(a, c)
 
 
-def test_two_frames_in_flight_on_one_host_thread(gpu):
+@pytest.mark.parametrize("defer", [None, "1"])
+def test_two_frames_in_flight_on_one_host_thread(gpu, monkeypatch, defer):
     """tcv_estimators_optimize_begin / _end with the calling thread's two library streams (tcv_thread_stream_slot): a thread that alternates
     between two groups of estimators -- the second group's frame begun before the first one's is collected -- gets the results of the plain
-    begin-and-collect loop, bit for bit (same batches; only what overlaps on the device and the host differs)."""
+    begin-and-collect loop, bit for bit (same batches; only what overlaps on the device and the host differs).  Two windows per ticket launch
+    their marginalisation eagerly; TCV_EST_MARG_DEFER=1 hands every ticket's batch over to the estimators' next frame instead."""
+    if defer is None:
+        monkeypatch.delenv("TCV_EST_MARG_DEFER", raising=False)
+    else:
+        monkeypatch.setenv("TCV_EST_MARG_DEFER", defer)
     streams = [replay.simulate_stream(90 + s, 40, max_features=30) for s in range(4)]
 
     def run(pipelined):
