@@ -211,8 +211,19 @@ int tcv_problem_plan_stats(const tcv_problem *p, int *out16);
  * its header (as ints) followed by the int pool; *len = number of ints (out may be NULL or too small: only *len is set then).
  * tcv_set_packer_reference(1): plans are built by the generic gather-program builder without any cache -- the reference the fast
  * builder is compared with int by int (tests/test_pack_cpu.py).  tcv_plan_cache_stats: out4 = { whole-plan cache hits, misses,
- * camera-half cache hits, misses } since the process started. */
+ * camera-half cache hits, misses } since the process started.
+ * tcv_problem_marg_plan: one window through the marginalisation packer (what tcv_batch_create / tcv_marginalize upload for it) -- ints =
+ * its header (as ints) followed by the int pool, doubles = its double pool; lengths and short buffers as above.  solve_problem (may be
+ * NULL): the window's solve problem, packed like tcv_problem_plan_ints packs it, so that the plan refers to its state and data pool.
+ * A marginalisation that keeps nothing: TCV_OK with both lengths 0.
+ * tcv_marg_lds_layout: the host's copy of the marginalisation kernel's LDS carve for a window of pos = m + n tangent dims and nx state
+ * doubles whose coupling buffer C (row stride cb_stride) lies at cb_off (< 0: none); out7 = { doubles of region P, of region R2, of C
+ * inside R2, the offset C may take in P (-1: no room), the one behind the staging records of R2, total doubles, 1 if such a window
+ * runs in one piece }. */
 int tcv_problem_plan_ints(const tcv_problem *p, int *out, int cap, int *len);
+int tcv_problem_marg_plan(const tcv_problem *marg_problem, double *const *drop, int num_drop, const tcv_problem *solve_problem,
+                          int *ints, int ints_cap, int *ints_len, double *doubles, int doubles_cap, int *doubles_len);
+int tcv_marg_lds_layout(int pos, int m, int n, int nx, int cb_off, int cb_stride, int *out7);
 int tcv_set_packer_reference(int on);
 int tcv_plan_cache_stats(long long *out4);
 /* the packing pass of tcv_batch_create (plans and data sizes of n problems on `threads` of the library's host worker threads, chunked

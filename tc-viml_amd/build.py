@@ -12,8 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libtcv_hip.so")
-SOURCES = ["tcv_capi.hip", "tcv_solve.hip", "tcv_marg.hip", "tcv_eval.hip", "tcv_preint.hip", "tcv_gauge.hip", "tcv_lines.hip", "tcv_microbench.hip", "tcv_pack.cpp", "tcv_hostpool.cpp", "tcv_estimator.cpp"]
-HEADERS = ["tcv_math.h", "tcv_gauge.h", "tcv_factors.h", "tcv_packed.h", "tcv_host.h", "tcv_hostpool.h", "tcv_dev.h", "tcv_eval.h", os.path.join("..", "..", "include", "tcv.h"), os.path.join("..", "..", "include", "tcv_estimator.h")]
+SOURCES = ["tcv_capi.hip", "tcv_solve.hip", "tcv_marg.hip", "tcv_eval.hip", "tcv_preint.hip", "tcv_gauge.hip", "tcv_lines.hip", "tcv_microbench.hip", "tcv_marg_host.cpp", "tcv_pack.cpp", "tcv_hostpool.cpp", "tcv_estimator.cpp"]
+HEADERS = ["tcv_math.h", "tcv_gauge.h", "tcv_factors.h", "tcv_packed.h", "tcv_host.h", "tcv_hostpool.h", "tcv_dev.h", "tcv_eval.h", "tcv_marg.h", os.path.join("..", "..", "include", "tcv.h"), os.path.join("..", "..", "include", "tcv_estimator.h")]
 
 
 def _stale() -> bool:
@@ -77,8 +77,6 @@ def _compile(out: str, verbose: bool, extra, opt: str = "-O3", link_extra=()) ->
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     base = [hipcc, "--offload-arch=gfx950", opt, "-std=c++17", "-fPIC", "-ffp-contract=on",
             "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value", "-Wno-unused-result", "-Wno-option-ignored", "-x", "hip"]
-    if os.path.exists(os.path.join(CSRC, "tcv_marg.hip")):
-        base.append("-DTCV_HAVE_MARG=1")
     if verbose:
         base.append("-Rpass-analysis=kernel-resource-usage")
     base += list(extra)

@@ -61,7 +61,6 @@ static bool coop_admit(tcv_batch *b, int groups, int wg) {
     return true;
 }
 static int g_coop_helpers = -1;    // cooperative mode of small batches: -1 automatic, 0 off, h >= 1: h helper workgroups per window (when the batch allows it)
-extern "C" int tcv_launch_marg(const void *args, int grid, size_t lds_bytes, void *stream);
 
 namespace tcv {
 static thread_local std::string g_err;
@@ -506,6 +505,23 @@ extern "C" int tcv_problem_plan_ints(const tcv_problem *p, int *out, int cap, in
     const int nh = (int)(sizeof(PlanHdr) / sizeof(int));
     *len = nh + (int)pints.size();
     if (out && cap >= *len) { std::memcpy(out, &pk.hdr, sizeof(PlanHdr)); std::memcpy(out + nh, pints.data(), sizeof(int) * pints.size()); }
+    return TCV_OK;
+}
+// the same for the marginalisation packer (tests/test_marg_pack_cpu.py): [MargHdr as ints | int pool] and the double pool of one window
+extern "C" int tcv_problem_marg_plan(const tcv_problem *mp, double *const *drop, int num_drop, const tcv_problem *solve_p,
+                                     int *ints, int ints_cap, int *ints_len, double *doubles, int doubles_cap, int *doubles_len) {
+    if (!mp || !ints_len || !doubles_len || num_drop < 0 || (num_drop > 0 && !drop)) return TCV_ERR_INVALID;
+    Packed pk;
+    if (solve_p) {
+        const char *ec = getenv("TCV_PLAN_COOP");
+        if (const int rc = pack_problem(*solve_p, pk, nullptr, g_solver_variant, 0, true, ec ? atoi(ec) : 0)) return rc;
+    }
+    std::vector<int> I;
+    std::vector<double> D;
+    if (const int rc = tcv_marg_plan(*mp, drop, num_drop, solve_p, solve_p ? &pk : nullptr, I, D)) return rc;
+    *ints_len = (int)I.size(); *doubles_len = (int)D.size();
+    if (ints && ints_cap >= *ints_len && !I.empty()) std::memcpy(ints, I.data(), sizeof(int) * I.size());
+    if (doubles && doubles_cap >= *doubles_len && !D.empty()) std::memcpy(doubles, D.data(), sizeof(double) * D.size());
     return TCV_OK;
 }
 extern "C" int tcv_set_packer_reference(int on) { tcv::set_pack_reference(on); return TCV_OK; }

@@ -28,7 +28,7 @@ namespace tcv {
 hipStream_t util_stream(); hipStream_t aux_stream();      // (tcv_capi.hip: the calling thread's utility stream and its second stream)
 void set_error(const std::string &s);
 }
-int tcv_marg_layout_n(const tcv_batch *b, int window);      // (tcv_marg.hip: n of the prior a window's attached marginalisation problem makes, known before the kernel runs)
+int tcv_marg_layout_n(const tcv_batch *b, int window);      // (tcv_marg_host.cpp: n of the prior a window's attached marginalisation problem makes, known before the kernel runs)
 
 namespace {
 

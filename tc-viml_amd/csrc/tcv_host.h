@@ -43,7 +43,7 @@ struct tcv_prior {
     // device-resident form (tcv_batch_get_priors_device): J0 | r0 | the marginalisation problem's state vector stay in the producing
     // batch's result buffer; `host` says whether x0 / J0 / r0 above have been materialised (tcv_prior_host)
     std::shared_ptr<tcv::DevBlob> dev;
-    const double *d_block = nullptr;  // this window's result block in that buffer (layout: tcv_marg.hip MARG_OUT_*)
+    const double *d_block = nullptr;  // this window's result block in that buffer (layout: tcv_marg.h MARG_OUT_*)
     int k0 = 0;                       // leading rows of J0 | r0 that are exact zeros (tcv_packed.h prior_zero_rows, computed on the device)
                                       // -1: not known on the host (tcv_batch_get_priors_device_async: the marginalisation may still be running) --
     const int *d_k0 = nullptr;        //     the consumer reads it on the device, behind the producer's event (dev->ready): [status | k0] of this window
@@ -214,7 +214,7 @@ struct tcv_batch {
     int *d_coop_ctl = nullptr;
     double *d_coop_x = nullptr, *d_coop_exp = nullptr;
     // marginalisation
-    void *marg = nullptr;                 // tcv_marg.hip state
+    void *marg = nullptr;                 // tcv_marg_host.cpp MargState
     void (*marg_free)(tcv_batch *) = nullptr;
     // evaluation (tcv_batch_evaluate)
     void *eval = nullptr;                 // tcv_capi.hip EvalState: owner lists, staging and output buffers, made at the first evaluation
@@ -235,10 +235,14 @@ int tcv_marg_get_priors_device(tcv_batch *b, tcv_prior **out, int n, bool nowait
 int tcv_marg_status_prefetch(tcv_batch *b, void *stream);
 bool tcv_marg_has_problem(const tcv_batch *b, int window);      // false: marg_problems[window] was NULL
 int tcv_marg_layout_n(const tcv_batch *b, int window);          // n of the prior this window's marginalisation makes (known from the attached problem, before the kernel runs); -1: none
+// host only (tcv_problem_marg_plan): one window through the marginalisation packer -- ints = [MargHdr as ints | int pool], doubles = the
+// double pool; both empty when the marginalisation keeps nothing
+int tcv_marg_plan(const tcv_problem &p, double *const *drop, int ndrop, const tcv_problem *solve_p, const tcv::Packed *solve_pk,
+                  std::vector<int> &ints, std::vector<double> &doubles);
 // copies device-resident priors into a batch's data pool (one job per window that holds one): launched by tcv_batch_create on the stream
 // of its upload, behind it
 namespace tcv {
-// kind 0: a prior (src = the result block of its window, tcv_marg.hip MARG_OUT_*); kind 1: an IMU factor's constants (src = the
+// kind 0: a prior (src = the result block of its window, tcv_marg.h MARG_OUT_*); kind 1: an IMU factor's constants (src = the
 // pre-integration kernel's output record; n, k0, nblk unused)
 struct PriorSplice {
     const double *src; long long dst; int n, k0, nblk, kind; int goff[32], size[32];

@@ -20,82 +20,11 @@
 // order they were added to the problem, then kept blocks in that order.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <thread>
-#include <string>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
 #include "tcv_factors.h"
-#include "tcv_host.h"
+#include "tcv_marg.h"
 #include "tcv_dev.h"
 
 namespace tcv {
-
-enum { MARG_MAX_M = 64, MARG_MAX_N = 80, MARG_MAX_POS = MARG_MAX_M + MARG_MAX_N, MARG_MAX_X = 1408 };
-// Two launch shapes of the one kernel: 512 threads per window and one workgroup per CU (few windows: shortest time per window), or
-// 256 threads per window and two workgroups per CU when every window of the batch fits 80 KB of LDS (many windows: the barrier and
-// LDS round trips of one window hide behind the other's arithmetic).
-enum { MARG_SM_DOUBLES = 720 };
-enum { MARG_NT_WIDE = 512, MARG_NT_PAIR = 256, MARG_SM = MARG_SM_DOUBLES, MARG_STAGE = 64 * 43, MARG_CB_LM = 16 };
-// per-window result block: [J0 | r0 | x (linearisation point) + 64 diagnostics] is what a caller needs (MARG_OUT_COMPACT doubles, the
-// part tcv_batch_download_priors_compact copies); A', b' (parity / debug surface) follow
-enum { MARG_OUT_J0 = 0, MARG_OUT_R0 = 6400, MARG_OUT_X = 6480, MARG_OUT_COMPACT = 6480 + 1408 + 64, MARG_OUT_AS = MARG_OUT_COMPACT, MARG_OUT_BS = MARG_OUT_AS + 6400,
-       MARG_OUT_STRIDE = MARG_OUT_BS + 80 };
-// per-workgroup scratch in HBM (L2-resident): Z = diag(sqrt(lam^+)) V' Amr, its right-hand side, and the eigenvector matrix of the
-// Jacobi safety net for A' (the LDS holds one n x n matrix, not two)
-enum { MARG_SCR_Z = 0, MARG_SCR_PR = MARG_MAX_M * MARG_MAX_N, MARG_SCR_V = MARG_SCR_PR + 256, MARG_SCR_STRIDE = MARG_SCR_V + (MARG_MAX_N + 1) * (MARG_MAX_N + 2) };
-
-struct MargHdr {
-    int nblk, pos, m, n, nx;
-    int n_imu, n_proj, prior_n, prior_nblk, prior_xsize;
-    int o_blk;     // nblk x 5: gsize, goff, mloc (-1 constant), kind, xsrc (offset in the solve state, -1 none)
-    int o_imu;     // n_imu x 4
-    int o_proj;    // n_proj x 4
-    int o_prior;   // prior_nblk x 4: blk, idx, gsize, x0 offset
-    int o_pcol;    // prior_n: mloc index of every J0 column (-1 constant)
-    int d_x, d_imu, d_proj, d_prior, d_misc;
-    long long ibase, dbase;
-    int prior_k0, pad_k0;  // leading zero rows of the prior's J0 | r0 that are not stored (WinHdr::prior_k0, tcv_packed.h)
-    long long prior_abs;   // >= 0: J0 | r0 | x0 of the prior are read from the solve batch's data pool at this offset (the marginalised factor
-                           // set holds the same prior object as the solve problem: no second copy is packed or uploaded)
-    int solve_window;
-    long long imu_abs;     // >= 0: the (single) IMU factor's 287 constants are read from the solve batch's data pool at this offset (the
-                           // factor is one of the solve problem's: no second copy is packed, uploaded or spliced)
-    int block_mode;   // 1: the marginalised inverse depths (1 x 1 blocks) are eliminated by scalar pivots while the factors are
-                      // accumulated, only the frame part of the dropped set (m) goes through the eigen pseudo-inverse
-    int o_plast;      // block mode: n_proj flags, 1 = last factor of its landmark (factors sorted by landmark)
-    // block mode, chunked path (proj_disjoint, no Td): the factors come in chunks of whole landmarks (<= 64 factors, <= MARG_CB_LM eliminated
-    // landmarks); per chunk the landmarks' couplings C (landmark x camera column), diagonals and gradients are accumulated next to the
-    // camera-camera J'J, and A -= C diag(1/hll) C', b -= C diag(1/hll) gl is ONE rank-16 update on the matrix cores
-    int n_pchunk, o_pchunk;   // n_pchunk x 4: first factor, factors, eliminated landmarks, offset of the chunk's group table behind o_pgrp
-    int o_plm;                // n_proj: index of the factor's landmark among the chunk's eliminated landmarks (-1: its landmark is a regular column)
-    int o_pgrp, pad_pgrp;     // per chunk: [frames nfr | landmark runs nlg | 1 if every factor shares its first pose and its extrinsic block | length |
-                              //  (first, count) x nfr into the list at the end | (first factor, count) x nlg | the chunk's factors grouped by their
-                              //  second pose, factor order inside a group]: the task decomposition of the accumulation (marg_kernel)
-    int cb_off, cb_stride;    // LDS offset (doubles) and row stride of C: [MARG_CB_LM x cb_stride | hll MARG_CB_LM | gl MARG_CB_LM]; cb_off < 0: old path
-    int td_blk;       // >= 0: the point factors are ProjectionTdFactors on this block (d_proj then holds 14 doubles per factor)
-    int sqrt_src;        // >= 0: index of the (single) IMU factor among the solve problem's IMU factors: its sqrt_info was computed by the solve
-    int proj_disjoint;   // 1: no block is the frame-i pose of one point factor and the frame-j pose of another (MARGIN_OLD: every factor is
-                         // anchored in the dropped frame), so one thread can own one entry of the 19 x 20 record across all factors of a chunk
-};
-
-struct MargArgs {
-    const MargHdr *hdr;
-    const int *ipool;
-    const double *dpool;
-    const double *solve_state;   // may be null
-    const double *solve_sqrt;    // may be null: per window 225 doubles, the solve's sqrt_info of IMU factor sqrt_src
-    const double *solve_dpool;   // the solve batch's data pool (MargHdr::prior_abs)
-    const void *solve_win;       // its window headers (WinHdr): prior_k0 of a prior whose zero-row count was only known on the device (MargHdr::prior_k0 < 0)
-    double *out;                 // per window MARG_OUT_STRIDE
-    int *out_status;             // per window: 0 ok
-    double *scratch;             // per workgroup MARG_SCR_STRIDE
-    int nwin, state_stride, use_solved_state;
-    int eig_mm;                  // 1: Amm^+ through the eigen-decomposition for every window (TCV_MARG_EIG_MM=1: A/B checks)
-    int eig_flags;               // developer A/B switches of the eigen-solver of A' (TCV_MARG_EIG_FLAGS): 1 = round 2's eigenvalue search (every eigenvalue, 4- / 7-section), 2 = reflector-by-reflector back-transformation on the VALU
-};
 
 __device__ __forceinline__ int pidx(int a, int b) { return a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a; }
 
@@ -939,9 +868,9 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag
 }
 
 #ifdef TCV_PROFILE
-#define MARG_MARK(id) do { const long long t_ = clock64(); if (tid == 0) out[MARG_OUT_X + MARG_MAX_X + 2 + (id)] += (double)(t_ - t_last); t_last = t_; } while (0)
+#define MARG_MARK(id) do { const long long t_ = clock64(); if (tid == 0) out[MARG_DIAG_PHASE + (id)] += (double)(t_ - t_last); t_last = t_; } while (0)
 // parts of the projection phase on the chunked block path (slots 44..47: - | evaluation and chunk set-up | accumulation | landmark elimination)
-#define MARG_SUB(id) do { const long long t_ = clock64(); if (tid == 0) out[MARG_OUT_X + MARG_MAX_X + 44 + (id)] += (double)(t_ - t_sub); t_sub = t_; } while (0)
+#define MARG_SUB(id) do { const long long t_ = clock64(); if (tid == 0) out[MARG_DIAG_PROJ_SUB + (id)] += (double)(t_ - t_sub); t_sub = t_; } while (0)
 #else
 #define MARG_MARK(id) do { } while (0)
 #define MARG_SUB(id) do { } while (0)
@@ -1028,7 +957,7 @@ __global__ void __launch_bounds__(MARG_NT) __attribute__((disable_tail_calls)) _
             continue;
         }
         const int npk = pos * (pos + 1) / 2;
-        // LDS carve (marg_lds_doubles() on the host is the same sum).  P: the prior's J0 while J0'J0 is formed, then the packed lower
+        // LDS carve (marg_lds_layout() in tcv_marg_host.cpp is the host's copy of this arithmetic: change the two together).  P: the prior's J0 while J0'J0 is formed, then the packed lower
         // triangle of A, then A' and finally its eigenvectors V2.  R2: the factor staging records, then Amm + V, then the reflectors of
         // the tridiagonalisation of A'.
         lds_d *Apk = lds;
@@ -1048,7 +977,7 @@ __global__ void __launch_bounds__(MARG_NT) __attribute__((disable_tail_calls)) _
         lds_i *cnt = (lds_i *)(rot + 158);
         gbl_d *out = (gbl_d *)Aarg.out + (size_t)win * MARG_OUT_STRIDE;
         long long t_last = clock64();
-        if (tid == 0) for (int i = 0; i < 12; i++) out[MARG_OUT_X + MARG_MAX_X + 2 + i] = 0.0;
+        if (tid == 0) for (int i = 0; i < 12; i++) out[MARG_DIAG_PHASE + i] = 0.0;
 
         cst_i *blk = ip + H.o_blk;
         for (int b = tid; b < H.nblk; b += MARG_NT) {
@@ -1261,7 +1190,7 @@ __global__ void __launch_bounds__(MARG_NT) __attribute__((disable_tail_calls)) _
         const bool cb_path = H.block_mode && H.cb_off >= 0;
 #ifdef TCV_PROFILE
         long long t_sub = clock64();
-        if (tid == 0) for (int i = 0; i < 4; i++) out[MARG_OUT_X + MARG_MAX_X + 44 + i] = 0.0;
+        if (tid == 0) for (int i = 0; i < 4; i++) out[MARG_DIAG_PROJ_SUB + i] = 0.0;
 #endif
         MARG_SUB(0);
         // chunked block path: tables in the eigen-solver's vector area (idle until the eigen-decomposition): the current chunk's group table,
@@ -1625,7 +1554,7 @@ __global__ void __launch_bounds__(MARG_NT) __attribute__((disable_tail_calls)) _
             double tr = 0, trs = 0;
             for (int j = 0; j < m; j++) { tr += rot[j]; trs += rot[j] * Apk[pidx(j, j)]; }
             chol = tr < 1e8;                                    // lambda_min >= 1 / tr > 1e-8 (false for NaN)
-            if (tid == 0) { out[MARG_OUT_X + MARG_MAX_X + 40] = tr; out[MARG_OUT_X + MARG_MAX_X + 41] = trs; }
+            if (tid == 0) { out[MARG_DIAG_AMM_TRACE] = tr; out[MARG_DIAG_AMM_TRACE + 1] = trs; }
         } else
         if (chol) {
             // forward substitutions L z = rhs, one thread per right-hand side: the n columns of Amr, bmm, and the m unit vectors whose
@@ -1662,7 +1591,7 @@ __global__ void __launch_bounds__(MARG_NT) __attribute__((disable_tail_calls)) _
             double tr = 0, trs = 0;
             for (int j = 0; j < m; j++) { tr += rot[j]; trs += rot[j] * Apk[pidx(j, j)]; }
             chol = tr < 1e8;                                    // lambda_min >= 1 / tr > 1e-8 (false for NaN)
-            if (tid == 0) { out[MARG_OUT_X + MARG_MAX_X + 40] = tr; out[MARG_OUT_X + MARG_MAX_X + 41] = trs; }
+            if (tid == 0) { out[MARG_DIAG_AMM_TRACE] = tr; out[MARG_DIAG_AMM_TRACE + 1] = trs; }
         }
         int sweeps1 = 0;
         const int ldn = ne + 1;
@@ -1759,14 +1688,14 @@ __global__ void __launch_bounds__(MARG_NT) __attribute__((disable_tail_calls)) _
         // over the diagonalised A' at the end: the LDS holds one n x n matrix)
         int sweeps2 = 0;
         {
-            const bool ok = sym_eig_tridiag<MARG_NT>(As, R2, sm, rot, n, ldn, tid, out + MARG_OUT_X + MARG_MAX_X + 14, Aarg.eig_flags);    // rot: 160 doubles >= n eigenvalues
+            const bool ok = sym_eig_tridiag<MARG_NT>(As, R2, sm, rot, n, ldn, tid, out + MARG_DIAG_EIG_CHECK, Aarg.eig_flags);    // rot: 160 doubles >= n eigenvalues
             if (ok) {
                 if (tid < n) lam[tid] = rot[tid];
             } else {
                 gbl_d *Vg = scr + MARG_SCR_V;
                 for (int e = tid; e < n * n; e += MARG_NT) { const int i2 = e / n, j2 = e - i2 * n; As[i2 * ldn + j2] = out[MARG_OUT_AS + i2 * n + j2]; }
                 __syncthreads();
-                sweeps2 = 100 + jacobi_eig<MARG_NT, gbl_d>(As, Vg, n, ldn, rot, cnt, tid, 2.3e-16, out + MARG_OUT_X + MARG_MAX_X + 2 + 9);
+                sweeps2 = 100 + jacobi_eig<MARG_NT, gbl_d>(As, Vg, n, ldn, rot, cnt, tid, 2.3e-16, out + MARG_DIAG_PHASE + 9);
                 if (tid < n) lam[tid] = As[tid * ldn + tid];
                 __syncthreads();
                 for (int e = tid; e < n * n; e += MARG_NT) { const int i2 = e / n, j2 = e - i2 * n; V2[i2 * ldn + j2] = Vg[i2 * ldn + j2]; }
@@ -1809,314 +1738,21 @@ __global__ void __launch_bounds__(MARG_NT) __attribute__((disable_tail_calls)) _
         for (int i = tid; i < H.nx; i += MARG_NT) out[MARG_OUT_X + i] = x[i];
         MARG_MARK(8);
         if (tid == 0) ((gbl_i *)Aarg.out_status)[win] = (sweeps1 >= 24 || sweeps2 == 124) ? 1 : (sweeps2 >= 100 ? 2 : 0);   // 1: a Jacobi sweep hit its cap, 2: A' went through the Jacobi safety net
-        if (tid == 0) { out[MARG_OUT_X + MARG_MAX_X] = sweeps1; out[MARG_OUT_X + MARG_MAX_X + 1] = sweeps2; }
+        if (tid == 0) { out[MARG_DIAG_SWEEPS_MM] = sweeps1; out[MARG_DIAG_SWEEPS_RR] = sweeps2; }
         __syncthreads();
         if (bad) ((gbl_i *)Aarg.out_status)[Aarg.nwin + win] = -1;      // (ordered behind lane 0's store by the barrier)
     }
 }
 
 // ------------------------------------------------------------------------------------------------------
-// host side
+// launchers (the host side is tcv_marg_host.cpp)
 // ------------------------------------------------------------------------------------------------------
-struct MargWindow {
-    MargHdr hdr;
-    std::vector<int> keep_block;      // marg-problem block index of every kept block (in mloc order)
-    std::vector<int> keep_size, keep_idx, keep_goff;
-    std::vector<double *> keep_addr;
-    int m_total = 0;                  // all dropped tangent dims (landmarks included), the reference's m
-    bool empty_keep = false;          // every block the factors touch is dropped (n = 0): nothing runs on the device, the result is the reference's
-                                      // empty MarginalizationInfo (marginalization_factor.cpp:174-194 with n = pos - m = 0; carried into the next frame
-                                      // by estimator.cpp:2040-2043, where its factor has no residuals and no blocks)
-};
-struct MargState {
-    std::vector<MargWindow> win;
-    void *d_input = nullptr;          // one allocation: [double pool | headers | int pool]
-    MargHdr *d_hdr = nullptr;
-    int *d_ipool = nullptr, *d_status = nullptr;      // d_status: per window [status | k0] (2 n ints): marginalisation status, leading zero rows of J0 | r0 (-1: NaN)
-    double *d_dpool = nullptr, *d_out = nullptr, *d_scratch = nullptr;
-    std::shared_ptr<DevBlob> out_blob;                // owns d_out: device-resident priors (tcv_batch_get_priors_device) keep it alive after the batch
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    size_t lds_bytes = 0;
-    int grid = 0, nt = MARG_NT_WIDE;
-    int *h_status_pre = nullptr;      // pinned: [status | k0] copied behind the kernel by tcv_marg_status_prefetch (valid once the batch's work is waited for)
-    bool status_prefetched = false;
-    bool ran = false;
-    double *h_out = nullptr;          // pinned host copy of every window's result block (tcv_batch_download_priors), valid until the next run
-    size_t h_stride = 0;              // doubles per window in h_out: MARG_OUT_STRIDE, or MARG_OUT_COMPACT (no A', b')
-    std::vector<int> h_status;
-    bool h_valid = false;
-};
-
-static void marg_free(tcv_batch *b) {
-    MargState *s = (MargState *)b->marg;
-    if (!s) return;
-    (void)tcv::dev_free(s->d_input);      // (d_hdr, d_ipool, d_dpool point into d_input; d_status lives behind d_out in the result blob)
-    s->out_blob.reset(); s->d_out = nullptr;      // (freed when the last device-resident prior that reads it is gone)
-    (void)tcv::dev_free(s->d_scratch);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    tcv::host_staging_release(s->h_out);
-    tcv::host_staging_release(s->h_status_pre);
-    delete s;
-    b->marg = nullptr;
-}
-
-// LDS doubles one window needs (the kernel's carve): [P: packed A, later A' and its eigenvectors | R2: staging records (64 x 43: a
-// ProjectionTdFactor record is 2 x 21 + 1), later Amm + V, later the packed reflectors | b | x | rot | lam | landmark row | eigen vectors]
-static size_t marg_lds_doubles(int pos, int m, int n, int nx, int cb_in_r2 = 0) {
-    const int me = m + (m & 1), ne = n + (n & 1);
-    const int r1 = std::max(pos * (pos + 1) / 2, ne * (ne + 1));
-    const int r2 = std::max(std::max((int)MARG_STAGE + cb_in_r2, me * (me + 1) + std::max(me * (me + 1), m * (n + 1))), (n - 2) * (n - 1) / 2 + 1);
-    return (size_t)((r1 + 1) & ~1) + ((r2 + 1) & ~1) + MARG_MAX_POS + ((nx + 7) & ~7) + 160 + MARG_MAX_N + MARG_MAX_POS + 8 + MARG_SM;
-}
-
-enum { MARG_PACK_EMPTY_KEEP = 1 };      // pack_marg: the marginalisation keeps nothing (MargWindow::empty_keep); not an error
-static int pack_marg(const tcv_problem &p, double *const *drop, int ndrop, const tcv_problem *solve_p, const Packed *solve_pk,
-                     MargWindow &mw, std::vector<int> &I, std::vector<double> &D) {
-    const int nb = (int)p.blocks.size();
-    if (!p.line.empty()) { set_error("line factors are not marginalised (estimator.cpp:1992 `if (0)`)"); return TCV_ERR_UNSUPPORTED; }
-    if (p.prior.size() > 1) { set_error("more than one marginalisation factor"); return TCV_ERR_UNSUPPORTED; }
-    std::vector<char> touched(nb, 0), dropped(nb, 0);
-    for (auto &f : p.imu) for (int k = 0; k < 4; k++) touched[f.b[k]] = 1;
-    for (auto &f : p.proj) { for (int k = 0; k < 4; k++) touched[f.b[k]] = 1; if (f.btd >= 0) touched[f.btd] = 1; }
-    for (auto &f : p.prior) for (int b : f.b) touched[b] = 1;
-    for (int k = 0; k < ndrop; k++) {
-        const int bd = p.index.find(drop[k]);
-        if (bd < 0) { set_error("marginalize: dropped block is not part of the problem"); return TCV_ERR_INVALID; }
-        if (touched[bd]) dropped[bd] = 1;
-    }
-    // ambient offsets and [m | n] tangent order.  MarginalizationInfo knows nothing about SetParameterBlockConstant: a constant block
-    // (para_Ex_Pose with ESTIMATE_EXTRINSIC = 0, estimator.cpp:1694-1698) is kept / dropped like any other and its Jacobian columns are
-    // accumulated (marginalization_factor.cpp:89-108, :176-194), so the prior of the shipped EuRoC configuration has n = 75 too.
-    std::vector<int> id_of(nb, -1), gsize, goff, mloc, kind, xsrc, orig;
-    int nx = 0;
-    for (int b = 0; b < nb; b++) {
-        if (!touched[b]) continue;
-        id_of[b] = (int)gsize.size();
-        gsize.push_back(p.blocks[b].size); goff.push_back(nx); kind.push_back(p.blocks[b].kind); mloc.push_back(-1); xsrc.push_back(-1);
-        orig.push_back(b);
-        nx += p.blocks[b].size;
-    }
-    const int nblk = (int)gsize.size();
-    // marginalised inverse depths: size-1 blocks that only ever appear as 4th block of projection factors.  When the dropped
-    // set is too large for the LDS-resident eigen-solver (a 150-feature front end anchors far more than 49 landmarks in the
-    // oldest frame) they are eliminated by scalar pivots (block mode) and only the frame part goes through the eigen step.
-    std::vector<char> is_lm(nb, 0), other_use(nb, 0);
-    for (auto &f : p.proj) { is_lm[f.b[3]] = 1; for (int k = 0; k < 3; k++) other_use[f.b[k]] = 1; if (f.btd >= 0) other_use[f.btd] = 1; }
-    for (auto &f : p.imu) for (int k = 0; k < 4; k++) other_use[f.b[k]] = 1;
-    for (auto &f : p.prior) for (int b : f.b) other_use[b] = 1;
-    int m_all = 0, n_lm_drop = 0;
-    for (int c = 0; c < nblk; c++) {
-        const ParamBlock &pb = p.blocks[orig[c]];
-        if (dropped[orig[c]]) {
-            m_all += pb.kind == KIND_POSE ? 6 : pb.size;
-            if (is_lm[orig[c]] && !other_use[orig[c]] && pb.size == 1) n_lm_drop++;
-        }
-    }
-    int n_all = 0;
-    for (int c = 0; c < nblk; c++) {
-        const ParamBlock &pb = p.blocks[orig[c]];
-        if (!dropped[orig[c]]) n_all += pb.kind == KIND_POSE ? 6 : pb.size;
-    }
-    // one-piece eigen-decomposition of A_mm (the reference's) whenever it fits the LDS, block mode otherwise
-    const bool fits = m_all <= MARG_MAX_M && n_all <= MARG_MAX_N && marg_lds_doubles(m_all + n_all, m_all, n_all, nx) <= (size_t)LDS_DOUBLES;
-    const bool block_mode = !fits && n_lm_drop > 0;
-    int pos = 0;
-    std::vector<int> lm_id(nb, -1);
-    int n_lm = 0;
-    for (int c = 0; c < nblk; c++) {
-        const ParamBlock &pb = p.blocks[orig[c]];
-        if (dropped[orig[c]]) {
-            if (block_mode && is_lm[orig[c]] && !other_use[orig[c]] && pb.size == 1) { lm_id[orig[c]] = n_lm; mloc[c] = -2 - n_lm; n_lm++; continue; }
-            mloc[c] = pos; pos += pb.kind == KIND_POSE ? 6 : pb.size;
-        }
-    }
-    const int m = pos;
-    mw.keep_block.clear(); mw.keep_size.clear(); mw.keep_idx.clear(); mw.keep_addr.clear(); mw.keep_goff.clear();
-    for (int c = 0; c < nblk; c++) {
-        const ParamBlock &pb = p.blocks[orig[c]];
-        if (dropped[orig[c]]) continue;
-        mloc[c] = pos;
-        mw.keep_block.push_back(c); mw.keep_size.push_back(pb.size); mw.keep_idx.push_back(pos); mw.keep_addr.push_back(pb.addr);
-        mw.keep_goff.push_back(goff[c]);
-        pos += pb.kind == KIND_POSE ? 6 : pb.size;
-    }
-    const int n = pos - m;
-    // nothing kept -- every touched block is dropped, or the problem holds no factor at all (frame 0 without a prior, its IMU factor left out,
-    // nothing anchored in it): the reference's marginalize() runs with n = 0 (and m = 0 in the second case) and leaves an empty MarginalizationInfo
-    if (n < 1) { mw.m_total = m_all; mw.empty_keep = true; return MARG_PACK_EMPTY_KEEP; }      // (the caller writes a header the kernel skips)
-    if (m_all < 1) { set_error("marginalize: none of the dropped blocks is touched by a factor (m = 0, n > 0: the kernel has no path without a dropped block)"); return TCV_ERR_INVALID; }
-    if (block_mode && m < 1) { set_error("marginalize: block mode needs a non-landmark block in the dropped set"); return TCV_ERR_UNSUPPORTED; }
-    mw.m_total = m_all;
-    if (m > MARG_MAX_M || n > MARG_MAX_N || nx > MARG_MAX_X || p.imu.size() > 16) {
-        set_error("marginalisation too large for the LDS-resident kernel (m <= 64, n <= 80)");
-        return TCV_ERR_TOO_LARGE;
-    }
-    // where the current value of each block lives in the solve's state vector
-    if (solve_p && solve_pk) {
-        std::unordered_map<double *, int> off;
-        int o = 0;
-        for (int blkid : solve_pk->cam_block) { off[solve_p->blocks[blkid].addr] = o; o += solve_p->blocks[blkid].size; }
-        for (int blkid : solve_pk->lm_block) { off[solve_p->blocks[blkid].addr] = o; o += 1; }
-        for (int c = 0; c < nblk; c++) { auto it = off.find(p.blocks[orig[c]].addr); if (it != off.end()) xsrc[c] = it->second; }
-    }
-    MargHdr &H = mw.hdr;
-    std::memset(&H, 0, sizeof H);
-    H.nblk = nblk; H.pos = pos; H.m = m; H.n = n; H.nx = nx;
-    H.n_imu = (int)p.imu.size(); H.n_proj = (int)p.proj.size();
-    H.ibase = (long long)I.size(); H.dbase = (long long)D.size();
-    const size_t i0 = I.size(), d0 = D.size();
-    auto imark = [&]() { return (int)(I.size() - i0); };
-    auto dmark = [&]() { return (int)(D.size() - d0); };
-    H.o_blk = imark();
-    for (int c = 0; c < nblk; c++) { I.push_back(gsize[c]); I.push_back(goff[c]); I.push_back(mloc[c]); I.push_back(kind[c]); I.push_back(xsrc[c]); }
-    H.o_imu = imark();
-    for (auto &f : p.imu) for (int k = 0; k < 4; k++) I.push_back(id_of[f.b[k]]);
-    H.sqrt_src = -1;
-    if (p.imu.size() == 1 && solve_p)      // the same pre-integration among the solve's factors (MARGIN_OLD: the factor between frames 0 and 1)
-        for (size_t g = 0; g < solve_p->imu.size(); g++) {
-            const bool same = p.imu[0].dev ? solve_p->imu[g].dev == p.imu[0].dev
-                                           : (!solve_p->imu[g].dev && std::memcmp(&solve_p->imu[g].pre, &p.imu[0].pre, sizeof(tcv_imu_preintegration)) == 0);
-            if (same) { H.sqrt_src = (int)g; break; }
-        }
-    std::vector<int> porder(p.proj.size());
-    for (size_t i = 0; i < porder.size(); i++) porder[i] = (int)i;
-    if (block_mode) {
-        for (auto &f : p.proj)
-            if (dropped[f.b[3]] && lm_id[f.b[3]] < 0) { set_error("marginalize: dropped inverse depth shared with a non-projection factor"); return TCV_ERR_UNSUPPORTED; }
-        std::stable_sort(porder.begin(), porder.end(), [&](int a, int b2) { return p.proj[a].b[3] < p.proj[b2].b[3]; });
-    }
-    H.block_mode = block_mode ? 1 : 0;
-    H.td_blk = -1;
-    for (size_t k = 0; k < p.proj.size(); k++) {
-        if (p.proj[k].btd != p.proj[0].btd) { set_error("projection factors must all be ProjectionTdFactors on one Td block, or none"); return TCV_ERR_UNSUPPORTED; }
-        if (p.proj[k].btd >= 0) H.td_blk = id_of[p.proj[k].btd];
-    }
-    H.o_proj = imark();
-    for (int k2 : porder) for (int k = 0; k < 4; k++) I.push_back(id_of[p.proj[k2].b[k]]);
-    {
-        std::vector<char> as_i(nb, 0), as_j(nb, 0);
-        for (auto &f : p.proj) { as_i[f.b[0]] = 1; as_j[f.b[1]] = 1; }
-        H.proj_disjoint = 1;
-        for (int c = 0; c < nb; c++) if (as_i[c] && as_j[c]) H.proj_disjoint = 0;
-        if (getenv("TCV_MARG_PROJ_SERIAL")) H.proj_disjoint = 0;      // A/B checks: the factor-by-factor accumulation
-    }
-    H.o_plast = imark();
-    for (size_t i = 0; i < porder.size(); i++)
-        I.push_back(block_mode && lm_id[p.proj[porder[i]].b[3]] >= 0 && (i + 1 == porder.size() || p.proj[porder[i + 1]].b[3] != p.proj[porder[i]].b[3]) ? 1 : 0);
-    // chunked block path: chunks of whole landmarks, the landmarks' couplings eliminated by one rank-16 update per chunk
-    H.cb_off = -1; H.cb_stride = 0; H.n_pchunk = 0; H.o_pchunk = imark(); H.o_plm = imark();
-    if (block_mode && H.proj_disjoint && H.td_blk < 0 && !getenv("TCV_MARG_BLOCK_SERIAL")) {
-        std::vector<int> chunks, plm(porder.size(), -1);
-        size_t i = 0;
-        while (i < porder.size()) {
-            const size_t c0 = i;
-            int nl = 0;
-            while (i < porder.size()) {
-                size_t j = i;      // the factors of one landmark: [i, j)
-                const int lmb = p.proj[porder[i]].b[3];
-                while (j < porder.size() && p.proj[porder[j]].b[3] == lmb) j++;
-                const bool elim = lm_id[lmb] >= 0;
-                if (i > c0 && (j - c0 > 64 || (elim && nl == MARG_CB_LM))) break;
-                if (j - c0 > 64) { j = c0 + 64; if (elim) { chunks.clear(); i = porder.size(); break; } }      // (a landmark with more than 64 factors: old path)
-                for (size_t q = i; q < j; q++) plm[q] = elim ? nl : -1;
-                if (elim) nl++;
-                i = j;
-            }
-            if (i == porder.size() && chunks.empty() && c0 != 0) break;
-            chunks.push_back((int)c0); chunks.push_back((int)(i - c0)); chunks.push_back(nl); chunks.push_back(0);
-        }
-        if (!chunks.empty() || porder.empty()) {
-            H.n_pchunk = (int)chunks.size() / 4;
-            if (getenv("TCV_DEBUG")) {
-                fprintf(stderr, "[tcv] marg plan: %d projection factors in %d chunks (factors, eliminated landmarks):", (int)porder.size(), H.n_pchunk);
-                for (size_t c = 0; c + 3 < chunks.size(); c += 4) fprintf(stderr, " (%d, %d)", chunks[c + 1], chunks[c + 2]);
-                fprintf(stderr, "\n");
-            }
-            std::vector<int> pgrp;
-            for (size_t c = 0; c + 3 < chunks.size(); c += 4) {
-                const int c0 = chunks[c], cn = chunks[c + 1];
-                chunks[c + 3] = (int)pgrp.size();
-                std::vector<int> keys;
-                std::vector<std::vector<int>> members;
-                std::vector<int> runs;
-                bool uniform = true;
-                for (int q = 0; q < cn; q++) {
-                    const ProjFac &f = p.proj[porder[c0 + q]];
-                    size_t k = 0;
-                    while (k < keys.size() && keys[k] != f.b[1]) k++;
-                    if (k == keys.size()) { keys.push_back(f.b[1]); members.emplace_back(); }
-                    members[k].push_back(q);
-                    if (q == 0 || p.proj[porder[c0 + q - 1]].b[3] != f.b[3]) { runs.push_back(q); runs.push_back(0); }
-                    runs.back()++;
-                    if (f.b[0] != p.proj[porder[c0]].b[0] || f.b[2] != p.proj[porder[c0]].b[2]) uniform = false;
-                }
-                const size_t h0 = pgrp.size();
-                pgrp.push_back((int)keys.size()); pgrp.push_back((int)runs.size() / 2); pgrp.push_back(uniform ? 1 : 0); pgrp.push_back(0);
-                int off = 0;
-                for (auto &mbr : members) { pgrp.push_back(off); pgrp.push_back((int)mbr.size()); off += (int)mbr.size(); }
-                pgrp.insert(pgrp.end(), runs.begin(), runs.end());
-                for (auto &mbr : members) pgrp.insert(pgrp.end(), mbr.begin(), mbr.end());
-                pgrp[h0 + 3] = (int)(pgrp.size() - h0);
-            }
-            H.o_pchunk = imark(); I.insert(I.end(), chunks.begin(), chunks.end());
-            H.o_plm = imark(); I.insert(I.end(), plm.begin(), plm.end());
-            H.o_pgrp = imark(); I.insert(I.end(), pgrp.begin(), pgrp.end());
-            const int ne = n + (n & 1), npk = pos * (pos + 1) / 2, r1 = std::max(npk, ne * (ne + 1));
-            H.cb_stride = (pos + 15) & ~15;
-            const int need = MARG_CB_LM * H.cb_stride + 2 * MARG_CB_LM;
-            if (r1 - ((npk + 1) & ~1) >= need) H.cb_off = (npk + 1) & ~1;                      // in the part of region P the packed A does not use
-            else H.cb_off = ((r1 + 1) & ~1) + (int)MARG_STAGE;                                 // behind the staging records in region R2
-        }
-    }
-    H.o_prior = imark();
-    std::vector<int> pcol;
-    const tcv_prior *pr = p.prior.empty() ? nullptr : p.prior[0].prior;
-    if (pr) {
-        if (pr->n > 128) { set_error("prior with more than 128 rows"); return TCV_ERR_TOO_LARGE; }
-        H.prior_n = pr->n; H.prior_nblk = (int)pr->size.size(); H.prior_xsize = pr->xsize;
-        pcol.assign(pr->n, -1);
-        for (int k = 0; k < H.prior_nblk; k++) {
-            const int c = id_of[p.prior[0].b[k]];
-            I.push_back(c); I.push_back(pr->idx[k]); I.push_back(pr->size[k]); I.push_back(pr->xoff[k]);
-            const int local = pr->size[k] == 7 ? 6 : pr->size[k];
-            for (int j = 0; j < local; j++) if (pr->idx[k] + j < pr->n) pcol[pr->idx[k] + j] = mloc[c] < 0 ? -1 : mloc[c] + j;
-        }
-    }
-    H.o_pcol = imark();
-    for (int v : pcol) I.push_back(v);
-    H.d_x = dmark();
-    for (int c = 0; c < nblk; c++) { const ParamBlock &pb = p.blocks[orig[c]]; D.insert(D.end(), pb.addr, pb.addr + pb.size); }
-    H.d_imu = dmark();
-    Sink DS(D);      // the records shared with the solve windows: one writer each (tcv_host.h)
-    // the factor's constants are the solve problem's (same pre-integration): the kernel reads them from the solve batch's pool
-    H.imu_abs = -1;
-    if (H.sqrt_src >= 0 && solve_pk && !getenv("TCV_MARG_OWN_IMU")) H.imu_abs = solve_pk->win.dbase + solve_pk->win.d_imu + (long long)H.sqrt_src * IMU_CONST;
-    for (auto &f : p.imu) {
-        if (H.imu_abs >= 0) break;
-        if (f.dev) { if (int rc = tcv_preint_host(f.dev)) return rc; }      // (no shared copy to read from: the numbers are needed here)
-        const tcv_imu_preintegration &q = f.dev ? f.dev->pod : f.pre;
-        put_imu_const(DS, q);
-    }
-    H.d_proj = dmark();
-    for (size_t k = 0; k < p.proj.size(); k++) {
-        const ProjFac &f = p.proj[porder[k]];
-        if (int rc = put_proj_record(DS, f, p.proj[porder[0]])) return rc;
-        if (p.blocks[f.b[3]].size != 1) { set_error("projection factor: 4th block must be an inverse depth"); return TCV_ERR_UNSUPPORTED; }
-    }
-    const double psi = p.proj.empty() ? 0.0 : p.proj[porder[0]].sqrt_info, pla = p.proj.empty() ? 0.0 : p.proj[porder[0]].loss_a;
-    H.d_prior = dmark();
-    H.prior_abs = -1;
-    if (pr && solve_p && solve_pk && !solve_p->prior.empty() && solve_p->prior[0].prior == pr && solve_pk->hdr.prior_n == pr->n && !getenv("TCV_MARG_OWN_PRIOR"))
-        { H.prior_abs = solve_pk->win.dbase + solve_pk->win.d_prior; H.prior_k0 = solve_pk->prior_k0_deferred ? -1 : solve_pk->win.prior_k0; }      // the same record: put_prior_region, or the splice kernel's copy of it
-    else if (pr) {
-        if (int rc = tcv_prior_host(pr)) return rc;      // (a device-resident prior that the solve problem does not share: its numbers are needed here)
-        H.prior_k0 = prior_keep_zero_rows() ? 0 : prior_zero_rows(pr->J0.data(), pr->r0.data(), pr->n);
-        put_prior_region(DS, *pr, H.prior_k0);
-    }
-    H.d_misc = dmark();
-    D.insert(D.end(), p.G, p.G + 3); D.push_back(psi); D.push_back(pla); D.push_back(0.0); D.push_back(p.td_TR); D.push_back(p.td_ROW);
-    if (D.size() & 1) D.push_back(0.0);
+// the 512-thread instance (one workgroup per CU) or the 256-thread one (two), with lds_bytes of dynamic LDS
+template <int NT> static int launch_marg_nt(const MargArgs &a, int grid, size_t lds_bytes, hipStream_t st) {
+    hipError_t e = hipFuncSetAttribute((const void *)marg_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(marg)");
+    hipLaunchKernelGGL(marg_kernel<NT>, dim3(grid), dim3(NT), lds_bytes, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "marg kernel launch");
     return TCV_OK;
 }
 
@@ -2164,358 +1800,10 @@ int launch_prior_splice(const PriorSplice *d_jobs, int njobs, double *d_dpool, v
     if (e != hipSuccess) return hip_fail(e, "prior splice kernel launch");
     return TCV_OK;
 }
-int DevBlob::wait_ready(hipStream_t consumer) const {
-    if (!ready) return TCV_OK;
-    const hipError_t e = hipStreamWaitEvent(consumer, ready, 0);
-    return e == hipSuccess ? TCV_OK : hip_fail(e, "hipStreamWaitEvent (device-resident input)");
-}
-int DevBlob::sync_ready() const {
-    if (!ready) return TCV_OK;
-    const hipError_t e = hipEventSynchronize(ready);
-    return e == hipSuccess ? TCV_OK : hip_fail(e, "hipEventSynchronize (device-resident input)");
-}
-DevBlob::~DevBlob() {
-    if (ready) { (void)hipEventSynchronize(ready); (void)hipEventDestroy(ready); }      // (the buffer goes back to a pool: its producer must be done)
-    if (!p) return;
-    int cur = 0;
-    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != dev;
-    if (sw) (void)hipSetDevice(dev);      // (the free list is per device)
-    (void)dev_free(p);
-    if (sw) (void)hipSetDevice(cur);
-}
 
 }  // namespace tcv
-using namespace tcv;
 
-// materialises a device-resident prior on the host (export / checkpoint, or a consumer that needs the numbers: a marginalisation problem
-// that does not share its prior with the solve problem)
-int tcv_prior_host(const tcv_prior *pr) {
-    if (!pr) return TCV_ERR_INVALID;
-    std::lock_guard<std::mutex> g(pr->mu);
-    if (pr->host) return TCV_OK;
-    const int n = pr->n;
-    std::vector<double> o(MARG_OUT_COMPACT);
-    int cur = 0;
-    const bool sw = hipGetDevice(&cur) == hipSuccess && pr->dev && cur != pr->dev->dev;
-    if (sw) (void)hipSetDevice(pr->dev->dev);
-    if (pr->dev) if (const int rcw = pr->dev->sync_ready()) { if (sw) (void)hipSetDevice(cur); return rcw; }
-    const hipError_t e = hipMemcpy(o.data(), pr->d_block, sizeof(double) * MARG_OUT_COMPACT, hipMemcpyDeviceToHost);
-    if (sw) (void)hipSetDevice(cur);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H (device-resident prior)");
-    pr->J0.assign(o.begin() + MARG_OUT_J0, o.begin() + MARG_OUT_J0 + (size_t)n * n);
-    pr->r0.assign(o.begin() + MARG_OUT_R0, o.begin() + MARG_OUT_R0 + n);
-    pr->x0.clear();
-    for (size_t k = 0; k < pr->size.size(); k++) for (int i = 0; i < pr->size[k]; i++) pr->x0.push_back(o[MARG_OUT_X + pr->x_goff[k] + i]);
-    pr->host = true;
-    return TCV_OK;
-}
-
-int tcv_marg_attach(tcv_batch *b, tcv_problem *const *marg_problems, double *const *const *marg_drop, const int *marg_num_drop) {
-    MargState *s = new MargState();
-    b->marg = s;
-    b->marg_free = marg_free;
-    s->win.resize(b->n);
-    std::vector<MargHdr> hdrs(b->n);
-    size_t lds = 0;
-    for (int w = 0; w < b->n; w++)
-        if (marg_problems[w] && (!marg_drop || !marg_drop[w])) { set_error("marginalisation problem without a drop list"); return TCV_ERR_INVALID; }
-    // the windows are packed by host threads, each into its own int / double pools (contiguous window ranges); the pools are then laid end
-    // to end in pinned upload buffers and the headers' pool offsets shifted accordingly
-    const int nth = tcv::host_threads(std::max(1, std::min(b->n <= 16 ? b->n : b->n / 8, 16)));      // (inside tcv_batch_create's HostOp; a lock-step frame's handful of windows: one each)
-    std::vector<std::vector<int>> It(nth);
-    std::vector<std::vector<double>> Dt(nth);
-    std::vector<int> rcs(nth, TCV_OK);
-    std::vector<std::string> msgs(nth);
-    auto range = [&](int t) { return std::make_pair((int)((long long)b->n * t / nth), (int)((long long)b->n * (t + 1) / nth)); };
-    auto work = [&](int t) {
-        const auto r = range(t);
-        for (int w = r.first; w < r.second; w++) {
-            auto skip_header = [&]() {      // an empty header (nblk = 0), which the kernel skips
-                MargHdr &H = s->win[w].hdr;
-                std::memset(&H, 0, sizeof H);
-                H.ibase = (long long)It[t].size(); H.dbase = (long long)Dt[t].size();
-                H.sqrt_src = -1; H.prior_abs = -1; H.imu_abs = -1; H.cb_off = -1; H.td_blk = -1; H.solve_window = w;
-            };
-            if (!marg_problems[w]) { skip_header(); continue; }      // this window is not marginalised
-            const size_t i0 = It[t].size(), d0 = Dt[t].size();
-            const int rc = pack_marg(*marg_problems[w], marg_drop[w], marg_num_drop[w], b->problems[w], &b->packed[w], s->win[w], It[t], Dt[t]);
-            if (rc == MARG_PACK_EMPTY_KEEP) { It[t].resize(i0); Dt[t].resize(d0); skip_header(); continue; }      // keeps nothing: an empty prior comes back
-            if (rc != TCV_OK) { rcs[t] = rc; msgs[t] = tcv_last_error(); return; }
-            s->win[w].hdr.solve_window = w;
-        }
-    };
-    tcv::parallel_run(nth, work);
-    for (int t = 0; t < nth; t++) if (rcs[t] != TCV_OK) { if (!msgs[t].empty()) set_error(msgs[t]); return rcs[t]; }
-    std::vector<size_t> ib(nth + 1, 0), db(nth + 1, 0);
-    for (int t = 0; t < nth; t++) { ib[t + 1] = ib[t] + It[t].size(); db[t + 1] = db[t] + Dt[t].size(); }
-    for (int t = 0; t < nth; t++) {
-        const auto r = range(t);
-        for (int w = r.first; w < r.second; w++) {
-            s->win[w].hdr.ibase += (long long)ib[t]; s->win[w].hdr.dbase += (long long)db[t];
-            hdrs[w] = s->win[w].hdr;
-            if (hdrs[w].nblk == 0) continue;
-            const int ne_ = hdrs[w].n + (hdrs[w].n & 1), r1_ = std::max(hdrs[w].pos * (hdrs[w].pos + 1) / 2, ne_ * (ne_ + 1));
-            const int cb_r2 = (hdrs[w].cb_off >= 0 && hdrs[w].cb_off >= ((r1_ + 1) & ~1)) ? MARG_CB_LM * hdrs[w].cb_stride + 2 * MARG_CB_LM : 0;
-            const size_t need = marg_lds_doubles(hdrs[w].pos, hdrs[w].m, hdrs[w].n, hdrs[w].nx, cb_r2) * 8;
-            if (need > (size_t)LDS_DOUBLES * 8) { set_error("marginalisation does not fit LDS"); return TCV_ERR_TOO_LARGE; }
-            lds = std::max(lds, need);
-        }
-    }
-    // one pinned staging buffer, one device blob: [double pool | headers | int pool], one asynchronous copy on the calling thread's stream
-    const size_t i_total = ib[nth], d_total = db[nth];
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_hdr = up16(sizeof(double) * std::max<size_t>(1, d_total)), o_int = up16(o_hdr + sizeof(MargHdr) * hdrs.size());
-    const size_t in_bytes = up16(o_int + sizeof(int) * std::max<size_t>(1, i_total));
-    hipStream_t ust = tcv::util_stream();
-    // (released at every exit; once the asynchronous upload has been issued the stream is drained first: the pinned buffer goes back to a
-    // pool another host thread takes from)
-    tcv::StagedTransfer staged(ust, in_bytes);
-    char *h_in = (char *)staged.host;
-    if (!h_in) { set_error("hipHostMalloc (upload staging) failed"); return TCV_ERR_HIP; }
-    int *h_I = (int *)(h_in + o_int);
-    double *h_D = (double *)h_in;
-    std::memcpy(h_in + o_hdr, hdrs.data(), sizeof(MargHdr) * hdrs.size());
-    {
-        auto copy = [&](int t) {
-            if (!It[t].empty()) std::memcpy(h_I + ib[t], It[t].data(), sizeof(int) * It[t].size());
-            if (!Dt[t].empty()) std::memcpy(h_D + db[t], Dt[t].data(), sizeof(double) * Dt[t].size());
-        };
-        tcv::parallel_run(nth, copy);
-    }
-    s->lds_bytes = lds;
-    const int n_cu = b->n_cu;      // (of the batch's device: tcv_batch_create sets it before anything attaches)
-    // more windows than CUs and every window within half a CU's LDS: two 256-thread workgroups per CU; otherwise one of 512 threads
-    const char *force = getenv("TCV_MARG_NT");
-    const bool pair = force ? atoi(force) == MARG_NT_PAIR : (b->n > n_cu && lds <= (size_t)LDS_DOUBLES * 4);
-    if (pair && lds > (size_t)LDS_DOUBLES * 4) { set_error("TCV_MARG_NT=256: the batch does not fit 80 KB of LDS per window"); return TCV_ERR_TOO_LARGE; }
-    s->nt = pair ? MARG_NT_PAIR : MARG_NT_WIDE;
-    if (pair) s->lds_bytes = (size_t)LDS_DOUBLES * 4;
-    s->grid = std::min(b->n, pair ? 2 * n_cu : n_cu);
-    if (const char *eg = getenv("TCV_MARG_GRID")) { const int g = atoi(eg); if (g > 0) s->grid = std::min(s->grid, g); }      // tuning experiments (one workgroup per CU: TCV_MARG_GRID=256)
-    {
-        hipError_t e_ = tcv::dev_malloc(&s->d_input, in_bytes);
-        if (e_ == hipSuccess) { staged.issued(); e_ = hipMemcpyAsync(s->d_input, h_in, in_bytes, hipMemcpyHostToDevice, ust); }
-        // result blocks and, behind them, [status | k0] of every window: one buffer, kept alive by the device-resident priors that read it
-        if (e_ == hipSuccess) e_ = tcv::dev_malloc((void **)&s->d_out, sizeof(double) * std::max<size_t>(1, (size_t)b->n * MARG_OUT_STRIDE) + sizeof(int) * 2 * (size_t)b->n);
-        if (e_ == hipSuccess) { s->out_blob = std::make_shared<DevBlob>(); s->out_blob->p = s->d_out; (void)hipGetDevice(&s->out_blob->dev); s->d_status = (int *)(s->d_out + std::max<size_t>(1, (size_t)b->n * MARG_OUT_STRIDE)); }
-        if (e_ == hipSuccess) e_ = tcv::dev_malloc((void **)&s->d_scratch, sizeof(double) * (size_t)s->grid * MARG_SCR_STRIDE);
-        if (e_ == hipSuccess) e_ = hipMemsetAsync(s->d_status, 0xff, sizeof(int) * 2 * b->n, ust);
-        // No wait for the upload: the native estimator attaches the problems while the batch's SOLVE runs on this very stream, and a wait here
-        // is a wait for that kernel (a caller that overlaps another group's host work with it -- tcv_estimators_optimize_begin -- lost the whole
-        // overlap to it).  The batch notes the stream (a later launch on another stream is ordered behind the upload by an event,
-        // tcv_batch_enter_stream); the pinned staging buffer is parked until this thread's next wait on the stream.
-        if (e_ == hipSuccess && ust != nullptr) {
-            if (int rce = tcv_batch_enter_stream(b, (void *)ust)) return rce;
-            staged.park();
-        } else if (e_ == hipSuccess) e_ = staged.wait();
-        if (e_ != hipSuccess) return hip_fail(e_, "upload of the marginalisation problems");
-        s->d_dpool = (double *)s->d_input; s->d_hdr = (MargHdr *)((char *)s->d_input + o_hdr); s->d_ipool = (int *)((char *)s->d_input + o_int);
-    }
-    if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) return TCV_ERR_HIP;
-    return TCV_OK;
-}
-
-int tcv_marg_run(tcv_batch *b, void *stream) {
-    MargState *s = (MargState *)b->marg;
-    if (!s) { set_error("batch was created without marginalisation problems"); return TCV_ERR_INVALID; }
-    MargArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.hdr = s->d_hdr; a.ipool = s->d_ipool; a.dpool = s->d_dpool; a.solve_state = b->d_state; a.out = s->d_out;
-    a.out_status = s->d_status; a.scratch = s->d_scratch; a.nwin = b->n; a.state_stride = b->state_stride;
-    a.use_solved_state = b->solved ? 1 : 0;
-    a.solve_dpool = b->d_dpool; a.solve_win = (const void *)b->d_win;
-    a.solve_sqrt = (b->solved && b->sqrt_out_valid && !getenv("TCV_MARG_OWN_SQRT")) ? b->d_sqrt_out : nullptr;
-    a.eig_mm = getenv("TCV_MARG_EIG_MM") ? 1 : 0;
-    a.eig_flags = getenv("TCV_MARG_EIG_FLAGS") ? atoi(getenv("TCV_MARG_EIG_FLAGS")) : 0;
-    hipStream_t st = (hipStream_t)stream;
-    const void *fn = s->nt == MARG_NT_PAIR ? (const void *)marg_kernel<MARG_NT_PAIR> : (const void *)marg_kernel<MARG_NT_WIDE>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bytes);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(marg)");
-    if ((e = hipEventRecord(s->ev0, st)) != hipSuccess) return hip_fail(e, "hipEventRecord");
-    if (s->nt == MARG_NT_PAIR) hipLaunchKernelGGL(marg_kernel<MARG_NT_PAIR>, dim3(s->grid), dim3(MARG_NT_PAIR), s->lds_bytes, st, a);
-    else hipLaunchKernelGGL(marg_kernel<MARG_NT_WIDE>, dim3(s->grid), dim3(MARG_NT_WIDE), s->lds_bytes, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "marg kernel launch");
-    if ((e = hipEventRecord(s->ev1, st)) != hipSuccess) return hip_fail(e, "hipEventRecord");
-    // what consumers of device-resident priors on other streams (and host readers) wait for: tcv_batch_get_priors_device_async hands the
-    // results out while this kernel may still be running
-    if (s->out_blob) {
-        if (!s->out_blob->ready && hipEventCreateWithFlags(&s->out_blob->ready, hipEventDisableTiming) != hipSuccess) s->out_blob->ready = nullptr;
-        if (s->out_blob->ready && (e = hipEventRecord(s->out_blob->ready, st)) != hipSuccess) return hip_fail(e, "hipEventRecord");
-    }
-    s->ran = true;
-    s->h_valid = false;
-    s->status_prefetched = false;
-    return TCV_OK;
-}
-
-// the statuses on their way to the host behind the marginalisation kernel (tcv_batch_get_priors_device_async): whoever asks later, after
-// waiting for the batch, finds them in pinned memory instead of paying a blocking copy
-int tcv_marg_status_prefetch(tcv_batch *b, void *stream) {
-    MargState *s = (MargState *)b->marg;
-    if (!s || !s->ran) return TCV_OK;
-    if (!s->h_status_pre) s->h_status_pre = (int *)tcv::host_staging_acquire(sizeof(int) * 2 * (size_t)b->n);
-    if (!s->h_status_pre) return TCV_OK;      // (the blocking copy later)
-    const hipError_t e = hipMemcpyAsync(s->h_status_pre, s->d_status, sizeof(int) * 2 * (size_t)b->n, hipMemcpyDeviceToHost, (hipStream_t)stream);
-    s->status_prefetched = e == hipSuccess;
-    return TCV_OK;
-}
-
-int tcv_marg_layout_n(const tcv_batch *b, int window) {
-    const MargState *s = (const MargState *)b->marg;
-    if (!s || window < 0 || window >= (int)s->win.size() || s->win[window].hdr.nblk == 0) return -1;
-    return s->win[window].hdr.n;
-}
-bool tcv_marg_has_problem(const tcv_batch *b, int window) {
-    const MargState *s = (const MargState *)b->marg;
-    return s && window >= 0 && window < b->n && (s->win[window].hdr.nblk != 0 || s->win[window].empty_keep);
-}
-int tcv_marg_sqrt_source(const tcv_batch *b, int window) {
-    const MargState *s = (const MargState *)b->marg;
-    return (s && window >= 0 && window < b->n) ? s->win[window].hdr.sqrt_src : -1;
-}
-
-// one D2H copy of every window's result block and status instead of one copy per tcv_batch_get_prior call, into a pinned buffer.
-// compact: J0, r0 and the linearisation point only (a strided copy of the first MARG_OUT_COMPACT doubles of every block); the priors
-// handed out afterwards carry no A', b'.
-int tcv_marg_download(tcv_batch *b, int compact) {
-    MargState *s = (MargState *)b->marg;
-    if (!s || !s->ran) { set_error("no marginalisation result"); return TCV_ERR_INVALID; }
-    const size_t stride = compact ? (size_t)MARG_OUT_COMPACT : (size_t)MARG_OUT_STRIDE;
-    if (s->h_out && s->h_stride != stride) { tcv::host_staging_release(s->h_out); s->h_out = nullptr; }
-    if (!s->h_out) s->h_out = (double *)tcv::host_staging_acquire(sizeof(double) * stride * b->n);
-    if (!s->h_out) { set_error("hipHostMalloc (download staging) failed"); return TCV_ERR_HIP; }
-    s->h_stride = stride;
-    s->h_status.resize(b->n);
-    hipStream_t ust = tcv::util_stream();      // (h_out is pinned: asynchronous copies on the calling thread's own stream)
-    hipError_t e = compact ? hipMemcpy2DAsync(s->h_out, sizeof(double) * stride, s->d_out, sizeof(double) * MARG_OUT_STRIDE, sizeof(double) * stride, b->n, hipMemcpyDeviceToHost, ust)
-                           : hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * stride * b->n, hipMemcpyDeviceToHost, ust);
-    if (e == hipSuccess) e = tcv::stream_wait(ust);
-    if (e == hipSuccess) e = hipMemcpy(s->h_status.data(), s->d_status, sizeof(int) * b->n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
-    s->h_valid = true;
-    return TCV_OK;
-}
-
-// elapsed time of the last marginalisation launch (called from tcv_batch_synchronize)
-void tcv_marg_elapsed(tcv_batch *b) {
-    MargState *s = (MargState *)b->marg;
-    if (s && s->ran) (void)hipEventElapsedTime(&b->marg_ms, s->ev0, s->ev1);
-}
-
-// per-window status of the last marginalisation: 0 ok, 1 an eigen-solver hit its sweep cap, 2 the tridiagonal eigen-solver's
-// self-check failed and the cyclic-Jacobi safety net produced the result, < 0 not run
-extern "C" int tcv_batch_marg_status(tcv_batch *b, int *out, int n) {
-    MargState *s = b ? (MargState *)b->marg : nullptr;
-    if (!s || !s->ran || !out || n > b->n) { set_error("no marginalisation result"); return TCV_ERR_INVALID; }
-    if (b->pending) if (int rc = tcv_batch_synchronize(b)) return rc;      // (a copy on the null stream is not ordered behind a non-blocking stream)
-    std::vector<int> st(2 * (size_t)b->n);
-    if (s->status_prefetched) std::memcpy(st.data(), s->h_status_pre, sizeof(int) * st.size());      // (came down behind the kernel; the wait above covers it)
-    else {
-        const hipError_t e = hipMemcpy(st.data(), s->d_status, sizeof(int) * st.size(), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
-    }
-    for (int w = 0; w < n; w++)      // -2: a NaN in the result; a marginalisation that keeps nothing has nothing to run: 0
-        out[w] = s->win[w].empty_keep ? 0 : ((st[w] == 0 && st[b->n + w] < 0 && s->win[w].hdr.nblk != 0) ? -2 : st[w]);
-    return TCV_OK;
-}
-
-// kernel status of a window: TCV_OK, or the error it stands for
-static int marg_status_error(int status) {
-    if (status < 0) { set_error("marginalisation kernel did not complete for this window"); return TCV_ERR_NUMERIC; }
-    // status 1: an eigen-solver ran into its sweep cap -- the decomposition is not converged and the prior would silently degrade every
-    // later window (the reference's SelfAdjointEigenSolver has no such exit); status 2 (safety net took over) is a valid result
-    if (status == 1) { set_error("marginalisation: eigen-decomposition did not converge (sweep cap)"); return TCV_ERR_NUMERIC; }
-    return TCV_OK;
-}
-// host-side layout of the prior a window's marginalisation makes (no numbers yet): kept blocks' sizes, columns, offsets in x0, addresses
-static tcv_prior *prior_layout(const MargWindow &mw) {
-    tcv_prior *pr = new tcv_prior();
-    pr->m = mw.m_total; pr->n = mw.hdr.n;     // the reference's m counts every marginalised dim (marginalization_factor.cpp:176-186)
-    int xo = 0;
-    for (size_t k = 0; k < mw.keep_block.size(); k++) {
-        pr->size.push_back(mw.keep_size[k]);
-        pr->idx.push_back(mw.keep_idx[k] - mw.hdr.m);      // (hdr.m: dropped dims that went through the eigen step)
-        pr->xoff.push_back(xo);
-        xo += mw.keep_size[k];
-        pr->addr.push_back(mw.keep_addr[k]);
-    }
-    pr->xsize = xo;
-    return pr;
-}
-
-int tcv_marg_get_prior(tcv_batch *b, int window, tcv_prior **out) {
-    MargState *s = (MargState *)b->marg;
-    if (!s || !s->ran || window < 0 || window >= b->n) { set_error("no marginalisation result for this window"); return TCV_ERR_INVALID; }
-    const MargWindow &mw = s->win[window];
-    if (mw.empty_keep) { tcv_prior *pr = new tcv_prior(); pr->m = mw.m_total; pr->n = 0; *out = pr; return TCV_OK; }      // the reference's empty MarginalizationInfo
-    if (mw.hdr.nblk == 0) { set_error("this window of the batch has no marginalisation problem"); return TCV_ERR_INVALID; }
-    const int n = mw.hdr.n, m = mw.hdr.m;      // m: dropped dims that went through the eigen step (all of them unless block mode)
-    std::vector<double> o(MARG_OUT_STRIDE);
-    int status = -1;
-    bool have_schur = true;
-    if (s->h_valid) {
-        std::copy(s->h_out + (size_t)window * s->h_stride, s->h_out + (size_t)(window + 1) * s->h_stride, o.begin());
-        have_schur = s->h_stride == (size_t)MARG_OUT_STRIDE;
-        status = s->h_status[window];
-    } else {
-        hipError_t e = hipMemcpy(o.data(), s->d_out + (size_t)window * MARG_OUT_STRIDE, sizeof(double) * MARG_OUT_STRIDE, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(&status, s->d_status + window, sizeof(int), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
-    }
-    if (int rc = marg_status_error(status)) return rc;
-    tcv_prior *pr = prior_layout(mw);
-    for (size_t k = 0; k < mw.keep_block.size(); k++)
-        for (int i = 0; i < mw.keep_size[k]; i++) pr->x0.push_back(o[MARG_OUT_X + mw.keep_goff[k] + i]);
-    pr->J0.assign(o.begin() + MARG_OUT_J0, o.begin() + MARG_OUT_J0 + (size_t)n * n);
-    pr->r0.assign(o.begin() + MARG_OUT_R0, o.begin() + MARG_OUT_R0 + n);
-    if (have_schur) {
-        pr->As.assign(o.begin() + MARG_OUT_AS, o.begin() + MARG_OUT_AS + (size_t)n * n);
-        pr->bs.assign(o.begin() + MARG_OUT_BS, o.begin() + MARG_OUT_BS + n);
-    }
-    if (getenv("TCV_DEBUG")) {
-        fprintf(stderr, "[tcv] marg window %d: m=%d n=%d jacobi sweeps %g / %g status %d\n", window, m, n, o[MARG_OUT_X + MARG_MAX_X], o[MARG_OUT_X + MARG_MAX_X + 1], status);
-        const char *nm[12] = {"load", "prior", "imu", "proj", "eig_mm", "Z", "schur", "eig_rr", "out", "j_angle|chol_mm", "j_cols|barrier", "j_rows|subst_mm"};      // (9..11: Jacobi safety net, or the register Cholesky route of Amm)
-        fprintf(stderr, "[tcv]   Amm: trace(Amm^-1) %.3e, of the unit-diagonal scaling %.3e\n", o[MARG_OUT_X + MARG_MAX_X + 40], o[MARG_OUT_X + MARG_MAX_X + 41]);
-        for (int i = 0; i < 12; i++) fprintf(stderr, "[tcv]   %-7s %12.0f cycles\n", nm[i], o[MARG_OUT_X + MARG_MAX_X + 2 + i]);
-        fprintf(stderr, "[tcv]     proj, chunked block path: evaluation + chunk set-up %.0f | accumulation %.0f | landmark elimination %.0f cycles\n",
-                o[MARG_OUT_X + MARG_MAX_X + 45], o[MARG_OUT_X + MARG_MAX_X + 46], o[MARG_OUT_X + MARG_MAX_X + 47]);
-        const char *en[6] = {"tridiag", "bisect", "vectors", "mgs", "backtr", "check"};
-        for (int i = 0; i < 6; i++) fprintf(stderr, "[tcv]     eig_rr.%-8s %10.0f cycles\n", en[i], o[MARG_OUT_X + MARG_MAX_X + 14 + 8 + i]);
-        fprintf(stderr, "[tcv]     tridiag steps (wave 0): part 1 %.0f | barrier %.0f | update m > 40 %.0f, m > 16 %.0f, m <= 16 %.0f | barrier %.0f cycles\n", o[MARG_OUT_X + MARG_MAX_X + 28], o[MARG_OUT_X + MARG_MAX_X + 29], o[MARG_OUT_X + MARG_MAX_X + 30], o[MARG_OUT_X + MARG_MAX_X + 31], o[MARG_OUT_X + MARG_MAX_X + 32], o[MARG_OUT_X + MARG_MAX_X + 33]);
-        fprintf(stderr, "[tcv]   tridiag check: dev %.3e sum(lam) %.10e trace %.10e |T| %.3e lam_min %.3e lam_max %.3e\n", o[MARG_OUT_X + MARG_MAX_X + 14], o[MARG_OUT_X + MARG_MAX_X + 15], o[MARG_OUT_X + MARG_MAX_X + 16], o[MARG_OUT_X + MARG_MAX_X + 17], o[MARG_OUT_X + MARG_MAX_X + 18], o[MARG_OUT_X + MARG_MAX_X + 19]);
-    }
-    for (double v : pr->J0) if (!(v == v)) { delete pr; set_error("NaN in marginalisation result"); return TCV_ERR_NUMERIC; }
-    *out = pr;
-    return TCV_OK;
-}
-
-// tcv_batch_get_priors_device: layout on the host, numbers left in the batch's result buffer (shared with the handles)
-int tcv_marg_get_priors_device(tcv_batch *b, tcv_prior **out, int n, bool nowait) {
-    MargState *s = (MargState *)b->marg;
-    if (!s || !s->ran || n != b->n) { set_error("no marginalisation result (or n is not the batch size)"); return TCV_ERR_INVALID; }
-    if (nowait && !(s->out_blob && s->out_blob->ready)) {      // (no event to order consumers by: wait as usual)
-        nowait = false;
-        if (b->pending) if (int rcs = tcv_batch_synchronize(b)) return rcs;
-    }
-    std::vector<int> st(2 * (size_t)n, 0);
-    if (nowait) { for (int w = 0; w < n; w++) st[n + w] = -1; }      // status unknown here (tcv_batch_marg_status later), k0 read on the device
-    else if (int rcd = tcv::staged_download(st.data(), s->d_status, sizeof(int) * st.size(), "hipMemcpy D2H (marginalisation status)")) return rcd;
-    for (int w = 0; w < n; w++) out[w] = nullptr;
-    int rc = TCV_OK;
-    for (int w = 0; w < n && rc == TCV_OK; w++) {
-        const MargWindow &mw = s->win[w];
-        if (mw.empty_keep) { tcv_prior *pr = new tcv_prior(); pr->m = mw.m_total; pr->n = 0; out[w] = pr; continue; }      // empty prior: host-resident, nothing to splice
-        if (mw.hdr.nblk == 0) continue;      // not marginalised: out[w] stays NULL
-        const int status = st[w], k0 = st[n + w];
-        if ((rc = marg_status_error(status)) != TCV_OK) break;
-        if (k0 < 0 && !nowait) { set_error("NaN in marginalisation result"); rc = TCV_ERR_NUMERIC; break; }
-        if ((int)mw.keep_block.size() > PRIOR_SPLICE_MAX_BLOCKS) { set_error("device-resident prior: too many kept blocks"); rc = TCV_ERR_TOO_LARGE; break; }
-        tcv_prior *pr = prior_layout(mw);
-        pr->x_goff.assign(mw.keep_goff.begin(), mw.keep_goff.begin() + mw.keep_block.size());
-        pr->dev = s->out_blob; pr->d_block = s->d_out + (size_t)w * MARG_OUT_STRIDE; pr->k0 = k0; pr->host = false;
-        pr->d_status = s->d_status + w; pr->d_k0 = s->d_status + n + w;
-        out[w] = pr;
-    }
-    if (rc != TCV_OK) for (int w = 0; w < n; w++) if (out[w]) { delete out[w]; out[w] = nullptr; }
-    return rc;
+int tcv_launch_marg(const tcv::MargArgs *args, int grid, int nt, size_t lds_bytes, hipStream_t st) {
+    return nt == tcv::MARG_NT_PAIR ? tcv::launch_marg_nt<tcv::MARG_NT_PAIR>(*args, grid, lds_bytes, st)
+                                   : tcv::launch_marg_nt<tcv::MARG_NT_WIDE>(*args, grid, lds_bytes, st);
 }

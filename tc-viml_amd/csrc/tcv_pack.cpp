@@ -1207,7 +1207,7 @@ static int pack_plan(const tcv_problem &p, Packed &out, int mode, int chain_lds,
 
 // data half: the window's doubles in the layout the plan expects (offsets depend on the counts only).  The sink either counts
 // (no destination) or writes: a batch first sizes every window, then all windows are written straight into one upload buffer.
-// The three record layouts the marginalisation packer (tcv_marg.hip pack_marg) writes too:
+// The three record layouts the marginalisation packer (tcv_marg_host.cpp marg_write_doubles) writes too:
 void put_imu_const(Sink &D, const tcv_imu_preintegration &q) {
     D.put(q.delta_p, 3); D.put(q.delta_q, 4); D.put(q.delta_v, 3); D.put(q.linearized_ba, 3); D.put(q.linearized_bg, 3); D.put1(q.sum_dt);
     const int rc[5][2] = {{0, 9}, {0, 12}, {3, 12}, {6, 9}, {6, 12}};   // dp_dba dp_dbg dq_dbg dv_dba dv_dbg (imu_factor.h:61-79)

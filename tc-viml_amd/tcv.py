@@ -42,7 +42,7 @@ EXPORTS = [
     "tcv_batch_get_priors_device", "tcv_batch_get_priors_device_async", "tcv_prior_is_device_resident", "tcv_problem_set_marginalization_prior",
     "tcv_problems_set_marginalization_prior", "tcv_priors_destroy",
     "tcv_match_lines_batch", "tcv_preintegrate_device", "tcv_preint_sum_dt", "tcv_preint_export", "tcv_preint_destroy", "tcv_problem_add_imu_factor_device",
-    "tcv_microbench_fp64", "tcv_problem_plan_ints", "tcv_set_packer_reference", "tcv_plan_cache_stats", "tcv_problems_pack_bench", "tcv_line_map_create", "tcv_line_map_destroy", "tcv_batch_download_states_brief", "tcv_thread_stream_slot", "tcv_batch_download_states_begin", "tcv_batch_download_states_end",
+    "tcv_microbench_fp64", "tcv_problem_plan_ints", "tcv_problem_marg_plan", "tcv_marg_lds_layout", "tcv_set_packer_reference", "tcv_plan_cache_stats", "tcv_problems_pack_bench", "tcv_line_map_create", "tcv_line_map_destroy", "tcv_batch_download_states_brief", "tcv_thread_stream_slot", "tcv_batch_download_states_begin", "tcv_batch_download_states_end",
     "tcv_evaluate_options_default", "tcv_batch_evaluate", "tcv_batch_evaluation_dims", "tcv_batch_get_evaluation", "tcv_batch_get_evaluation_costs",
     "tcv_problem_evaluate", "tcv_problem_num_effective_parameters",
 ]
@@ -412,6 +412,40 @@ class Window:
         if getattr(self, "h", None) is not None and _lib is not None:
             _lib.tcv_problem_destroy(self.h)
             self.h = None
+
+
+class MargHdr(C.Structure):
+    """csrc/tcv_marg.h MargHdr: the header tcv_problem_marg_plan returns in front of the int pool"""
+    _fields_ = [(k, C.c_int) for k in ("nblk", "pos", "m", "n", "nx", "n_imu", "n_proj", "prior_n", "prior_nblk", "prior_xsize",
+                                       "o_blk", "o_imu", "o_proj", "o_prior", "o_pcol", "d_x", "d_imu", "d_proj", "d_prior", "d_misc")] + \
+               [("ibase", C.c_longlong), ("dbase", C.c_longlong), ("prior_k0", C.c_int), ("pad_k0", C.c_int), ("prior_abs", C.c_longlong),
+                ("solve_window", C.c_int), ("imu_abs", C.c_longlong)] + \
+               [(k, C.c_int) for k in ("block_mode", "o_plast", "n_pchunk", "o_pchunk", "o_plm", "o_pgrp", "pad_pgrp", "cb_off", "cb_stride",
+                                       "td_blk", "sqrt_src", "proj_disjoint")]
+
+
+def marg_plan(marg_window: "Window", drops, solve_window: "Window | None" = None):
+    """tcv_problem_marg_plan (host only): (MargHdr, ints = header + int pool, double pool) of one marginalisation problem, packed next to
+    its solve problem when one is given; (None, empty, empty) when the marginalisation keeps nothing"""
+    lib().tcv_problem_marg_plan.argtypes = [C.c_void_p, C.POINTER(_dp), C.c_int, C.c_void_p, _ip, C.c_int, _ip, _dp, C.c_int, _ip]
+    arr = (_dp * max(1, len(drops)))(*drops)
+    ni, nd = C.c_int(), C.c_int()
+    sh = solve_window.h if solve_window is not None else None
+    check(lib().tcv_problem_marg_plan(marg_window.h, arr, len(drops), sh, None, 0, C.byref(ni), None, 0, C.byref(nd)))
+    ints, dbl = np.zeros(ni.value, np.int32), np.zeros(nd.value)
+    check(lib().tcv_problem_marg_plan(marg_window.h, arr, len(drops), sh, iptr(ints), ni.value, C.byref(ni), dptr(dbl), nd.value, C.byref(nd)))
+    if ni.value == 0:
+        return None, ints, dbl
+    assert ni.value * 4 >= C.sizeof(MargHdr)
+    return MargHdr.from_buffer_copy(ints[:C.sizeof(MargHdr) // 4].tobytes()), ints, dbl
+
+
+def marg_lds_layout(pos, m, n, nx, cb_off=-1, cb_stride=0):
+    """tcv_marg_lds_layout: the host's copy of the marginalisation kernel's LDS carve, in doubles"""
+    lib().tcv_marg_lds_layout.argtypes = [C.c_int] * 6 + [_ip]
+    out = np.zeros(7, np.int32)
+    check(lib().tcv_marg_lds_layout(pos, m, n, nx, cb_off, cb_stride, iptr(out)))
+    return dict(zip(("p", "r2", "cb_in_r2", "cb_off_p", "cb_off_r2", "total", "fits"), (int(v) for v in out)))
 
 
 def margin_old_window(win: dict) -> dict:

@@ -199,7 +199,7 @@ def test_large_drop_set_uses_landmark_pivots(gpu):
 @pytest.mark.parametrize("nt", ["256", "512"])
 def test_both_launch_shapes_of_the_marginalisation_kernel(gpu, monkeypatch, nt):
     """The kernel runs as one 512-thread workgroup per CU or, for batches larger than the CU count whose windows fit 80 KB of LDS, as
-    two 256-thread workgroups per CU (csrc/tcv_marg.hip; chosen by batch size, forced here through TCV_MARG_NT).  The accumulation of
+    two 256-thread workgroups per CU (csrc/tcv_marg_host.cpp marg_launch_shape; chosen by batch size, forced here through TCV_MARG_NT).  The accumulation of
     A and the Schur complement do not depend on the shape: A', b' bit for bit; the eigen step differs in rounding only (4-section vs
     7-section eigenvalue search, three vs four lanes per column in the back-transformation): J0'J0 = A' and J0'r0 = b' to the same floor."""
     pre, main, z = golden_windows()
