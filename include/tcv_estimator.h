@@ -8,7 +8,9 @@
  *   removeFront :655-696) and the chaining of the marginalisation prior (:2027-2044, :2083-2113).
  * The solver itself is the C-ABI of tcv.h (device pre-integration, fused solve, gauge fix, marginalisation, line association).
  * Out of scope as in the rest of this library: image / line front end (the caller delivers tracked points and line tracks),
- * initialisation (the window is filled from caller-provided states), relocalisation, ESTIMATE_TD.
+ * initialisation (the window is filled from caller-provided states), relocalisation.  ESTIMATE_TD (the online camera-IMU time offset,
+ * with the rolling-shutter terms TR / ROW) is in: its entry points are declared in tcv_estimator_td.h, included at the end of this file; cutting the IMU
+ * stream at img_t + td stays with the caller, like the rest of estimator_node.cpp.
  *
  * Several estimators (one per sequence) are advanced in lock step by tcv_estimators_optimize(): all full windows of a frame form
  * ONE device batch (BASELINE configs[4]: per-sequence replay, many sequences per GPU).
@@ -149,4 +151,5 @@ int tcv_estimators_kernel_profile(double *out8);
 #ifdef __cplusplus
 }
 #endif
+#include "tcv_estimator_td.h"      /* ESTIMATE_TD: time offset, staged point aux, the snapshot's TD part */
 #endif

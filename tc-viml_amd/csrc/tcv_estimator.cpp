@@ -107,6 +107,7 @@ void smallest_right_singular_vector(std::vector<std::array<double, 4>> A, double
 struct Feature {
     int id, start;
     std::vector<V3> obs;
+    std::vector<std::array<double, 5>> aux;      // ESTIMATE_TD only, one per observation: uv (pixels), velocity (normalised plane), cur_td (feature_manager.h:138-149); empty otherwise
     double depth = -1.0;       // FeaturePerId ctor: estimated_depth(-1.0)
     int solve_flag = 0;
     int end() const { return start + (int)obs.size() - 1; }
@@ -192,7 +193,8 @@ struct EstInflight {
 // snapshot of the window an estimator handed to the solver (tcv_estimator_set_window_tap)
 struct WindowTap {
     bool on = false, have = false;
-    std::vector<double> pose_in, sb_in, ex_in, feat_in, pose_out, sb_out, ex_out, feat_out, pts, ld, x0, J0, r0;
+    std::vector<double> pose_in, sb_in, ex_in, feat_in, pose_out, sb_out, ex_out, feat_out, pts, ld, x0, J0, r0, aux;
+    double td_in = 0, td_out = 0;
     std::vector<tcv_imu_preintegration> imu;
     std::vector<int> imu_i, imu_j, pi, pj, pl, lf, pk, pidx, psize, pcol;
     double Ric[9];
@@ -227,7 +229,7 @@ struct tcv_estimator {
     std::vector<unsigned char> fov[W + 1];   // WorldLinesInFOV[i] as a mask over the map (empty: not set)
     bool fov_ready = false;
     tcv_prior *prior = nullptr;
-    std::vector<std::pair<int, int>> prior_blocks;      // (kind 0 pose / 1 sb / 2 ex, index)
+    std::vector<std::pair<int, int>> prior_blocks;      // (kind 0 pose / 1 sb / 2 ex / 3 td, index)
     int frame_count = 0, marg_flag = MARGIN_OLD;
     bool have_acc0 = false, have_last = false;
     V3 acc_0, gyr_0, last_P;
@@ -252,6 +254,13 @@ struct tcv_estimator {
     int phase = 0;                           // 0: between frames, 1: window full, waiting for the optimisation, 2: optimised, waiting for finish_frame
     int opt_failed = 0;                      // != TCV_OK: this estimator's window failed in the last lock-step batch (reported by finish_frame)
     std::string opt_msg;
+    // ESTIMATE_TD (tcv_estimator_set_time_offset): the globals ESTIMATE_TD / TD / TR / ROW (parameters.cpp:135-138), Estimator::td and para_Td[0]
+    int estimate_td = 0;
+    double td0 = 0.0, td = 0.0, td_TR = 0.0, td_ROW = 1.0;
+    double para_td[1] = {0.0};
+    std::vector<double> staged_aux;          // tcv_estimator_stage_point_aux: n x 4 for the next begin_frame
+    int staged_n = -1;                       // -1: nothing staged
+    std::vector<double> w_aux, m_aux;        // proj_td_aux of the window / of its marginalisation problem (n_proj x 8)
     int pend_failed = 0;                     // != TCV_OK: the previous frame's (deferred) marginalisation could not be launched: this frame's window is solved without
     std::string pend_msg;                    // its prior, nothing of it is applied and finish_frame reports the failure (the caller resets, like after failureDetection)
 };
@@ -292,7 +301,7 @@ void process_imu(tcv_estimator *e, int n, const double *acc, const double *gyr) 
     e->pre_valid[j] = false;
 }
 
-bool add_features_check_parallax(tcv_estimator *e, int n_points, const int *ids, const double *pts, int n_lines, const int *line_ids, const double *lines) {
+bool add_features_check_parallax(tcv_estimator *e, int n_points, const int *ids, const double *pts, const double *aux4, int n_lines, const int *line_ids, const double *lines) {
     const int fc = e->frame_count;
     std::unordered_map<int, int> by_id;
     for (size_t k = 0; k < e->features.size(); k++) by_id[e->features[k].id] = (int)k;
@@ -305,6 +314,7 @@ bool add_features_check_parallax(tcv_estimator *e, int n_points, const int *ids,
             e->features.push_back(f); idx = (int)e->features.size() - 1; by_id[ids[k]] = idx;
         } else { idx = it->second; last_track_num++; }
         e->features[idx].obs.push_back(V3{pts[3 * k], pts[3 * k + 1], pts[3 * k + 2]});
+        if (aux4) e->features[idx].aux.push_back({aux4[4 * k], aux4[4 * k + 1], aux4[4 * k + 2], aux4[4 * k + 3], e->td});      // FeaturePerFrame(point, td) (feature_manager.cpp:215, :271)
     }
     if (e->assoc) {      // the line tracker's (id, end points): addFeaturesCheckParallax :291-311
         std::unordered_map<int, int> by_lid;
@@ -455,18 +465,24 @@ int build_window(tcv_estimator *e) {
     for (size_t k = 0; k < e->features.size(); k++) if (selected(e->features[k])) e->sel.push_back((int)k);
     e->para_feature.resize(std::max<size_t>(1, e->sel.size()));
     for (size_t l = 0; l < e->sel.size(); l++) e->para_feature[l] = 1.0 / e->features[e->sel[l]].depth;
+    if (e->estimate_td) e->para_td[0] = e->td;      // :1533-1534
     e->w_imu.clear(); e->w_imu_i.clear(); e->w_imu_j.clear(); e->w_imu_dev.clear();
     for (int k = 0; k < W; k++)
         if (e->pre[k + 1].sum_dt <= 10.0) {      // estimator.cpp:1726
             e->w_imu.push_back(e->pre[k + 1]); e->w_imu_i.push_back(k); e->w_imu_j.push_back(k + 1);
             e->w_imu_dev.push_back(e->preh[k + 1].get());
         }
-    e->w_pi.clear(); e->w_pj.clear(); e->w_pl.clear(); e->w_pts.clear();
+    e->w_pi.clear(); e->w_pj.clear(); e->w_pl.clear(); e->w_pts.clear(); e->w_aux.clear();
     for (size_t l = 0; l < e->sel.size(); l++) {      // estimator.cpp:1737-1771
         const Feature &f = e->features[e->sel[l]];
         for (size_t k = 1; k < f.obs.size(); k++) {
             e->w_pi.push_back(f.start); e->w_pj.push_back(f.start + (int)k); e->w_pl.push_back((int)l);
             e->w_pts.insert(e->w_pts.end(), f.obs[0].begin(), f.obs[0].end()); e->w_pts.insert(e->w_pts.end(), f.obs[k].begin(), f.obs[k].end());
+            if (e->estimate_td) {      // the constructor arguments of ProjectionTdFactor (:1757-1763): velocities, cur_td, uv.y() of the anchor and of observation k
+                const std::array<double, 5> &a = f.aux[0], &b = f.aux[k];
+                const double x[8] = {a[2], a[3], b[2], b[3], a[4], b[4], a[1], b[1]};
+                e->w_aux.insert(e->w_aux.end(), x, x + 8);
+            }
         }
     }
     e->w_lf.clear(); e->w_ld.clear();
@@ -507,6 +523,7 @@ void fill_desc(const tcv_estimator *e, tcv_window_desc &d, bool marg, int flag) 
     for (int c = 0; c < 3; c++) { d.line_Tic[c] = e->tic[c]; d.gravity[c] = e->cfg.gravity[c]; }
     d.line_exact_jacobian = e->cfg.line_exact_jacobian;
     d.prior = e->prior; d.prior_block_kind = e->w_pk.data(); d.prior_block_index = e->w_pidx.data();
+    if (e->estimate_td) { d.para_td = m->para_td; d.proj_td_aux = marg ? e->m_aux.data() : e->w_aux.data(); d.td_TR = e->td_TR; d.td_ROW = e->td_ROW; }      // :1703-1707
     if (!marg) {
         d.n_imu = (int)e->w_imu.size(); d.imu = e->w_imu.data(); d.imu_frame_i = e->w_imu_i.data(); d.imu_frame_j = e->w_imu_j.data();
         d.imu_device = e->w_imu_dev.empty() ? nullptr : e->w_imu_dev.data();      // (entries may be null: that factor's host copy is used)
@@ -521,7 +538,7 @@ void fill_desc(const tcv_estimator *e, tcv_window_desc &d, bool marg, int flag) 
 
 // factor set and drop sets MarginalizationInfo receives: estimator.cpp:1911-1986 (MARGIN_OLD), :2047-2063 (MARGIN_SECOND_NEW)
 void build_marg(tcv_estimator *e, int flag) {
-    e->m_imu.clear(); e->m_imu_dev.clear(); e->m_imu_i.clear(); e->m_imu_j.clear(); e->m_pi.clear(); e->m_pj.clear(); e->m_pl.clear(); e->m_pts.clear(); e->m_drop.clear();
+    e->m_imu.clear(); e->m_imu_dev.clear(); e->m_imu_i.clear(); e->m_imu_j.clear(); e->m_pi.clear(); e->m_pj.clear(); e->m_pl.clear(); e->m_pts.clear(); e->m_aux.clear(); e->m_drop.clear();
     if (flag == MARGIN_OLD) {
         for (size_t k = 0; k < e->w_imu.size(); k++)
             if (e->w_imu_i[k] == 0 && e->w_imu[k].sum_dt < 10.0) { e->m_imu.push_back(e->w_imu[k]); e->m_imu_dev.push_back(e->w_imu_dev[k]); e->m_imu_i.push_back(0); e->m_imu_j.push_back(e->w_imu_j[k]); }
@@ -530,6 +547,7 @@ void build_marg(tcv_estimator *e, int flag) {
             if (e->w_pi[k] == 0) {
                 e->m_pi.push_back(0); e->m_pj.push_back(e->w_pj[k]); e->m_pl.push_back(e->w_pl[k]);
                 e->m_pts.insert(e->m_pts.end(), e->w_pts.begin() + 6 * k, e->w_pts.begin() + 6 * k + 6);
+                if (e->estimate_td) e->m_aux.insert(e->m_aux.end(), e->w_aux.begin() + 8 * k, e->w_aux.begin() + 8 * k + 8);      // :1970-1979: ProjectionTdFactors on para_Td, which is kept
                 lms.push_back(e->w_pl[k]);
             }
         std::sort(lms.begin(), lms.end()); lms.erase(std::unique(lms.begin(), lms.end()), lms.end());
@@ -546,6 +564,7 @@ void apply_states(tcv_estimator *e) {
     }
     for (int c = 0; c < 3; c++) e->tic[c] = e->para_ex[c];
     e->ric = q2R(e->para_ex + 3);
+    if (e->estimate_td) e->td = e->para_td[0];      // :1601-1602
     for (size_t l = 0; l < e->sel.size(); l++) {
         Feature &f = e->features[e->sel[l]];
         f.depth = 1.0 / e->para_feature[l];
@@ -567,7 +586,8 @@ int take_prior(tcv_estimator *e, tcv_prior *np, int flag) {
         if (addr[k] >= e->para_pose && addr[k] < e->para_pose + (W + 1) * 7) { kind = 0; idx = (int)(addr[k] - e->para_pose) / 7; }
         else if (addr[k] >= e->para_sb && addr[k] < e->para_sb + (W + 1) * 9) { kind = 1; idx = (int)(addr[k] - e->para_sb) / 9; }
         else if (addr[k] == e->para_ex) { kind = 2; idx = 0; }
-        else { tcv::set_error("estimator: kept block is not a pose / speed-bias / extrinsic block"); return TCV_ERR_INVALID; }
+        else if (e->estimate_td && addr[k] == e->para_td) { kind = 3; idx = 0; }      // addr_shift[para_Td[0]] = para_Td[0] (:2035-2038, :2101-2104)
+        else { tcv::set_error("estimator: kept block is not a pose / speed-bias / extrinsic / time-offset block"); return TCV_ERR_INVALID; }
         if (kind < 2) {
             if (flag == MARGIN_OLD) idx -= 1;
             else if (idx == W) idx -= 1;
@@ -592,6 +612,7 @@ int tap_window(tcv_estimator *e) {
     for (size_t k = 0; k < T.imu.size(); k++)
         if (k < e->w_imu_dev.size() && e->w_imu_dev[k]) { const int rc = tcv_preint_export(e->w_imu_dev[k], &T.imu[k]); if (rc != TCV_OK) return rc; }
     T.pi = e->w_pi; T.pj = e->w_pj; T.pl = e->w_pl; T.pts = e->w_pts; T.lf = e->w_lf; T.ld = e->w_ld;
+    T.aux = e->w_aux; T.td_in = e->estimate_td ? e->para_td[0] : 0.0; T.td_out = 0.0;
     std::memcpy(T.Ric, e->w_Ric, sizeof T.Ric);
     T.marg_flag = e->marg_flag;
     T.pk = e->w_pk; T.pidx = e->w_pidx; T.psize.clear(); T.pcol.clear(); T.x0.clear(); T.J0.clear(); T.r0.clear();
@@ -645,6 +666,7 @@ void slide_window(tcv_estimator *e) {
             if (f.start != 0) { f.start -= 1; kept.push_back(std::move(f)); continue; }
             const V3 uv_i = f.obs.front();
             f.obs.erase(f.obs.begin());
+            if (!f.aux.empty()) f.aux.erase(f.aux.begin());
             if (f.obs.size() < 2) continue;
             const V3 pts_j = mv(tr(R1), sub(add(mv(R0, scl(uv_i, f.depth)), P0), P1));
             f.depth = pts_j[2] > 0 ? pts_j[2] : e->cfg.init_depth;
@@ -672,6 +694,7 @@ void slide_window(tcv_estimator *e) {
             if (f.start == W) { f.start -= 1; kept.push_back(std::move(f)); continue; }
             if (f.end() < W - 1) { kept.push_back(std::move(f)); continue; }
             f.obs.erase(f.obs.begin() + (W - 1 - f.start));
+            if (!f.aux.empty()) f.aux.erase(f.aux.begin() + (W - 1 - f.start));
             if (!f.obs.empty()) kept.push_back(std::move(f));
         }
         e->features.swap(kept);
@@ -710,6 +733,7 @@ static void clear_state(tcv_estimator *e) {
     e->have_acc0 = false; e->have_last = false;
     e->acc_0 = e->gyr_0 = e->last_P = V3{0, 0, 0};
     e->para_feature.clear(); e->sel.clear();
+    e->td = e->td0; e->para_td[0] = e->td0; e->staged_aux.clear(); e->staged_n = -1;      // td = TD (estimator.cpp:51, :170)
     e->n_line_obs_total = 0; e->phase = 0; e->opt_failed = 0; e->opt_msg.clear(); e->pend_failed = 0; e->pend_msg.clear();
 }
 extern "C" int tcv_estimator_create(tcv_estimator **out, const tcv_estimator_config *cfg) {
@@ -752,13 +776,37 @@ extern "C" int tcv_estimator_set_line_map(tcv_estimator *e, int n, const double 
     return TCV_OK;
 }
 
+extern "C" int tcv_estimator_set_time_offset(tcv_estimator *e, int estimate_td, double td0, double TR, double ROW) {
+    if (!e) { tcv::set_error("estimator_set_time_offset: bad argument"); return TCV_ERR_INVALID; }
+    if (!(ROW > 0.0) || !std::isfinite(ROW) || !std::isfinite(td0) || !std::isfinite(TR)) { tcv::set_error("estimator_set_time_offset: ROW must be positive (and ROW, td0, TR finite)"); return TCV_ERR_INVALID; }
+    if (e->frame_count != 0 || e->phase != 0 || !e->features.empty()) { tcv::set_error("estimator_set_time_offset: only while the window is empty (after create or reset)"); return TCV_ERR_INVALID; }
+    e->estimate_td = estimate_td != 0; e->td0 = td0; e->td = td0; e->para_td[0] = td0; e->td_TR = TR; e->td_ROW = ROW;
+    return TCV_OK;
+}
+extern "C" int tcv_estimator_stage_point_aux(tcv_estimator *e, int n_points, const double *aux4) {
+    if (!e || n_points < 0 || (n_points > 0 && !aux4)) { tcv::set_error("estimator_stage_point_aux: bad argument"); return TCV_ERR_INVALID; }
+    if (aux4) e->staged_aux.assign(aux4, aux4 + (size_t)4 * n_points); else e->staged_aux.clear();
+    e->staged_n = n_points;
+    return TCV_OK;
+}
+extern "C" int tcv_estimator_get_time_offset(const tcv_estimator *e, double *td) {
+    if (!e || !td) { tcv::set_error("estimator_get_time_offset: bad argument"); return TCV_ERR_INVALID; }
+    *td = e->td;
+    return TCV_OK;
+}
+
 extern "C" int tcv_estimator_begin_frame(tcv_estimator *e, int n_imu, const double *acc, const double *gyr, int n_points, const int *point_ids,
                                          const double *points, int n_lines, const int *line_ids, const double *lines, const double *truth, int *ready) {
     if (!e || !ready || n_imu < 0 || n_points < 0 || n_lines < 0 || (n_points > 0 && (!point_ids || !points)) || (n_lines > 0 && !lines) ||
         (n_lines > 0 && e->assoc && !line_ids) || (n_imu > 0 && (!acc || !gyr))) { tcv::set_error("estimator_begin_frame: bad argument"); return TCV_ERR_INVALID; }
     if (e->phase != 0) { tcv::set_error("estimator_begin_frame: the previous frame has not been optimised and finished"); return TCV_ERR_INVALID; }
+    // the tail of the front end's 7-vector staged for this frame (tcv_estimator_stage_point_aux): consumed here, used with ESTIMATE_TD only
+    const int staged_n = e->staged_n;
+    e->staged_n = -1;
+    if (e->estimate_td && staged_n < 0) { tcv::set_error("estimator_begin_frame: estimate_td is on and no point aux (pixel position, velocity) was staged for this frame (tcv_estimator_stage_point_aux)"); return TCV_ERR_INVALID; }
+    if (e->estimate_td && staged_n != n_points) { tcv::set_error("estimator_begin_frame: " + std::to_string(staged_n) + " points were staged with tcv_estimator_stage_point_aux, the frame has " + std::to_string(n_points)); return TCV_ERR_INVALID; }
     if (acc && gyr) process_imu(e, n_imu, acc, gyr);
-    e->marg_flag = add_features_check_parallax(e, n_points, point_ids, points, n_lines, line_ids, lines) ? MARGIN_OLD : MARGIN_SECOND_NEW;
+    e->marg_flag = add_features_check_parallax(e, n_points, point_ids, points, e->estimate_td ? e->staged_aux.data() : nullptr, n_lines, line_ids, lines) ? MARGIN_OLD : MARGIN_SECOND_NEW;
     const int fc = e->frame_count;
     if (truth) { for (int c = 0; c < 3; c++) { e->Ps[fc][c] = truth[c]; e->Vs[fc][c] = truth[12 + c]; } std::memcpy(e->Rs[fc].data(), truth + 3, sizeof(double) * 9); }
     if (fc < W) {
@@ -1227,6 +1275,7 @@ int apply_windows(tcv_opt_ticket &T) {
             WindowTap &tap = e->tap;
             tap.pose_out.assign(e->para_pose, e->para_pose + (W + 1) * 7); tap.sb_out.assign(e->para_sb, e->para_sb + (W + 1) * 9);
             tap.ex_out.assign(e->para_ex, e->para_ex + 7); tap.feat_out = e->para_feature;
+            tap.td_out = e->estimate_td ? e->para_td[0] : 0.0;
             tap.iterations = T.sum[k].num_iterations; tap.final_cost = T.sum[k].final_cost; tap.applied = 1;
         }
         e->stats.marg_flag = e->marg_flag; e->stats.n_landmarks = (int)e->sel.size(); e->stats.n_proj = (int)e->w_pi.size(); e->stats.n_line = (int)e->w_lf.size();
@@ -1341,6 +1390,16 @@ extern "C" int tcv_estimator_get_window_snapshot(const tcv_estimator *e, tcv_win
     o->prior_block_kind = T.pk.data(); o->prior_block_index = T.pidx.data(); o->prior_block_size = T.psize.data(); o->prior_block_idx = T.pcol.data();
     o->prior_x0 = T.x0.data(); o->prior_J0 = T.J0.data(); o->prior_r0 = T.r0.data();
     o->iterations = T.iterations; o->applied = T.applied; o->final_cost = T.final_cost;
+    return TCV_OK;
+}
+extern "C" int tcv_estimator_get_window_snapshot_td(const tcv_estimator *e, tcv_window_snapshot_td *o) {
+    if (!e || !o) return TCV_ERR_INVALID;
+    const WindowTap &T = e->tap;
+    if (!T.on || !T.have) { tcv::set_error("estimator_get_window_snapshot_td: no snapshot (tap off, or no window optimised since it was switched on)"); return TCV_ERR_INVALID; }
+    std::memset(o, 0, sizeof *o);
+    o->estimate_td = e->estimate_td; o->n_proj = (int)T.pi.size();
+    o->td_in = T.td_in; o->td_out = T.td_out; o->TR = e->td_TR; o->ROW = e->td_ROW;
+    o->proj_td_aux = T.aux.empty() ? nullptr : T.aux.data();
     return TCV_OK;
 }
 extern "C" int tcv_estimator_get_stats(const tcv_estimator *e, tcv_estimator_stats *out) {

@@ -134,6 +134,31 @@ def simulate_stream(seed: int, n_frames: int, max_features: int = 36, max_lines:
     return out
 
 
+def simulate_stream_td(seed: int, n_frames: int, td_true: float, TR: float = 0.0, ROW: float = None, **kw):
+    """`simulate_stream(seed, n_frames, **kw)` (unchanged, same draws) as a front end with a camera-IMU time offset delivers it: the stream
+    gains `point_aux` -- per frame {id: (u, v, velocity x, velocity y)}, the tail of the reference's 7-vector (feature_manager.h:138-147) --
+    and its `points` are moved.  Velocities are what the feature tracker computes on the normalised plane, (cur - prev) / dt between
+    consecutive frames and zero for a new track; u, v are the pixel positions of the (unmoved) points, the rolling-shutter row is v.
+    The observations are then shifted to be first-order consistent at td = td_true for observations stamped cur_td = 0, the construction of
+    `synth.with_time_offset` (projection_td_factor.cpp:50-51 undone): p += (td_true + TR / ROW * (v - ROW / 2)) * velocity.  The stream is
+    open loop: an estimator that stamps later observations with its own td = c (feature_manager.cpp:215, :271) expects its caller to have
+    cut the IMU stream at img_t + c (estimator_node.cpp:143-166), which nobody does here, so those observations are consistent at td_true + c.
+    Also returns td_true, TR, ROW in the stream."""
+    st = simulate_stream(seed, n_frames, **kw)
+    ROW = float(synth.IMG_H if ROW is None else ROW)
+    aux, moved, prev = [], [], {}
+    for pts in st["points"]:
+        a, m = {}, {}
+        for i, p in pts.items():
+            vel = (p[:2] - prev[i][:2]) / synth.DT_KF if i in prev else np.zeros(2)
+            u = synth.FX * p[0] + synth.CX; v = synth.FY * p[1] + synth.CY
+            a[i] = np.array([u, v, vel[0], vel[1]])
+            q = p.copy(); q[:2] += (td_true + TR / ROW * (v - ROW / 2)) * vel
+            m[i] = q
+        aux.append(a); moved.append(m); prev = pts
+    return dict(st, points=moved, point_aux=aux, td_true=float(td_true), TR=float(TR), ROW=ROW)
+
+
 def _front_end(rng, Rk, pk, ps_pool, pe_pool, max_features, max_lines, pixel_sigma, associate):
     """what the feature tracker and the line tracker would deliver along the body poses (Rk, pk): per frame {id: (x, y, 1)}
     tracked points on the normalised plane (a lost track is never re-acquired, new landmarks are spawned in front of the camera
@@ -269,6 +294,10 @@ class Feature:
 
 
 class Replay:
+    """The estimator's per-frame window management in Python, on a pluggable back end (HIP or oracle).  Without ESTIMATE_TD: the online
+    camera-IMU time offset exists in the native estimator only (include/tcv_estimator.h, `NativeLockstep(estimate_td=...)`); a stream of
+    `simulate_stream_td` replayed here is treated as a plain stream (its `point_aux` is ignored)."""
+
     def __init__(self, backend, num_iterations: int = 8, fixed_iterations: bool = False):
         W = WINDOW_SIZE
         self.backend = backend
@@ -811,8 +840,13 @@ class NativeLockstep:
     windows optimised.  Same perturbation draws as `run` / `run_many`."""
 
     def __init__(self, streams, num_iterations: int = 8, fixed_iterations: bool = False, init_sigma=(0.02, 0.005, 0.05), bias_sigma=(0.005, 0.0005),
-                 exact_line_jacobian: bool = False, estimate_extrinsic: bool = True, solver_time: float = 0.0):
-        """solver_time: SOLVER_TIME of the reference's configuration (sensor.yaml:85; 0: no clock)"""
+                 exact_line_jacobian: bool = False, estimate_extrinsic: bool = True, solver_time: float = 0.0,
+                 estimate_td=None, td0: float = 0.0, TR: float = 0.0, ROW: float = None):
+        """solver_time: SOLVER_TIME of the reference's configuration (sensor.yaml:85; 0: no clock).
+        estimate_td, td0, TR, ROW: tcv_estimator_set_time_offset (ESTIMATE_TD, TD, TR, ROW of parameters.cpp:135-138; ROW defaults to the image
+        height) -- None (default): the call is not made at all; a bool, or one entry (bool or None) per stream for a list that mixes both kinds.  A stream
+        that carries `point_aux` (`simulate_stream_td`) has it staged before every begin_frame (tcv_estimator_stage_point_aux), whatever
+        estimate_td says.  `time_offset(si)` reads the estimator's td."""
         import tcv
         self.tcv = tcv
         L = self.L = tcv.lib()
@@ -845,6 +879,13 @@ class NativeLockstep:
         cfg.solver_time = float(solver_time)
         self.streams, self.init_sigma = streams, init_sigma
         self.ests, self.rngs, self.outs = [], [], []
+        self._any_aux = any("point_aux" in st for st in streams)
+        if estimate_td is not None or self._any_aux:      # (bound only when used: a library from before ESTIMATE_TD still loads through TCV_LIB)
+            L.tcv_estimator_set_time_offset.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double]
+            L.tcv_estimator_stage_point_aux.argtypes = [vp, C.c_int, dp]
+        L_td = getattr(L, "tcv_estimator_get_time_offset", None)
+        if L_td is not None:
+            L_td.argtypes = [vp, dp]
         P = self._P
         for st in streams:
             h = vp()
@@ -854,6 +895,9 @@ class NativeLockstep:
             rng = np.random.Generator(np.random.PCG64(0xABCD))
             ba = self._f64(st["ba"] + rng.normal(size=3) * bias_sigma[0]); bg = self._f64(st["bg"] + rng.normal(size=3) * bias_sigma[1])
             tcv.check(L.tcv_estimator_set_biases(h, P(ba), P(bg)))
+            on = estimate_td[len(self.ests) - 1] if isinstance(estimate_td, (list, tuple)) else estimate_td
+            if on is not None:
+                tcv.check(L.tcv_estimator_set_time_offset(h, int(bool(on)), float(td0), float(TR), float(synth.IMG_H if ROW is None else ROW)))
             if "map_lines" in st:
                 ml = self._f64(st["map_lines"]); Rb = self._f64(st["Rbw"]).reshape(9); Tb = self._f64(st["Tbw"])
                 tcv.check(L.tcv_estimator_set_line_map(h, ml.shape[0], P(ml), P(Rb), P(Tb)))
@@ -905,7 +949,10 @@ class NativeLockstep:
         P, ip = self._P, self.ip
         args = (0 if acc is None else acc.shape[0] - 1, None if acc is None else P(acc), None if gyr is None else P(gyr), len(ids), ids.ctypes.data_as(ip), P(pv),
                 len(ln), lid.ctypes.data_as(ip), P(lv))
-        return args, (acc, gyr, ids, pv, lid, lv)
+        if "point_aux" not in st:
+            return args, (acc, gyr, ids, pv, lid, lv)
+        aux = f64(np.array([st["point_aux"][k][i] for i in pts.keys()]).reshape(-1, 4))      # (u, v, velocity x, y) in the order of point_ids
+        return args, (acc, gyr, ids, pv, lid, lv, aux)
 
     @staticmethod
     def _f64(a):
@@ -973,6 +1020,8 @@ class NativeLockstep:
         live, arr_all, rec, rdy, keep = self._batches.pop(k, None) or self._frame_batch(k)
         if not live:
             return
+        if self._any_aux:
+            self._stage_aux(live, keep)
         tcv.check(L.tcv_estimators_begin_frames(arr_all, len(live), rec, rdy, None))
         ready = [si for j, si in enumerate(live) if rdy[j]]
         t_b = time.perf_counter()
@@ -984,6 +1033,20 @@ class NativeLockstep:
         tcv.check(L.tcv_estimators_optimize_begin(arr, len(ready), C.byref(ticket)))
         self.host_s[1] += time.perf_counter() - t_b
         self._pending = (k, ready, arr, ticket, keep)
+
+    def _stage_aux(self, live, keep):
+        """tcv_estimator_stage_point_aux for the streams of this frame that carry point_aux"""
+        for si, (own, _) in zip(live, keep):
+            if len(own) < 7:
+                continue
+            aux = own[6]
+            self.tcv.check(self.L.tcv_estimator_stage_point_aux(self.ests[si], aux.shape[0], self._P(aux)))
+
+    def time_offset(self, si: int = 0) -> float:
+        """Estimator::td of stream si after its last applied window (tcv_estimator_get_time_offset)"""
+        td = C.c_double()
+        self.tcv.check(self.L.tcv_estimator_get_time_offset(self.ests[si], C.byref(td)))
+        return td.value
 
     def step_end(self) -> int:
         """second half: waits for the states, applies them (tcv_estimators_optimize_end), finish_frame of every stream; returns the number of windows"""
