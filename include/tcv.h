@@ -200,6 +200,16 @@ int tcv_problem_from_window(const tcv_window_desc *w, tcv_problem **out);
 /* Names the blocks that are the window's frames (para_Pose[i], para_SpeedBias[i], estimator.h:166-167); only
  * tcv_batch_gauge_fix needs it.  tcv_problem_from_window() does this implicitly. */
 int tcv_problem_set_frames(tcv_problem *p, int n_frames, double *const *pose, double *const *speedbias);
+/* double2vector's relocalisation tail (estimator.cpp:1606-1624) for a problem that carries relo_Pose (:1854-1886: added with
+ * tcv_problem_add_parameter_block(.., 7, TCV_PARAM_POSE) and one tcv_problem_add_projection_factor per matched landmark): names the block,
+ * relo_frame_local_index and prev_relo_t / prev_relo_r (row-major) of setReloFrame (:2261-2279).  TCV_ERR_INVALID (tcv_last_error says
+ * which) when relo_pose is not a size-7 pose block of the problem, when it is one of the frame poses, when the problem has no frame table
+ * (tcv_problem_set_frames) or when frame_local_index lies outside [0, n_frames).
+ * A batch that holds such a problem: tcv_batch_solve does not fuse the gauge fix whatever tcv_batch_set_fused_gauge_fix said (the tail
+ * needs the un-fixed pose 0; the stand-alone kernel gives the same bits), tcv_batch_gauge_fix computes the window's tcv_relo_result in
+ * front of the fix, every download of the states brings it to the host in the same round trip, tcv_batch_get_relocalization reads it.
+ * relo_pose itself comes back as the solver left it, un-fixed: the reference never writes relo_Pose back either. */
+int tcv_problem_set_relocalization(tcv_problem *p, double *relo_pose, int frame_local_index, const double prev_relo_t[3], const double prev_relo_r[9]);
 int tcv_problem_num_parameter_blocks(const tcv_problem *p);
 int tcv_problem_num_residual_blocks(const tcv_problem *p);
 int tcv_problem_num_residuals(const tcv_problem *p);
@@ -304,6 +314,20 @@ int tcv_batch_download_states_brief(tcv_batch *b, int *num_iterations, int *term
  * and writes the states into the callers' blocks.  Between the two calls the parameter blocks must not be read. */
 int tcv_batch_download_states_begin(tcv_batch *b, void *hip_stream);
 int tcv_batch_download_states_end(tcv_batch *b, int *num_iterations, int *termination, double *final_cost);
+/* What double2vector's relocalisation tail leaves behind (estimator.cpp:1606-1620; matrices row-major, quaternion x y z w, angles in
+ * degrees as in utility.h): relo_r / relo_t = the gauge-fixed relo_Pose; drift_correct_yaw = yaw(prev_relo_r) - yaw(relo_r),
+ * drift_correct_r = ypr2R(drift_correct_yaw, 0, 0), drift_correct_t = prev_relo_t - drift_correct_r relo_t; relo_relative_t / _q / _yaw =
+ * the matched frame in the loop-closure frame (yaw through Utility::normalizeAngle).  valid = 0 (everything else zero): the window has
+ * no relocalisation, or its solve ended in FAILURE. */
+typedef struct tcv_relo_result { int valid, pad_; double relo_r[9], relo_t[3], drift_correct_r[9], drift_correct_t[3],
+                                 relo_relative_t[3], relo_relative_q[4], relo_relative_yaw, drift_correct_yaw; } tcv_relo_result;
+/* the record of one window from the host copy that came with the states; TCV_ERR_INVALID before they have been downloaded (for a batch
+ * with relocalisation windows: downloaded behind tcv_batch_gauge_fix) */
+int tcv_batch_get_relocalization(tcv_batch *b, int window, tcv_relo_result *out);
+/* the same tail for n <= 4096 independent cases from host arrays (R0 9n, P0 3n: Rs[0] / Ps[0] before the solve; pose0, pose_l, relo_pose 7n:
+ * the solved, un-fixed para_Pose[0], para_Pose[relo_frame_local_index], relo_Pose; prev_relo_t 3n, prev_relo_r 9n): the twin of tcv_gauge_fix */
+int tcv_relocalization_fix(int n, const double *R0, const double *P0, const double *pose0, const double *pose_l,
+                           const double *relo_pose, const double *prev_relo_t, const double *prev_relo_r, tcv_relo_result *out);
 int tcv_batch_get_prior(tcv_batch *b, int window, tcv_prior **out);
 /* every window's prior in one call (n = the batch size): out[k] as tcv_batch_get_prior(b, k, &out[k]) would return it; the host copies are
  * made by several host threads.  On an error nothing is returned (out[] is all NULL). */

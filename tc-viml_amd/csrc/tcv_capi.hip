@@ -23,6 +23,7 @@
 #include "tcv_eval.h"
 #include "tcv_factors.h"
 #include "tcv_host.h"
+#include "tcv_relo.h"      // RELO_REC: the relocalisation record that rides with the states
 
 extern "C" int tcv_launch_solve(const tcv::SolveArgs *args, int grid, int nthreads, size_t lds_bytes, void *stream);
 extern "C" int tcv_solve_scratch_doubles(void);
@@ -464,6 +465,20 @@ extern "C" int tcv_problem_set_frames(tcv_problem *p, int n_frames, double *cons
     p->frame_pose = fp; p->frame_sb = fs;
     return TCV_OK;
 }
+// relo_Pose of estimator.cpp:1854-1886 and what double2vector's tail (:1606-1624) needs besides the solved states: relo_frame_local_index,
+// prev_relo_t / prev_relo_r.  The block itself and its ProjectionFactors were added before (tcv_problem_add_parameter_block / _projection_factor).
+extern "C" int tcv_problem_set_relocalization(tcv_problem *p, double *relo_pose, int frame_local_index, const double prev_relo_t[3], const double prev_relo_r[9]) {
+    if (!p || !prev_relo_t || !prev_relo_r) { set_error("set_relocalization: bad argument"); return TCV_ERR_INVALID; }
+    const int b = block_of(p, relo_pose);
+    if (b < 0 || p->blocks[b].size != 7 || p->blocks[b].kind != KIND_POSE) { set_error("set_relocalization: relo_pose is not a pose block (size 7, TCV_PARAM_POSE) of the problem"); return TCV_ERR_INVALID; }
+    if (p->frame_pose.empty()) { set_error("set_relocalization: the problem carries no frame table (tcv_problem_set_frames)"); return TCV_ERR_INVALID; }
+    for (int f : p->frame_pose) if (f == b) { set_error("set_relocalization: relo_pose is one of the frame poses"); return TCV_ERR_INVALID; }
+    if (frame_local_index < 0 || frame_local_index >= (int)p->frame_pose.size()) { set_error("set_relocalization: frame_local_index outside [0, n_frames)"); return TCV_ERR_INVALID; }
+    for (int i = 0; i < 12; i++) if (!std::isfinite(i < 3 ? prev_relo_t[i] : prev_relo_r[i - 3])) { set_error("set_relocalization: prev_relo_t / prev_relo_r not finite"); return TCV_ERR_INVALID; }
+    p->relo_block = b; p->relo_local = frame_local_index;
+    std::memcpy(p->relo_prev, prev_relo_t, 24); std::memcpy(p->relo_prev + 3, prev_relo_r, 72);
+    return TCV_OK;
+}
 extern "C" int tcv_problem_num_parameter_blocks(const tcv_problem *p) { return p ? (int)p->blocks.size() : 0; }
 extern "C" int tcv_problem_num_residual_blocks(const tcv_problem *p) {
     return p ? (int)(p->imu.size() + p->proj.size() + p->line.size() + p->prior.size()) : 0;
@@ -761,6 +776,7 @@ static void batch_free(tcv_batch *b) {
     tcv::dev_free(b->d_input);      // (d_dpool, d_win, d_plans, d_plan_base, d_ipool point into it)
     tcv::dev_free(b->d_imublk); tcv::dev_free(b->d_spill); tcv::dev_free(b->d_sqrt_out);
     tcv::dev_free(b->d_coop_ctl); tcv::dev_free(b->d_coop_x); tcv::dev_free(b->d_coop_exp);
+    if (b->d_relo) tcv::dev_free(b->d_relo);
     tcv::dev_free(b->d_zero); tcv::dev_free(b->d_state);      // (d_delta, d_scratch, d_summary, d_prof live inside d_zero)
     b->d_zero = nullptr; b->d_prof = nullptr; b->d_delta = nullptr; b->d_scratch = nullptr; b->d_summary = nullptr;
     if (b->ev0) hipEventDestroy(b->ev0);
@@ -1143,10 +1159,12 @@ extern "C" int tcv_batch_create(tcv_batch **out, tcv_problem *const *problems, t
         if ((e0 = alloc_work_buffers(b, &zero_bytes)) != hipSuccess) return hip_fail(e0, "hipMalloc");
         t_alloc = std::chrono::steady_clock::now();
         e0 = hipMemsetAsync(b->d_zero, 0, zero_bytes, ust);
+        const int rc_relo = tcv_relo_attach(b, ust);      // (relocalisation windows: their table and record buffer; nothing otherwise)
         // the batch is complete on the device before any stream uses it (and the upload is drained before its staging buffer is released, whatever the memsets returned)
         const hipError_t es = up.wait();
         if (e0 == hipSuccess) e0 = es;
         b->d_input = up.take_dev();      // (d_dpool, d_win, d_plans, d_plan_base, d_ipool point into it)
+        if (rc_relo != TCV_OK) return rc_relo;
     }
     tcv::flush_deferred(ust);      // (this thread just waited for its stream)
     if (e0 != hipSuccess) return hip_fail(e0, "upload of the batch");
@@ -1226,7 +1244,8 @@ extern "C" int tcv_batch_solve(tcv_batch *b, const tcv_solver_options *o, void *
     a.imublk = b->d_imublk; a.spill = b->d_spill; a.spill_stride = b->spill_stride;
     a.max_ticks = 0;
     a.sqrt_out = b->d_sqrt_out;
-    a.gauge_fix = b->fuse_gauge ? 1 : 0;
+    // (a batch with a relocalisation window never fuses: double2vector's tail needs the un-fixed pose 0, tcv_relo.hip; the stand-alone kernel gives the same bits)
+    a.gauge_fix = b->fuse_gauge && b->n_relo == 0 ? 1 : 0;
     // cooperative plans also run on the single-workgroup kernel (workgroups_per_window = 1): same chunks, same additions, same bits
     bool coop = b->coop_h > 0 && o->workgroups_per_window != 1;
     if (coop && b->coop_claim == 0)      // (a claim still held: the previous cooperative solve of this batch, same stream order, same rotation)
@@ -1254,6 +1273,7 @@ extern "C" int tcv_batch_solve(tcv_batch *b, const tcv_solver_options *o, void *
     if (rc != 0) return hip_fail((hipError_t)rc, "solve kernel launch");
     HIPCHK(hipEventRecord(b->ev1, st));
     b->solved = true;
+    b->relo_done = false;
     b->gauge_in_solve = a.gauge_fix != 0;
     if (a.gauge_fix) b->gauge_fixed = true;
     return TCV_OK;
@@ -1290,6 +1310,7 @@ static void scatter_states(const tcv_batch *b) {
 }
 extern "C" int tcv_batch_download_states(tcv_batch *b) {
     if (!b || !b->solved) return TCV_ERR_INVALID;
+    if (b->n_relo > 0) return tcv_batch_download_states_brief(b, nullptr, nullptr, nullptr);      // (the relocalisation records ride with the states, and their `valid` needs the terminations)
     if (b->pending) if (int rc = tcv_batch_synchronize(b)) return rc;
     b->h_state.resize((size_t)b->n * b->state_stride);
     if (int rc = tcv::staged_download(b->h_state.data(), b->d_state, sizeof(double) * b->h_state.size(), "download of the states")) return rc;
@@ -1308,16 +1329,20 @@ extern "C" int tcv_batch_download_states_begin(tcv_batch *b, void *hip_stream) {
     if (int rc = tcv_batch_enter_stream(b, hip_stream)) return rc;
     b->h_state.resize((size_t)b->n * b->state_stride);
     const size_t sbytes = sizeof(double) * b->h_state.size(), hbytes = (size_t)32 * b->n;
+    const bool relo = b->n_relo > 0 && b->relo_done;      // the relocalisation records of tcv_batch_gauge_fix (tcv_relo.hip) in the same round trip
+    const size_t rbytes = relo ? sizeof(double) * (size_t)tcv::RELO_REC * b->n_relo : 0;
     static_assert(offsetof(DevSummary, final_cost) == 24 && offsetof(DevSummary, num_iterations) == 0 && offsetof(DevSummary, termination) == 4, "head of DevSummary");
-    char *hs = (char *)host_staging_acquire(sbytes + hbytes);
+    char *hs = (char *)host_staging_acquire(sbytes + hbytes + rbytes);
     if (!hs) { set_error("hipHostMalloc (download staging) failed"); return TCV_ERR_HIP; }
     hipError_t e_ = hipSuccess;
     if (!b->ev_dl) e_ = hipEventCreateWithFlags(&b->ev_dl, hipEventDisableTiming);
     if (e_ == hipSuccess) e_ = hipMemcpyAsync(hs, b->d_state, sbytes, hipMemcpyDeviceToHost, st);
     if (e_ == hipSuccess) e_ = hipMemcpy2DAsync(hs + sbytes, 32, b->d_summary, sizeof(DevSummary), 32, (size_t)b->n, hipMemcpyDeviceToHost, st);
+    if (e_ == hipSuccess && relo) e_ = hipMemcpyAsync(hs + sbytes + hbytes, b->d_relo, rbytes, hipMemcpyDeviceToHost, st);
     if (e_ == hipSuccess) e_ = hipEventRecord(b->ev_dl, st);
     if (e_ != hipSuccess) { (void)tcv::stream_wait(st); host_staging_release(hs); return hip_fail(e_, "download of the states"); }
     b->dl_staging = hs;
+    b->relo_in_dl = relo;
     return TCV_OK;
 }
 extern "C" int tcv_batch_download_states_end(tcv_batch *b, int *num_iterations, int *termination, double *final_cost) {
@@ -1335,6 +1360,17 @@ extern "C" int tcv_batch_download_states_end(tcv_batch *b, int *num_iterations, 
             if (termination) termination[w] = tm;
             if (final_cost) final_cost[w] = fc;
         }
+        if (b->relo_in_dl) {
+            b->h_relo.resize((size_t)tcv::RELO_REC * b->n_relo);
+            std::memcpy(b->h_relo.data(), hs + sbytes + (size_t)32 * b->n, sizeof(double) * b->h_relo.size());
+            b->relo_valid.assign(b->n_relo, 0);
+            for (int k = 0; k < b->n_relo; k++) {
+                int tm;
+                std::memcpy(&tm, hs + sbytes + (size_t)32 * b->relo_win[k] + 4, 4);
+                b->relo_valid[k] = tm != 5;      // FAILURE: the window's states are not a solution, neither is its record
+            }
+        }
+        b->relo_have = b->relo_in_dl;
     }
     host_staging_release(hs);
     b->dl_staging = nullptr;

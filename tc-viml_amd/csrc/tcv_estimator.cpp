@@ -195,6 +195,13 @@ struct WindowTap {
     bool on = false, have = false;
     std::vector<double> pose_in, sb_in, ex_in, feat_in, pose_out, sb_out, ex_out, feat_out, pts, ld, x0, J0, r0, aux;
     double td_in = 0, td_out = 0;
+    // relocalisation part (tcv_window_snapshot_relo)
+    bool has_relo = false;
+    int relo_local = 0, relo_frame_index = 0, relo_frame_serial = 0;
+    double relo_in[7], relo_out[7], relo_prev[12];
+    std::vector<int> r_pi, r_pl;
+    std::vector<double> r_pts;
+    tcv_relo_result relo_result;
     std::vector<tcv_imu_preintegration> imu;
     std::vector<int> imu_i, imu_j, pi, pj, pl, lf, pk, pidx, psize, pcol;
     double Ric[9];
@@ -261,6 +268,22 @@ struct tcv_estimator {
     std::vector<double> staged_aux;          // tcv_estimator_stage_point_aux: n x 4 for the next begin_frame
     int staged_n = -1;                       // -1: nothing staged
     std::vector<double> w_aux, m_aux;        // proj_td_aux of the window / of its marginalisation problem (n_proj x 8)
+    // relocalisation (tcv_estimator_relo.h).  Frame serials stand in for Headers[i].stamp; the request of setReloFrame (estimator.cpp:2261-2279)
+    // waits for the next optimised window, whose relo_Pose block and factors (:1854-1886) are the r_* lists; relo_out is what the last
+    // applied relocalisation window left (:1606-1620)
+    int next_serial = 0;
+    int serials[W + 1];                      // serial of the frame in every slot, -1: none
+    bool relo_pending = false;
+    int relo_serial = -1, relo_frame_index = 0, relo_local = -1;
+    std::vector<double> relo_match;          // n x 3: x, y, feature id (ascending)
+    double relo_prev[12];                    // prev_relo_t | prev_relo_r
+    double relo_pose[7] = {0, 0, 0, 0, 0, 0, 1};      // relo_Pose: a parameter block of the window (identified by address)
+    bool w_relo = false;                     // the current window carries it
+    int w_relo_local = -1, w_relo_frame_index = 0, w_relo_serial = -1;
+    double w_relo_prev[12];
+    std::vector<int> r_pi, r_pl;             // start_frame and feature_index of every relocalisation factor
+    std::vector<double> r_pts;               // pts_i | pts_j
+    tcv_estimator_relo relo_out;
     int pend_failed = 0;                     // != TCV_OK: the previous frame's (deferred) marginalisation could not be launched: this frame's window is solved without
     std::string pend_msg;                    // its prior, nothing of it is applied and finish_frame reports the failure (the caller resets, like after failureDetection)
 };
@@ -485,6 +508,30 @@ int build_window(tcv_estimator *e) {
             }
         }
     }
+    // relocalisation (:1854-1886): relo_Pose and one ProjectionFactor per matched feature that starts at or before the matched frame.  The
+    // match list is walked once, in the order of the feature list, like :1870-1874 -- with an end check the reference does not have
+    e->w_relo = false; e->r_pi.clear(); e->r_pl.clear(); e->r_pts.clear();
+    if (e->relo_pending) {
+        e->relo_pending = false;      // this window consumes the request, applied or not
+        const size_t nm = e->relo_match.size() / 3;
+        size_t r = 0;
+        for (size_t l = 0; l < e->sel.size(); l++) {
+            const Feature &f = e->features[e->sel[l]];
+            if (f.start > e->relo_local) continue;
+            while (r < nm && (int)e->relo_match[3 * r + 2] < f.id) r++;
+            if (r < nm && (int)e->relo_match[3 * r + 2] == f.id) {
+                e->r_pi.push_back(f.start); e->r_pl.push_back((int)l);
+                e->r_pts.insert(e->r_pts.end(), f.obs[0].begin(), f.obs[0].end());
+                const double pj[3] = {e->relo_match[3 * r], e->relo_match[3 * r + 1], 1.0};
+                e->r_pts.insert(e->r_pts.end(), pj, pj + 3);
+                r++;
+            }
+        }
+        if (!e->r_pi.empty()) {
+            e->w_relo = true; e->w_relo_local = e->relo_local; e->w_relo_frame_index = e->relo_frame_index; e->w_relo_serial = e->relo_serial;
+            std::memcpy(e->w_relo_prev, e->relo_prev, sizeof e->w_relo_prev);
+        }
+    }
     e->w_lf.clear(); e->w_ld.clear();
     e->n_line_obs_total = 0;
     if (!e->assoc) {
@@ -613,6 +660,11 @@ int tap_window(tcv_estimator *e) {
         if (k < e->w_imu_dev.size() && e->w_imu_dev[k]) { const int rc = tcv_preint_export(e->w_imu_dev[k], &T.imu[k]); if (rc != TCV_OK) return rc; }
     T.pi = e->w_pi; T.pj = e->w_pj; T.pl = e->w_pl; T.pts = e->w_pts; T.lf = e->w_lf; T.ld = e->w_ld;
     T.aux = e->w_aux; T.td_in = e->estimate_td ? e->para_td[0] : 0.0; T.td_out = 0.0;
+    T.has_relo = e->w_relo; T.r_pi = e->r_pi; T.r_pl = e->r_pl; T.r_pts = e->r_pts;
+    T.relo_local = e->w_relo_local; T.relo_frame_index = e->w_relo_frame_index; T.relo_frame_serial = e->w_relo_serial;
+    std::memset(T.relo_out, 0, sizeof T.relo_out); std::memset(&T.relo_result, 0, sizeof T.relo_result);
+    if (e->w_relo) { std::memcpy(T.relo_in, e->relo_pose, sizeof T.relo_in); std::memcpy(T.relo_prev, e->w_relo_prev, sizeof T.relo_prev); }
+    else { std::memset(T.relo_in, 0, sizeof T.relo_in); std::memset(T.relo_prev, 0, sizeof T.relo_prev); }
     std::memcpy(T.Ric, e->w_Ric, sizeof T.Ric);
     T.marg_flag = e->marg_flag;
     T.pk = e->w_pk; T.pidx = e->w_pidx; T.psize.clear(); T.pcol.clear(); T.x0.clear(); T.J0.clear(); T.r0.clear();
@@ -652,11 +704,13 @@ void slide_window(tcv_estimator *e) {
             e->Ps[i] = e->Ps[i + 1]; e->Rs[i] = e->Rs[i + 1]; e->Vs[i] = e->Vs[i + 1]; e->Bas[i] = e->Bas[i + 1]; e->Bgs[i] = e->Bgs[i + 1];
             // (moves, not copies: this runs once per frame and estimator on the host's critical path; slot W is refilled right below --
             // except the line bookkeeping, whose slot W keeps its content: WorldLinesInFOV[W] = WorldLinesInFOV[W-1], :2158)
+            e->serials[i] = e->serials[i + 1];
             e->bufs[i] = std::move(e->bufs[i + 1]); e->pre[i] = e->pre[i + 1]; e->preh[i] = std::move(e->preh[i + 1]); e->pre_valid[i] = e->pre_valid[i + 1];
             if (i + 1 < W) { e->line_obs[i] = std::move(e->line_obs[i + 1]); e->fov[i] = std::move(e->fov[i + 1]); }
             else { e->line_obs[i] = e->line_obs[i + 1]; e->fov[i] = e->fov[i + 1]; }
         }
         e->pre_valid[W] = false;
+        e->serials[W] = -1;
         new_buf(e, W);
         // slideWindowOld (:2242-2259) -> removeBackShiftDepth (feature_manager.cpp:559-616)
         const M3 R0 = mm(back_R0, e->ric), R1 = mm(e->Rs[0], e->ric);
@@ -687,6 +741,7 @@ void slide_window(tcv_estimator *e) {
         e->pre_valid[W - 1] = false;
         e->Ps[W - 1] = e->Ps[W]; e->Rs[W - 1] = e->Rs[W]; e->Vs[W - 1] = e->Vs[W]; e->Bas[W - 1] = e->Bas[W]; e->Bgs[W - 1] = e->Bgs[W];
         e->line_obs[W - 1] = e->line_obs[W];
+        e->serials[W - 1] = e->serials[W]; e->serials[W] = -1;
         new_buf(e, W);
         e->pre_valid[W] = false;
         std::vector<Feature> kept;                     // slideWindowNew -> removeFront(frame_count) (feature_manager.cpp:655-675)
@@ -735,6 +790,12 @@ static void clear_state(tcv_estimator *e) {
     e->para_feature.clear(); e->sel.clear();
     e->td = e->td0; e->para_td[0] = e->td0; e->staged_aux.clear(); e->staged_n = -1;      // td = TD (estimator.cpp:51, :170)
     e->n_line_obs_total = 0; e->phase = 0; e->opt_failed = 0; e->opt_msg.clear(); e->pend_failed = 0; e->pend_msg.clear();
+    // relocalization_info = 0, drift_correct_r = Identity, drift_correct_t = Zero (estimator.cpp:185-188); the serials restart
+    e->next_serial = 0;
+    for (int i = 0; i <= W; i++) e->serials[i] = -1;
+    e->relo_pending = false; e->relo_match.clear(); e->w_relo = false; e->r_pi.clear(); e->r_pl.clear(); e->r_pts.clear();
+    std::memset(&e->relo_out, 0, sizeof e->relo_out);
+    e->relo_out.drift_correct_r[0] = e->relo_out.drift_correct_r[4] = e->relo_out.drift_correct_r[8] = 1.0;
 }
 extern "C" int tcv_estimator_create(tcv_estimator **out, const tcv_estimator_config *cfg) {
     if (!out || !cfg || !(cfg->imu_dt > 0) || !(cfg->focal_length > 0) || cfg->num_iterations < 1) { tcv::set_error("estimator_create: bad configuration"); return TCV_ERR_INVALID; }
@@ -795,6 +856,44 @@ extern "C" int tcv_estimator_get_time_offset(const tcv_estimator *e, double *td)
     return TCV_OK;
 }
 
+extern "C" int tcv_estimator_frame_serial(const tcv_estimator *e, int *next_serial, int *window_serials, int *n_slots) {
+    if (!e) { tcv::set_error("estimator_frame_serial: bad argument"); return TCV_ERR_INVALID; }
+    if (next_serial) *next_serial = e->next_serial;
+    int n = 0;
+    for (int i = 0; i <= W; i++) { if (window_serials) window_serials[i] = e->serials[i]; n += e->serials[i] >= 0 ? 1 : 0; }
+    if (n_slots) *n_slots = n;
+    return TCV_OK;
+}
+// Estimator::setReloFrame (estimator.cpp:2261-2279)
+extern "C" int tcv_estimator_set_relo_frame(tcv_estimator *e, int frame_serial, int frame_index, int n_match, const double *match_points,
+                                            const double prev_relo_t[3], const double prev_relo_r[9], int *accepted) {
+    if (accepted) *accepted = 0;
+    if (!e || !accepted || n_match < 0 || (n_match > 0 && !match_points) || !prev_relo_t || !prev_relo_r) { tcv::set_error("estimator_set_relo_frame: bad argument"); return TCV_ERR_INVALID; }
+    if (e->phase != 0) { tcv::set_error("estimator_set_relo_frame: only between frames (after finish_frame, before the next begin_frame)"); return TCV_ERR_INVALID; }
+    if (e->estimate_td) { tcv::set_error("estimator_set_relo_frame: not with estimate_td on (a problem holds either ProjectionFactors or ProjectionTdFactors)"); return TCV_ERR_INVALID; }
+    for (int k = 0; k < 3 * n_match; k++) if (!std::isfinite(match_points[k])) { tcv::set_error("estimator_set_relo_frame: match_points not finite"); return TCV_ERR_INVALID; }
+    for (int k = 1; k < n_match; k++)
+        if (!((int)match_points[3 * k + 2] > (int)match_points[3 * k - 1])) { tcv::set_error("estimator_set_relo_frame: match_points must be strictly ascending in feature id"); return TCV_ERR_INVALID; }
+    for (int k = 0; k < 12; k++) if (!std::isfinite(k < 3 ? prev_relo_t[k] : prev_relo_r[k - 3])) { tcv::set_error("estimator_set_relo_frame: prev_relo_t / prev_relo_r not finite"); return TCV_ERR_INVALID; }
+    if (frame_serial < 0) return TCV_OK;
+    for (int i = 0; i < W; i++) {      // :2269: the newest slot is not searched
+        if (e->serials[i] != frame_serial) continue;
+        e->relo_pending = true; e->relo_serial = frame_serial; e->relo_frame_index = frame_index; e->relo_local = i;
+        e->relo_match.assign(match_points, match_points + (size_t)3 * n_match);
+        std::memcpy(e->relo_prev, prev_relo_t, 24); std::memcpy(e->relo_prev + 3, prev_relo_r, 72);
+        for (int c = 0; c < 3; c++) e->relo_pose[c] = e->Ps[i][c];      // the slot's pose as vector2double writes it (:1494-1503; the reference: see the header)
+        R2q(e->Rs[i], e->relo_pose + 3);
+        *accepted = 1;
+        break;
+    }
+    return TCV_OK;
+}
+extern "C" int tcv_estimator_get_relocalization(const tcv_estimator *e, tcv_estimator_relo *out) {
+    if (!e || !out) { tcv::set_error("estimator_get_relocalization: bad argument"); return TCV_ERR_INVALID; }
+    *out = e->relo_out;
+    return TCV_OK;
+}
+
 extern "C" int tcv_estimator_begin_frame(tcv_estimator *e, int n_imu, const double *acc, const double *gyr, int n_points, const int *point_ids,
                                          const double *points, int n_lines, const int *line_ids, const double *lines, const double *truth, int *ready) {
     if (!e || !ready || n_imu < 0 || n_points < 0 || n_lines < 0 || (n_points > 0 && (!point_ids || !points)) || (n_lines > 0 && !lines) ||
@@ -805,6 +904,7 @@ extern "C" int tcv_estimator_begin_frame(tcv_estimator *e, int n_imu, const doub
     e->staged_n = -1;
     if (e->estimate_td && staged_n < 0) { tcv::set_error("estimator_begin_frame: estimate_td is on and no point aux (pixel position, velocity) was staged for this frame (tcv_estimator_stage_point_aux)"); return TCV_ERR_INVALID; }
     if (e->estimate_td && staged_n != n_points) { tcv::set_error("estimator_begin_frame: " + std::to_string(staged_n) + " points were staged with tcv_estimator_stage_point_aux, the frame has " + std::to_string(n_points)); return TCV_ERR_INVALID; }
+    e->serials[e->frame_count] = e->next_serial++;      // (the frame's name for tcv_estimator_set_relo_frame: Headers[frame_count] = header)
     if (acc && gyr) process_imu(e, n_imu, acc, gyr);
     e->marg_flag = add_features_check_parallax(e, n_points, point_ids, points, e->estimate_td ? e->staged_aux.data() : nullptr, n_lines, line_ids, lines) ? MARGIN_OLD : MARGIN_SECOND_NEW;
     const int fc = e->frame_count;
@@ -926,6 +1026,7 @@ struct tcv_opt_ticket {
     std::vector<int> ndrop;
     std::vector<tcv_solver_summary> sum;
     std::vector<tcv_prior *> newp;
+    std::vector<tcv_relo_result> relo;   // per window: its relocalisation record (valid = 0: none), read with the states
     std::vector<int> est_rc;          // per estimator: TCV_ERR_NUMERIC when its own window failed
     std::string est_msg;
     tcv_batch *b = nullptr;
@@ -1058,6 +1159,15 @@ int build_marg_problem(tcv_opt_ticket &T, int k) {
     T.drops[k] = e->m_drop.data(); T.ndrop[k] = (int)e->m_drop.size();
     return rc;
 }
+// relo_Pose and its factors behind the window's own (estimator.cpp:1854-1886), then what double2vector's tail needs (:1606-1624)
+int add_relocalization(tcv_estimator *e, tcv_problem *p, double sqrt_info, double loss_a) {
+    int rc = tcv_problem_add_parameter_block(p, e->relo_pose, 7, TCV_PARAM_POSE);
+    for (size_t k = 0; k < e->r_pi.size() && rc == TCV_OK; k++)
+        rc = tcv_problem_add_projection_factor(p, e->r_pts.data() + 6 * k, e->r_pts.data() + 6 * k + 3, sqrt_info, loss_a, e->para_pose + 7 * e->r_pi[k], e->relo_pose,
+                                               e->para_ex, e->para_feature.data() + e->r_pl[k]);
+    if (rc == TCV_OK) rc = tcv_problem_set_relocalization(p, e->relo_pose, e->w_relo_local, e->w_relo_prev, e->w_relo_prev + 3);
+    return rc;
+}
 // every window's problem.  Host priors: a marginalising window's second problem in the same task; priors on the device: the batch is created
 // without them, they are built and attached while the solve runs (attach_marginalization)
 void build_problems(tcv_opt_ticket &T) {
@@ -1065,7 +1175,8 @@ void build_problems(tcv_opt_ticket &T) {
         tcv_estimator *e = T.es[k];
         tcv_window_desc d;
         fill_desc(e, d, false, e->marg_flag);
-        const int rc = tcv_problem_from_window(&d, &T.P[k]);
+        int rc = tcv_problem_from_window(&d, &T.P[k]);
+        if (rc == TCV_OK && e->w_relo) rc = add_relocalization(e, T.P[k], d.proj_sqrt_info, d.proj_loss_a);
         return rc == TCV_OK && T.dm[k] && T.host_priors ? build_marg_problem(T, k) : rc;
     }));
 }
@@ -1186,6 +1297,17 @@ void download_to_host(tcv_opt_ticket &T) {
     if (T.rc == TCV_OK) T.rc = download_states(T, tcv_batch_download_states_brief);
     if (T.rc == TCV_OK && T.any_marg) T.rc = tcv_batch_download_priors_compact(T.b);
 }
+// the relocalisation records came with the states (tcv_batch_download_states_end / _brief): taken before the batch is handed on or destroyed
+void collect_relocalizations(tcv_opt_ticket &T) {
+    bool any = false;
+    for (const tcv_estimator *e : T.es) any = any || e->w_relo;
+    if (!any) return;
+    T.relo.assign(T.n(), tcv_relo_result());
+    for (int k = 0; k < T.n() && T.rc == TCV_OK; k++) {
+        std::memset(&T.relo[k], 0, sizeof T.relo[k]);
+        if (T.es[k]->w_relo) T.rc = tcv_batch_get_relocalization(T.b, k, &T.relo[k]);
+    }
+}
 // what became of each window: est_rc / est_msg.  A failed window fails alone -- the other estimators of the lock-step batch are applied,
 // this one reports the failure from tcv_estimator_finish_frame
 void judge_windows(tcv_opt_ticket &T) {
@@ -1271,6 +1393,16 @@ int apply_windows(tcv_opt_ticket &T) {
             continue;
         }
         apply_states(e);
+        if (e->w_relo && T.relo[k].valid) {      // the tail of double2vector (:1606-1620); the drift pair stays until the next relocalisation
+            const tcv_relo_result &r = T.relo[k];
+            tcv_estimator_relo &o = e->relo_out;
+            o.valid = 1; o.frame_index = e->w_relo_frame_index; o.frame_serial = e->w_relo_serial;
+            std::memcpy(o.drift_correct_r, r.drift_correct_r, sizeof o.drift_correct_r); std::memcpy(o.drift_correct_t, r.drift_correct_t, sizeof o.drift_correct_t);
+            std::memcpy(o.relo_relative_t, r.relo_relative_t, sizeof o.relo_relative_t); std::memcpy(o.relo_relative_q, r.relo_relative_q, sizeof o.relo_relative_q);
+            o.relo_relative_yaw = r.relo_relative_yaw;
+            std::memcpy(o.relo_r, r.relo_r, sizeof o.relo_r); std::memcpy(o.relo_t, r.relo_t, sizeof o.relo_t);
+        }
+        if (e->tap.on && e->tap.have && e->w_relo) { std::memcpy(e->tap.relo_out, e->relo_pose, sizeof e->tap.relo_out); e->tap.relo_result = T.relo[k]; }
         if (e->tap.on && e->tap.have) {
             WindowTap &tap = e->tap;
             tap.pose_out.assign(e->para_pose, e->para_pose + (W + 1) * 7); tap.sb_out.assign(e->para_sb, e->para_sb + (W + 1) * 9);
@@ -1298,6 +1430,7 @@ int optimize_end(tcv_opt_ticket &T) {
     T.lap.add(4);
     const double td0 = now_s();
     if (T.host_priors) download_to_host(T);
+    collect_relocalizations(T);
     const double td1 = now_s();
     judge_windows(T);
     if (T.host_priors) take_host_priors(T); else hand_over_batch(T);
@@ -1400,6 +1533,19 @@ extern "C" int tcv_estimator_get_window_snapshot_td(const tcv_estimator *e, tcv_
     o->estimate_td = e->estimate_td; o->n_proj = (int)T.pi.size();
     o->td_in = T.td_in; o->td_out = T.td_out; o->TR = e->td_TR; o->ROW = e->td_ROW;
     o->proj_td_aux = T.aux.empty() ? nullptr : T.aux.data();
+    return TCV_OK;
+}
+extern "C" int tcv_estimator_get_window_snapshot_relo(const tcv_estimator *e, tcv_window_snapshot_relo *o) {
+    if (!e || !o) return TCV_ERR_INVALID;
+    const WindowTap &T = e->tap;
+    if (!T.on || !T.have) { tcv::set_error("estimator_get_window_snapshot_relo: no snapshot (tap off, or no window optimised since it was switched on)"); return TCV_ERR_INVALID; }
+    std::memset(o, 0, sizeof *o);
+    if (!T.has_relo) return TCV_OK;
+    o->has_relo = 1; o->local_index = T.relo_local; o->n_relo = (int)T.r_pi.size(); o->frame_index = T.relo_frame_index; o->frame_serial = T.relo_frame_serial;
+    std::memcpy(o->relo_pose_in, T.relo_in, sizeof o->relo_pose_in); std::memcpy(o->relo_pose_out, T.relo_out, sizeof o->relo_pose_out);
+    o->relo_frame_i = T.r_pi.data(); o->relo_feature = T.r_pl.data(); o->relo_pts = T.r_pts.data();
+    std::memcpy(o->prev_relo_t, T.relo_prev, sizeof o->prev_relo_t); std::memcpy(o->prev_relo_r, T.relo_prev + 3, sizeof o->prev_relo_r);
+    o->result = T.relo_result;
     return TCV_OK;
 }
 extern "C" int tcv_estimator_get_stats(const tcv_estimator *e, tcv_estimator_stats *out) {

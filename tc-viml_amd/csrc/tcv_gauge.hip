@@ -104,6 +104,8 @@ extern "C" int tcv_batch_gauge_fix(tcv_batch *b, void *hip_stream) {
     for (auto &H : b->plans)
         if (H.n_frames <= 0 || H.n_frames > 64) { set_error("batch_gauge_fix: problem carries no frame table (tcv_problem_set_frames)"); return TCV_ERR_INVALID; }
     if (int rc = tcv_batch_enter_stream(b, hip_stream)) return rc;
+    // relocalisation windows: double2vector's tail (estimator.cpp:1606-1624) from the un-fixed states, before pose 0 is overwritten (tcv_relo.hip)
+    if (b->n_relo > 0 && !b->relo_done) if (int rc = tcv_relo_launch(b, (hipStream_t)hip_stream)) return rc;
     hipLaunchKernelGGL(gauge_batch_kernel, dim3(b->n), dim3(64), 0, (hipStream_t)hip_stream, b->d_win, b->d_plans, b->d_plan_base, b->d_ipool,
                        b->d_dpool, b->d_state, b->state_stride);
     hipError_t e = hipGetLastError();

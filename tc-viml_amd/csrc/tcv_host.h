@@ -161,6 +161,9 @@ struct tcv_problem {
     double td_TR = 0.0, td_ROW = 1.0;        // rolling-shutter globals of ProjectionTdFactor
     int line_exact = 0;                      // 1: line factors use the exact derivative of their residual (opt-in extension)
     std::vector<int> frame_pose, frame_sb;   // block ids of para_Pose[i] / para_SpeedBias[i] (gauge fix), may be empty
+    // tcv_problem_set_relocalization: block id of relo_Pose (-1: none), relo_frame_local_index, prev_relo_t 3 | prev_relo_r 9
+    int relo_block = -1, relo_local = -1;
+    double relo_prev[12] = {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1};
 };
 
 struct tcv_batch {
@@ -218,7 +221,19 @@ struct tcv_batch {
     void (*marg_free)(tcv_batch *) = nullptr;
     // evaluation (tcv_batch_evaluate)
     void *eval = nullptr;                 // tcv_capi.hip EvalState: owner lists, staging and output buffers, made at the first evaluation
+    // relocalisation (tcv_relo.hip): the windows whose problem carries tcv_problem_set_relocalization; n_relo = 0: nothing below is used
+    int n_relo = 0;
+    std::vector<int> relo_win;            // window of every table entry
+    double *d_relo = nullptr;             // one allocation: [records x n_relo | prev_relo_t / _r x n_relo | table], tcv_relo.h
+    std::vector<double> h_relo_up;        // the upload's host image (alive as long as the batch: the copy is asynchronous)
+    bool relo_done = false;               // the records belong to the last solve (tcv_batch_gauge_fix ran behind it)
+    bool relo_in_dl = false;              // the download in flight carries them
+    bool relo_have = false;               // h_relo / relo_valid hold them
+    std::vector<double> h_relo;           // host copy of the records, downloaded with the states
+    std::vector<char> relo_valid;         // per entry: the window's solve did not end in FAILURE
 };
+int tcv_relo_attach(tcv_batch *b, hipStream_t upload_stream);      // tcv_batch_create: table + prev_relo_* up, record buffer (no-op without relocalisation problems)
+int tcv_relo_launch(tcv_batch *b, hipStream_t st);                 // tcv_batch_gauge_fix: relo_fix_batch_kernel in front of the gauge kernel
 
 
 // every asynchronous entry point of a batch passes through here: a call on another stream than the previous one waits (on the device) for

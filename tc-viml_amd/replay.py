@@ -833,6 +833,12 @@ class _FrameInput(C.Structure):
                 ("truth", C.POINTER(C.c_double))]
 
 
+class _EstimatorRelo(C.Structure):      # tcv_estimator_relo (include/tcv_estimator_relo.h)
+    _fields_ = [("valid", C.c_int), ("frame_index", C.c_int), ("frame_serial", C.c_int), ("pad_", C.c_int),
+                ("drift_correct_r", C.c_double * 9), ("drift_correct_t", C.c_double * 3), ("relo_relative_t", C.c_double * 3),
+                ("relo_relative_q", C.c_double * 4), ("relo_relative_yaw", C.c_double), ("relo_r", C.c_double * 9), ("relo_t", C.c_double * 3)]
+
+
 class NativeLockstep:
     """Several sequences advanced in lock step through the native estimator (include/tcv_estimator.h): one estimator per stream,
     every frame the full windows of all streams form ONE device batch (tcv_estimators_optimize).  Python only feeds the per-frame
@@ -841,12 +847,15 @@ class NativeLockstep:
 
     def __init__(self, streams, num_iterations: int = 8, fixed_iterations: bool = False, init_sigma=(0.02, 0.005, 0.05), bias_sigma=(0.005, 0.0005),
                  exact_line_jacobian: bool = False, estimate_extrinsic: bool = True, solver_time: float = 0.0,
-                 estimate_td=None, td0: float = 0.0, TR: float = 0.0, ROW: float = None):
+                 estimate_td=None, td0: float = 0.0, TR: float = 0.0, ROW: float = None, relo=None):
         """solver_time: SOLVER_TIME of the reference's configuration (sensor.yaml:85; 0: no clock).
         estimate_td, td0, TR, ROW: tcv_estimator_set_time_offset (ESTIMATE_TD, TD, TR, ROW of parameters.cpp:135-138; ROW defaults to the image
         height) -- None (default): the call is not made at all; a bool, or one entry (bool or None) per stream for a list that mixes both kinds.  A stream
         that carries `point_aux` (`simulate_stream_td`) has it staged before every begin_frame (tcv_estimator_stage_point_aux), whatever
-        estimate_td says.  `time_offset(si)` reads the estimator's td."""
+        estimate_td says.  `time_offset(si)` reads the estimator's td.
+        relo: {frame k: [(stream, frame serial, match_points (n, 3: x, y, feature id), prev_relo_t, prev_relo_r, frame_index)]} -- every request
+        is handed to tcv_estimator_set_relo_frame before frame k's begin_frame (Estimator::setReloFrame between two frames, estimator_node.cpp:376);
+        `relo_accepted` lists (k, stream, accepted) of the requests made, `relocalization(si)` reads the estimator's drift correction."""
         import tcv
         self.tcv = tcv
         L = self.L = tcv.lib()
@@ -883,6 +892,14 @@ class NativeLockstep:
         if estimate_td is not None or self._any_aux:      # (bound only when used: a library from before ESTIMATE_TD still loads through TCV_LIB)
             L.tcv_estimator_set_time_offset.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double]
             L.tcv_estimator_stage_point_aux.argtypes = [vp, C.c_int, dp]
+        self.relo = dict(relo or {})
+        self.relo_accepted = []
+        if self.relo:      # (bound only when used, like the ESTIMATE_TD entry points)
+            L.tcv_estimator_set_relo_frame.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp, ip]
+        L_relo = getattr(L, "tcv_estimator_get_relocalization", None)
+        if L_relo is not None:
+            L_relo.argtypes = [vp, C.POINTER(_EstimatorRelo)]
+            L.tcv_estimator_frame_serial.argtypes = [vp, ip, ip, ip]
         L_td = getattr(L, "tcv_estimator_get_time_offset", None)
         if L_td is not None:
             L_td.argtypes = [vp, dp]
@@ -1022,6 +1039,11 @@ class NativeLockstep:
             return
         if self._any_aux:
             self._stage_aux(live, keep)
+        for si, serial, match, prev_t, prev_r, frame_index in self.relo.get(k, ()):
+            m = self._f64(np.asarray(match, dtype=float).reshape(-1, 3)); pt = self._f64(prev_t).reshape(3); pr = self._f64(prev_r).reshape(9)
+            acc = C.c_int(0)
+            tcv.check(L.tcv_estimator_set_relo_frame(self.ests[si], int(serial), int(frame_index), m.shape[0], self._P(m), self._P(pt), self._P(pr), C.byref(acc)))
+            self.relo_accepted.append((k, si, acc.value))
         tcv.check(L.tcv_estimators_begin_frames(arr_all, len(live), rec, rdy, None))
         ready = [si for j, si in enumerate(live) if rdy[j]]
         t_b = time.perf_counter()
@@ -1047,6 +1069,23 @@ class NativeLockstep:
         td = C.c_double()
         self.tcv.check(self.L.tcv_estimator_get_time_offset(self.ests[si], C.byref(td)))
         return td.value
+
+    def relocalization(self, si: int = 0) -> dict:
+        """what the last applied relocalisation window of stream si left (tcv_estimator_get_relocalization): valid, frame_index, frame_serial,
+        drift_correct_r / _t (the caller corrects a published position with drift_correct_r @ P + drift_correct_t, visualization.cpp:194-195),
+        relo_relative_t / _q (x y z w) / _yaw (degrees), relo_r / relo_t"""
+        r = _EstimatorRelo()
+        self.tcv.check(self.L.tcv_estimator_get_relocalization(self.ests[si], C.byref(r)))
+        return dict(valid=int(r.valid), frame_index=int(r.frame_index), frame_serial=int(r.frame_serial), drift_correct_r=np.array(r.drift_correct_r).reshape(3, 3),
+                    drift_correct_t=np.array(r.drift_correct_t), relo_relative_t=np.array(r.relo_relative_t), relo_relative_q=np.array(r.relo_relative_q),
+                    relo_relative_yaw=float(r.relo_relative_yaw), relo_r=np.array(r.relo_r).reshape(3, 3), relo_t=np.array(r.relo_t))
+
+    def frame_serials(self, si: int = 0):
+        """(next serial, serial of the frame in every window slot (-1: none), slots that hold a frame) of stream si (tcv_estimator_frame_serial)"""
+        nxt, n = C.c_int(), C.c_int()
+        ws = (C.c_int * (WINDOW_SIZE + 1))()
+        self.tcv.check(self.L.tcv_estimator_frame_serial(self.ests[si], C.byref(nxt), ws, C.byref(n)))
+        return nxt.value, list(ws), n.value
 
     def step_end(self) -> int:
         """second half: waits for the states, applies them (tcv_estimators_optimize_end), finish_frame of every stream; returns the number of windows"""

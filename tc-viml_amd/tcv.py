@@ -45,6 +45,7 @@ EXPORTS = [
     "tcv_microbench_fp64", "tcv_problem_plan_ints", "tcv_problem_marg_plan", "tcv_marg_lds_layout", "tcv_set_packer_reference", "tcv_plan_cache_stats", "tcv_problems_pack_bench", "tcv_line_map_create", "tcv_line_map_destroy", "tcv_batch_download_states_brief", "tcv_thread_stream_slot", "tcv_batch_download_states_begin", "tcv_batch_download_states_end",
     "tcv_evaluate_options_default", "tcv_batch_evaluate", "tcv_batch_evaluation_dims", "tcv_batch_get_evaluation", "tcv_batch_get_evaluation_costs",
     "tcv_problem_evaluate", "tcv_problem_num_effective_parameters",
+    "tcv_problem_set_relocalization", "tcv_batch_get_relocalization", "tcv_relocalization_fix",
 ]
 
 
@@ -69,6 +70,19 @@ class EvaluateOptions(C.Structure):
 
 
 EVALUATE_AT_INITIAL, EVALUATE_AT_SOLUTION = 0, 1
+
+
+class ReloResult(C.Structure):
+    """tcv_relo_result: double2vector's relocalisation tail (estimator.cpp:1606-1620); matrices row-major, quaternion x y z w, degrees"""
+    _fields_ = [("valid", C.c_int), ("pad_", C.c_int), ("relo_r", C.c_double * 9), ("relo_t", C.c_double * 3), ("drift_correct_r", C.c_double * 9),
+                ("drift_correct_t", C.c_double * 3), ("relo_relative_t", C.c_double * 3), ("relo_relative_q", C.c_double * 4),
+                ("relo_relative_yaw", C.c_double), ("drift_correct_yaw", C.c_double)]
+
+    def as_dict(self):
+        return dict(valid=int(self.valid), relo_r=np.array(self.relo_r).reshape(3, 3), relo_t=np.array(self.relo_t),
+                    drift_correct_r=np.array(self.drift_correct_r).reshape(3, 3), drift_correct_t=np.array(self.drift_correct_t),
+                    relo_relative_t=np.array(self.relo_relative_t), relo_relative_q=np.array(self.relo_relative_q),
+                    relo_relative_yaw=float(self.relo_relative_yaw), drift_correct_yaw=float(self.drift_correct_yaw))
 
 
 class SolverSummary(C.Structure):
@@ -196,6 +210,10 @@ def lib():
         L.tcv_batch_get_evaluation_costs.argtypes = [vp, _dp, _dp, _dp, C.c_int]
         L.tcv_problem_evaluate.argtypes = [vp, C.POINTER(EvaluateOptions), _dp, _dp, _dp, _dp]
         L.tcv_problem_num_effective_parameters.argtypes = [vp]
+        if hasattr(L, "tcv_problem_set_relocalization"):      # (a library from before the relocalisation tail still loads through TCV_LIB: A/B runs of bench.py)
+            L.tcv_problem_set_relocalization.argtypes = [vp, _dp, C.c_int, _dp, _dp]
+            L.tcv_batch_get_relocalization.argtypes = [vp, C.c_int, C.POINTER(ReloResult)]
+            L.tcv_relocalization_fix.argtypes = [C.c_int] + [_dp] * 7 + [C.POINTER(ReloResult)]
         _lib = L
     return _lib
 
@@ -373,6 +391,12 @@ class Window:
         """tcv_problem_set_marginalization_prior: hand the problem a new prior with the layout of its current one (the same blocks)"""
         check(lib().tcv_problem_set_marginalization_prior(self.h, prior.h))
         self.prior = prior
+
+    def set_relocalization(self, relo_pose, frame_local_index, prev_relo_t, prev_relo_r):
+        """tcv_problem_set_relocalization: `relo_pose` is the array of the relocalisation block this problem already holds
+        (tcv_problem_add_parameter_block + its ProjectionFactors, estimator.cpp:1854-1886)"""
+        t, r = f64(prev_relo_t).reshape(3), f64(prev_relo_r).reshape(9)
+        check(lib().tcv_problem_set_relocalization(self.h, dptr(relo_pose), int(frame_local_index), dptr(t), dptr(r)))
 
     def states(self):
         out = dict(pose=self.pose.copy(), sb=self.sb.copy(), ex=self.ex.copy(), lam=self.lam.copy())
@@ -631,6 +655,13 @@ class Batch:
         """tcv_batch_set_fused_gauge_fix: the same fix in the solve kernel's epilogue; `gauge_fix()` behind such a solve is a no-op."""
         check(lib().tcv_batch_set_fused_gauge_fix(self.h, int(on)))
 
+    def relocalization(self, window):
+        """tcv_batch_get_relocalization: the window's relocalisation record (dict, `valid` = 0 without one) from the host copy that came
+        with the states"""
+        r = ReloResult()
+        check(lib().tcv_batch_get_relocalization(self.h, int(window), C.byref(r)))
+        return r.as_dict()
+
     def synchronize(self):
         check(lib().tcv_batch_synchronize(self.h))
 
@@ -826,6 +857,20 @@ def gauge_fix(R0, P0, pose, sb):
     Rs = np.zeros((n, 3, 3)); Ps = np.zeros((n, 3)); Vs = np.zeros((n, 3)); po = np.zeros((n, 7))
     check(lib().tcv_gauge_fix(n, dptr(R0), dptr(P0), dptr(pose), dptr(sb), dptr(Rs), dptr(Ps), dptr(Vs), dptr(po)))
     return Rs, Ps, Vs, po
+
+
+def relo_fix(R0, P0, pose0, pose_l, relo_pose, prev_relo_t, prev_relo_r):
+    """double2vector's relocalisation tail (estimator.cpp:1606-1620) on the GPU for n independent cases (tcv_relocalization_fix): R0 (n, 3, 3)
+    and P0 (n, 3) = Rs[0] / Ps[0] before the solve; pose0, pose_l, relo_pose (n, 7) = the solved, un-fixed para_Pose[0], para_Pose[l],
+    relo_Pose; prev_relo_t (n, 3), prev_relo_r (n, 3, 3).  Returns a dict of arrays over the cases (keys of ReloResult)."""
+    a = [f64(x).reshape(-1, k) for x, k in ((R0, 9), (P0, 3), (pose0, 7), (pose_l, 7), (relo_pose, 7), (prev_relo_t, 3), (prev_relo_r, 9))]
+    n = a[0].shape[0]
+    assert all(x.shape[0] == n for x in a)
+    out = (ReloResult * max(1, n))()
+    check(lib().tcv_relocalization_fix(n, *[dptr(x) for x in a], out))
+    rec = np.frombuffer(out, dtype=np.float64).reshape(max(1, n), -1)[:n, 1:].copy()      # (the two ints are one double wide)
+    return dict(valid=np.array([out[i].valid for i in range(n)]), relo_r=rec[:, 0:9].reshape(n, 3, 3), relo_t=rec[:, 9:12], drift_correct_r=rec[:, 12:21].reshape(n, 3, 3),
+                drift_correct_t=rec[:, 21:24], relo_relative_t=rec[:, 24:27], relo_relative_q=rec[:, 27:31], relo_relative_yaw=rec[:, 31], drift_correct_yaw=rec[:, 32])
 
 
 def match_lines(poses, ex_pose, Rbw, Tbw, K, width, height, window_size, lines3d, det_frame, det_lines, angle_th, overlap_th, in_fov=None, fov_frame=None):
