@@ -23,11 +23,8 @@
 
 #include "../../include/tcv_estimator.h"
 #include "tcv_hostpool.h"      // parallel_items, async_run, HostOp: the persistent host worker threads
+#include "tcv_runtime.h"       // util_stream, aux_stream, set_error
 
-namespace tcv {
-hipStream_t util_stream(); hipStream_t aux_stream();      // (tcv_capi.hip: the calling thread's utility stream and its second stream)
-void set_error(const std::string &s);
-}
 int tcv_marg_layout_n(const tcv_batch *b, int window);      // (tcv_marg_host.cpp: n of the prior a window's attached marginalisation problem makes, known before the kernel runs)
 
 namespace {

@@ -6,7 +6,7 @@
 // One 256-thread workgroup per window, states in LDS, a few KB of LDS otherwise (several workgroups per CU).  Every sum has a fixed
 // order that depends on the window alone -- never on the batch, the grid or the timing: family costs are per-thread partial sums (factor
 // f on thread f mod 256, ascending) folded by a fixed tree; a gradient entry is added by its OWNER thread from the J'r pieces the factors
-// left in the window's staging area, in factor order (owner lists: tcv_eval.h; built by the host once per plan, tcv_capi.hip); the
+// left in the window's staging area, in factor order (owner lists: tcv_eval.h; built by the host once per plan, tcv_eval_host.cpp); the
 // max-norm is a maximum.  No atomics.
 #include <hip/hip_runtime.h>
 

@@ -7,7 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <vector>
 
 #include "tcv_host.h"
 #include "tcv_math.h"
@@ -69,32 +68,22 @@ extern "C" int tcv_gauge_fix(int n, const double *R0, const double *P0, const do
     if (int rc = device_ready()) return rc;
     for (int i = 0; i < 7 * n; i++) if (!(pose[i] == pose[i])) { set_error("gauge_fix: NaN in poses"); return TCV_ERR_NUMERIC; }
     const size_t nin = 12 + (size_t)16 * n, nout = (size_t)22 * n;
-    std::vector<double> h(nin);
-    std::memcpy(h.data(), R0, 72); std::memcpy(h.data() + 9, P0, 24);
-    std::memcpy(h.data() + 12, pose, sizeof(double) * 7 * n); std::memcpy(h.data() + 12 + 7 * n, sb, sizeof(double) * 9 * n);
-    double *d = nullptr;
-    hipError_t e = tcv::dev_malloc((void **)&d, sizeof(double) * (nin + nout));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    int rc = TCV_OK;
-    e = hipMemcpy(d, h.data(), sizeof(double) * nin, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        double *o = d + nin;
-        hipStream_t st = tcv::util_stream();
-        hipLaunchKernelGGL(gauge_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, d, d + 9, d + 12, d + 12 + 7 * n, o, o + 9 * n, o + 12 * n,
-                           o + 15 * n);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = tcv::stream_wait(st);
-        std::vector<double> ho(nout);
-        if (e == hipSuccess) e = hipMemcpy(ho.data(), o, sizeof(double) * nout, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) {
-            std::memcpy(Rs, ho.data(), sizeof(double) * 9 * n); std::memcpy(Ps, ho.data() + 9 * n, sizeof(double) * 3 * n);
-            std::memcpy(Vs, ho.data() + 12 * n, sizeof(double) * 3 * n);
-            if (pose_out) std::memcpy(pose_out, ho.data() + 15 * n, sizeof(double) * 7 * n);
-        }
-    }
-    if (e != hipSuccess) rc = hip_fail(e, "gauge_fix");
-    tcv::dev_free(d);
-    return rc;
+    tcv::RoundTrip rt(tcv::util_stream(), sizeof(double) * nin, sizeof(double) * nout);      // [R0 | P0 | poses | speed-biases] -> [Rs | Ps | Vs | poses]
+    if (int rc = rt.ready("gauge_fix")) return rc;
+    double *h = rt.h_in();
+    std::memcpy(h, R0, 72); std::memcpy(h + 9, P0, 24);
+    std::memcpy(h + 12, pose, sizeof(double) * 7 * n); std::memcpy(h + 12 + 7 * n, sb, sizeof(double) * 9 * n);
+    const double *d = rt.d_in();
+    double *o = rt.d_out();
+    if (int rc = rt.run("gauge_fix", [&](hipStream_t st) {
+            hipLaunchKernelGGL(gauge_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, d, d + 9, d + 12, d + 12 + 7 * n, o, o + 9 * n, o + 12 * n,
+                               o + 15 * n);
+        })) return rc;
+    const double *ho = rt.h_out();
+    std::memcpy(Rs, ho, sizeof(double) * 9 * n); std::memcpy(Ps, ho + 9 * n, sizeof(double) * 3 * n);
+    std::memcpy(Vs, ho + 12 * n, sizeof(double) * 3 * n);
+    if (pose_out) std::memcpy(pose_out, ho + 15 * n, sizeof(double) * 7 * n);
+    return TCV_OK;
 }
 
 extern "C" int tcv_batch_gauge_fix(tcv_batch *b, void *hip_stream) {

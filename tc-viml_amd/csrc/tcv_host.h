@@ -16,6 +16,7 @@
 #include "../../include/tcv.h"
 #include "tcv_packed.h"
 #include "tcv_hostpool.h"
+#include "tcv_runtime.h"      // streams, pools, error text, StagedTransfer / RoundTrip
 
 namespace tcv {
 // a device allocation shared between its producer (a batch) and the handles that still read it (device-resident priors)
@@ -212,7 +213,7 @@ struct tcv_batch {
     int coop_h = 0, coop_groups = 0, slots = 0;
     int last_wg = 0;                              // workgroups per window of the last solve (1: single-workgroup kernel)
     int n_cu = 0, coop_claim = 0, coop_dev = 0;   // CUs of the device; CUs this batch's cooperative launch in flight has claimed (tcv_batch_solve)
-    int coop_claim_xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0}, coop_rot = 0;   // the claim per XCD; XCD of the launch's first group (tcv_capi.hip coop_admit)
+    int coop_claim_xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0}, coop_rot = 0;   // the claim per XCD; XCD of the launch's first group (tcv_batch.cpp coop_admit)
     int coop_exp_chunks = 0, coop_exp_stride = 0;
     int *d_coop_ctl = nullptr;
     double *d_coop_x = nullptr, *d_coop_exp = nullptr;
@@ -220,7 +221,7 @@ struct tcv_batch {
     void *marg = nullptr;                 // tcv_marg_host.cpp MargState
     void (*marg_free)(tcv_batch *) = nullptr;
     // evaluation (tcv_batch_evaluate)
-    void *eval = nullptr;                 // tcv_capi.hip EvalState: owner lists, staging and output buffers, made at the first evaluation
+    void *eval = nullptr;                 // tcv_eval_host.cpp EvalState: owner lists, staging and output buffers, made at the first evaluation
     // relocalisation (tcv_relo.hip): the windows whose problem carries tcv_problem_set_relocalization; n_relo = 0: nothing below is used
     int n_relo = 0;
     std::vector<int> relo_win;            // window of every table entry
@@ -248,6 +249,7 @@ void tcv_marg_elapsed(tcv_batch *b);
 int tcv_marg_download(tcv_batch *b, int compact);
 int tcv_marg_get_priors_device(tcv_batch *b, tcv_prior **out, int n, bool nowait);
 int tcv_marg_status_prefetch(tcv_batch *b, void *stream);
+void tcv_eval_free(tcv_batch *b);      // tcv_eval_host.cpp: the evaluation buffers of a batch (no-op before the first tcv_batch_evaluate)
 bool tcv_marg_has_problem(const tcv_batch *b, int window);      // false: marg_problems[window] was NULL
 int tcv_marg_layout_n(const tcv_batch *b, int window);          // n of the prior this window's marginalisation makes (known from the attached problem, before the kernel runs); -1: none
 // host only (tcv_problem_marg_plan): one window through the marginalisation packer -- ints = [MargHdr as ints | int pool], doubles = the
@@ -269,13 +271,7 @@ int launch_prior_splice(const PriorSplice *d_jobs, int njobs, double *d_dpool, v
 }  // namespace tcv
 
 namespace tcv {
-// device allocations go through a per-process free list (size-bucketed, per device): a per-frame estimator creates and destroys a
-// batch every frame, and hipMalloc / hipFree (each a device synchronisation) were a quarter of its host time
-hipError_t dev_malloc(void **p, size_t bytes);
-hipError_t dev_free(void *p);
-int hip_fail(hipError_t e, const char *what);
-int device_ready();
-void set_error(const std::string &s);
+int solver_variant();      // tcv_set_solver_variant (tcv_batch.cpp): 0 chain layout when the graph allows it, 1 always the dense 171-dim layout
 // returns TCV_OK or a negative status; fills out.  imu_sqrt: optional host-provided sqrt_info (n_imu x 225).
 // mode: 0 = chain layout when the graph allows it (speed-bias blocks form chains), else dense; 1 = dense layout
 // chain_lds: LDS doubles of a chain-layout workgroup (0: chain_lds_doubles(), half a CU's LDS so that two workgroups share a CU)
@@ -302,36 +298,18 @@ void put_imu_const(Sink &D, const tcv_imu_preintegration &q);      // IMU_CONST 
 void put_prior_region(Sink &D, const tcv_prior &pr, int k0);       // J0 rows k0 .. n - 1 (column-major) | r0[k0 ..] | x0; the prior is on the host (tcv_prior_host)
 // one projection record [pts 6 | aux 8 (ProjectionTdFactor only)]; `first` is the window's first record, whose sqrt_info and loss all share
 int put_proj_record(Sink &D, const ProjFac &f, const ProjFac &first);
-// pinned host staging buffers for uploads / downloads, recycled through a small per-process pool (hipHostMalloc costs milliseconds)
-void *host_staging_acquire(size_t bytes);
-void host_staging_release(void *p);
-// buffers of commands left in flight on the calling thread's stream `st`: released at the thread's next wait on it (tcv_capi.hip)
-void defer_release(void *host_staging, void *dev_buf, hipStream_t st);
-void flush_deferred(hipStream_t st);
-hipError_t stream_wait(hipStream_t st);      // waits for the stream; for the device when `st` is the null stream
-// The buffers of ONE call's transfer: a pinned staging buffer and, optionally, one pooled device buffer, bound to the stream the call's
-// commands go to.  Both go back to process-wide pools that other host threads take from, so releasing them while a copy or a kernel on
-// `st` still uses them is a use-after-free across threads: once the call has said issued(), every exit waits for the stream first.
-struct StagedTransfer {
-    void *host, *dev = nullptr;
-    const hipStream_t st;
-    StagedTransfer(hipStream_t stream, size_t host_bytes) : host(host_staging_acquire(host_bytes)), st(stream) {}
-    StagedTransfer(const StagedTransfer &) = delete;
-    ~StagedTransfer();                                      // in flight: waits for the stream; then both buffers go back to their pools
-    hipError_t dev_alloc(size_t bytes) { return dev_malloc(&dev, bytes); }
-    void issued() { in_flight = true; }                     // a command that uses a buffer is on the stream, or about to be
-    hipError_t wait();                                      // no longer in flight once a wait has succeeded
-    void park();                                            // left in flight: the buffers are released at the thread's next wait on the stream (defer_release)
-    void *take_dev() { void *p = dev; dev = nullptr; return p; }      // the caller keeps the device buffer (and frees it behind this guard's wait)
-private:
-    bool in_flight = false;
+// first failing window of a parallel packing pass, with the message of the thread that packed it (the message is thread-local)
+struct PackErrors {
+    std::vector<int> rcs, who;
+    std::vector<std::string> msgs;
+    PackErrors(int n, int nth) : rcs(n, TCV_OK), who(n, 0), msgs(nth) {}
+    void note(int w, int t, int rc) { rcs[w] = rc; who[w] = t; if (rc != TCV_OK && msgs[t].empty()) msgs[t] = tcv_last_error(); }
+    int first() const {      // TCV_OK, or that window's status with its message as the calling thread's error
+        for (size_t w = 0; w < rcs.size(); w++)
+            if (rcs[w] != TCV_OK) { if (!msgs[who[w]].empty()) set_error(msgs[who[w]]); return rcs[w]; }
+        return TCV_OK;
+    }
 };
-// blocking download through pinned staging on the calling thread's own stream (the default stream serialises the host threads of a process)
-int staged_download(void *dst, const void *d_src, size_t bytes, const char *what);
-// a non-blocking stream of the calling thread on its current device, created on first use and kept: the one-shot entry points
-// (pre-integration, line association, gauge fix) launch there and wait for THAT stream, never for the device -- another host thread's
-// batches keep running (several estimator groups per GPU, bench.py --mode replay)
-hipStream_t util_stream();
 // plan-cache statistics (hits, misses, entries); tcv_pack.cpp
 void plan_cache_stats(long long *hits, long long *misses, long long *entries);
 void set_pack_reference(int on);

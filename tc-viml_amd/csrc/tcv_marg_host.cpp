@@ -447,9 +447,9 @@ int tcv_prior_host(const tcv_prior *pr) {
     const bool sw = hipGetDevice(&cur) == hipSuccess && pr->dev && cur != pr->dev->dev;
     if (sw) (void)hipSetDevice(pr->dev->dev);
     if (pr->dev) if (const int rcw = pr->dev->sync_ready()) { if (sw) (void)hipSetDevice(cur); return rcw; }
-    const hipError_t e = hipMemcpy(o.data(), pr->d_block, sizeof(double) * MARG_OUT_COMPACT, hipMemcpyDeviceToHost);
+    const int rcd = tcv::staged_download(o.data(), pr->d_block, sizeof(double) * MARG_OUT_COMPACT, "download of a device-resident prior");
     if (sw) (void)hipSetDevice(cur);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H (device-resident prior)");
+    if (rcd != TCV_OK) return rcd;
     pr->J0.assign(o.begin() + MARG_OUT_J0, o.begin() + MARG_OUT_J0 + (size_t)n * n);
     pr->r0.assign(o.begin() + MARG_OUT_R0, o.begin() + MARG_OUT_R0 + n);
     pr->x0.clear();
@@ -674,16 +674,19 @@ int tcv_marg_download(tcv_batch *b, int compact) {
     if (!s || !s->ran) { set_error("no marginalisation result"); return TCV_ERR_INVALID; }
     const size_t stride = compact ? (size_t)MARG_OUT_COMPACT : (size_t)MARG_OUT_STRIDE;
     if (s->h_out && s->h_stride != stride) { tcv::host_staging_release(s->h_out); s->h_out = nullptr; }
-    if (!s->h_out) s->h_out = (double *)tcv::host_staging_acquire(sizeof(double) * stride * b->n);
+    const size_t out_bytes = sizeof(double) * stride * b->n;      // the status of every window rides behind the blocks in the same pinned buffer
+    if (!s->h_out) s->h_out = (double *)tcv::host_staging_acquire(out_bytes + sizeof(int) * b->n);
     if (!s->h_out) { set_error("hipHostMalloc (download staging) failed"); return TCV_ERR_HIP; }
     s->h_stride = stride;
     s->h_status.resize(b->n);
-    hipStream_t ust = tcv::util_stream();      // (h_out is pinned: asynchronous copies on the calling thread's own stream)
+    hipStream_t ust = tcv::util_stream();      // (h_out is pinned: asynchronous copies on the calling thread's own stream, one wait)
     hipError_t e = compact ? hipMemcpy2DAsync(s->h_out, sizeof(double) * stride, s->d_out, sizeof(double) * MARG_OUT_STRIDE, sizeof(double) * stride, b->n, hipMemcpyDeviceToHost, ust)
-                           : hipMemcpyAsync(s->h_out, s->d_out, sizeof(double) * stride * b->n, hipMemcpyDeviceToHost, ust);
-    if (e == hipSuccess) e = tcv::stream_wait(ust);
-    if (e == hipSuccess) e = hipMemcpy(s->h_status.data(), s->d_status, sizeof(int) * b->n, hipMemcpyDeviceToHost);
+                           : hipMemcpyAsync(s->h_out, s->d_out, out_bytes, hipMemcpyDeviceToHost, ust);
+    if (e == hipSuccess) e = hipMemcpyAsync((char *)s->h_out + out_bytes, s->d_status, sizeof(int) * b->n, hipMemcpyDeviceToHost, ust);
+    const hipError_t ew = tcv::stream_wait(ust);      // (whatever was issued is drained before anybody touches h_out again)
+    if (e == hipSuccess) e = ew;
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
+    std::memcpy(s->h_status.data(), (char *)s->h_out + out_bytes, sizeof(int) * b->n);
     s->h_valid = true;
     return TCV_OK;
 }
@@ -699,13 +702,10 @@ void tcv_marg_elapsed(tcv_batch *b) {
 extern "C" int tcv_batch_marg_status(tcv_batch *b, int *out, int n) {
     MargState *s = b ? (MargState *)b->marg : nullptr;
     if (!s || !s->ran || !out || n > b->n) { set_error("no marginalisation result"); return TCV_ERR_INVALID; }
-    if (b->pending) if (int rc = tcv_batch_synchronize(b)) return rc;      // (a copy on the null stream is not ordered behind a non-blocking stream)
+    if (b->pending) if (int rc = tcv_batch_synchronize(b)) return rc;      // (a copy on the calling thread's stream is not ordered behind the batch's streams)
     std::vector<int> st(2 * (size_t)b->n);
     if (s->status_prefetched) std::memcpy(st.data(), s->h_status_pre, sizeof(int) * st.size());      // (came down behind the kernel; the wait above covers it)
-    else {
-        const hipError_t e = hipMemcpy(st.data(), s->d_status, sizeof(int) * st.size(), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
-    }
+    else if (int rc = tcv::staged_download(st.data(), s->d_status, sizeof(int) * st.size(), "download of the marginalisation status")) return rc;
     for (int w = 0; w < n; w++)      // -2: a NaN in the result; a marginalisation that keeps nothing has nothing to run: 0
         out[w] = s->win[w].empty_keep ? 0 : ((st[w] == 0 && st[b->n + w] < 0 && s->win[w].hdr.nblk != 0) ? -2 : st[w]);
     return TCV_OK;
@@ -764,9 +764,16 @@ int tcv_marg_get_prior(tcv_batch *b, int window, tcv_prior **out) {
         have_schur = s->h_stride == (size_t)MARG_OUT_STRIDE;
         status = s->h_status[window];
     } else {
-        hipError_t e = hipMemcpy(o.data(), s->d_out + (size_t)window * MARG_OUT_STRIDE, sizeof(double) * MARG_OUT_STRIDE, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(&status, s->d_status + window, sizeof(int), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
+        // one round trip: the window's result block and, behind it in the staging buffer, its status (they are not neighbours on the device)
+        const size_t ob = sizeof(double) * MARG_OUT_STRIDE;
+        tcv::StagedTransfer dl(tcv::util_stream(), ob + sizeof(int));
+        if (!dl.host) { set_error("hipHostMalloc (download staging) failed"); return TCV_ERR_HIP; }
+        dl.issued();
+        hipError_t e = hipMemcpyAsync(dl.host, s->d_out + (size_t)window * MARG_OUT_STRIDE, ob, hipMemcpyDeviceToHost, dl.st);
+        if (e == hipSuccess) e = hipMemcpyAsync((char *)dl.host + ob, s->d_status + window, sizeof(int), hipMemcpyDeviceToHost, dl.st);
+        if (e == hipSuccess) e = dl.wait();
+        if (e != hipSuccess) return hip_fail(e, "download of a marginalisation result");
+        std::memcpy(o.data(), dl.host, ob); std::memcpy(&status, (char *)dl.host + ob, sizeof(int));
     }
     if (int rc = marg_status_error(status)) return rc;
     tcv_prior *pr = prior_layout(mw);

@@ -734,26 +734,15 @@ extern "C" int tcv_pose_graph_eval_edges(int n, const int *kind, const double *y
     }
     for (double v : in) if (!std::isfinite(v)) { set_error("pose_graph_eval_edges: non-finite input"); return TCV_ERR_INVALID; }
     if (int rc = device_ready()) return rc;
-    const size_t b_in = 8 * in.size(), b_kind = ((4 * (size_t)n + 7) / 8) * 8, b_out = 8 * (size_t)PG_EDGE_OUT * n;
-    hipStream_t st = tcv::util_stream();
-    tcv::StagedTransfer tr(st, b_in + b_kind + b_out);
-    if (!tr.host) { set_error("hipHostMalloc (pose graph staging) failed"); return TCV_ERR_HIP; }
-    char *h = (char *)tr.host;
-    std::memcpy(h, in.data(), b_in);
-    std::memcpy(h + b_in, kind, 4 * (size_t)n);
-    hipError_t e = tr.dev_alloc(b_in + b_kind + b_out);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc (pose graph edges)");
-    char *dv = (char *)tr.dev;
-    tr.issued();
-    e = hipMemcpyAsync(dv, h, b_in + b_kind, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(pose_graph_edges_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, (const int *)(dv + b_in), (const double *)dv, (double *)(dv + b_in + b_kind), pg_opts(options));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h + b_in + b_kind, dv + b_in + b_kind, b_out, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = tr.wait();
-    if (e != hipSuccess) return hip_fail(e, "pose_graph_eval_edges");
-    const double *o = (const double *)(h + b_in + b_kind);
+    const size_t b_in = 8 * in.size(), b_out = 8 * (size_t)PG_EDGE_OUT * n;
+    tcv::RoundTrip rt(tcv::util_stream(), b_in + 4 * (size_t)n, b_out);      // [edges | kind (ints)] -> n records of PG_EDGE_OUT doubles
+    if (int rc = rt.ready("pose_graph_eval_edges")) return rc;
+    std::memcpy(rt.h_in<char>(), in.data(), b_in);
+    std::memcpy(rt.h_in<char>() + b_in, kind, 4 * (size_t)n);
+    if (int rc = rt.run("pose_graph_eval_edges", [&](hipStream_t st) {
+            hipLaunchKernelGGL(pose_graph_edges_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, (const int *)(rt.d_in<char>() + b_in), (const double *)rt.d_in(), rt.d_out(), pg_opts(options));
+        })) return rc;
+    const double *o = rt.h_out();
     for (int i = 0; i < n; i++) {
         std::memcpy(residual + 4 * i, o + (size_t)PG_EDGE_OUT * i, 32);
         std::memcpy(jacobian + 32 * i, o + (size_t)PG_EDGE_OUT * i + 4, 256);

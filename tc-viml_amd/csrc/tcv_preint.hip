@@ -321,9 +321,9 @@ int tcv_preint_host(const tcv_preint *pre) {
     const bool sw = hipGetDevice(&cur) == hipSuccess && pre->dev && cur != pre->dev->dev;
     if (sw) (void)hipSetDevice(pre->dev->dev);
     if (pre->dev) if (const int rcw = pre->dev->sync_ready()) { if (sw) (void)hipSetDevice(cur); return rcw; }
-    const hipError_t e = hipMemcpy(o, pre->d_out, sizeof o, hipMemcpyDeviceToHost);
+    const int rcd = tcv::staged_download(o, pre->d_out, sizeof o, "download of a device-resident pre-integration");
     if (sw) (void)hipSetDevice(cur);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H (device-resident pre-integration)");
+    if (rcd != TCV_OK) return rcd;
     unpack_record(o, pre->pod);
     pre->host = true;
     return TCV_OK;

@@ -67,30 +67,20 @@ extern "C" int tcv_relocalization_fix(int n, const double *R0, const double *P0,
     if (n <= 0 || n > 4096 || !R0 || !P0 || !pose0 || !pose_l || !relo_pose || !prev_relo_t || !prev_relo_r || !out) { set_error("relocalization_fix: bad argument"); return TCV_ERR_INVALID; }
     if (int rc = device_ready()) return rc;
     const size_t nin = (size_t)RELO_CASE_IN * n, nout = (size_t)RELO_REC * n;
-    std::vector<double> h(nin);
+    tcv::RoundTrip rt(tcv::util_stream(), sizeof(double) * nin, sizeof(double) * nout);      // n cases of RELO_CASE_IN doubles -> n records
+    if (int rc = rt.ready("relocalization_fix")) return rc;
+    double *h = rt.h_in();
     for (int i = 0; i < n; i++) {
-        double *c = h.data() + (size_t)RELO_CASE_IN * i;
+        double *c = h + (size_t)RELO_CASE_IN * i;
         std::memcpy(c, R0 + 9 * i, 72); std::memcpy(c + 9, P0 + 3 * i, 24); std::memcpy(c + 12, pose0 + 7 * i, 56); std::memcpy(c + 19, pose_l + 7 * i, 56);
         std::memcpy(c + 26, relo_pose + 7 * i, 56); std::memcpy(c + 33, prev_relo_t + 3 * i, 24); std::memcpy(c + 36, prev_relo_r + 9 * i, 72);
     }
-    for (double v : h) if (!(v == v)) { set_error("relocalization_fix: NaN in the input"); return TCV_ERR_NUMERIC; }
-    double *d = nullptr;
-    hipError_t e = tcv::dev_malloc((void **)&d, sizeof(double) * (nin + nout));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    int rc = TCV_OK;
-    e = hipMemcpy(d, h.data(), sizeof(double) * nin, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipStream_t st = tcv::util_stream();
-        hipLaunchKernelGGL(relo_fix_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, d, d + nin);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = tcv::stream_wait(st);
-        std::vector<double> ho(nout);
-        if (e == hipSuccess) e = hipMemcpy(ho.data(), d + nin, sizeof(double) * nout, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) for (int i = 0; i < n; i++) record_to_public(ho.data() + (size_t)RELO_REC * i, 1, &out[i]);
-    }
-    if (e != hipSuccess) rc = hip_fail(e, "relocalization_fix");
-    tcv::dev_free(d);
-    return rc;
+    for (size_t k = 0; k < nin; k++) if (!(h[k] == h[k])) { set_error("relocalization_fix: NaN in the input"); return TCV_ERR_NUMERIC; }
+    if (int rc = rt.run("relocalization_fix", [&](hipStream_t st) {
+            hipLaunchKernelGGL(relo_fix_kernel, dim3((n + 63) / 64), dim3(64), 0, st, n, rt.d_in(), rt.d_out());
+        })) return rc;
+    for (int i = 0; i < n; i++) record_to_public(rt.h_out() + (size_t)RELO_REC * i, 1, &out[i]);
+    return TCV_OK;
 }
 
 // tcv_batch_create: the relocalisation table of the batch, its prev_relo_* and the record buffer in one device allocation
@@ -105,7 +95,7 @@ int tcv_relo_attach(tcv_batch *b, hipStream_t st) {
         const Packed &pk = b->packed[w];
         const int l = p.relo_local;
         if (l < 0 || l >= (int)p.frame_pose.size() || p.frame_pose.size() > 64) { set_error("batch_create: relocalisation without a frame table (tcv_problem_set_frames)"); return TCV_ERR_INVALID; }
-        // where the blocks sit in the state vector: camera blocks in plan order (scatter_states, tcv_capi.hip)
+        // where the blocks sit in the state vector: camera blocks in plan order (scatter_states, tcv_batch.cpp)
         int off = 0, relo_off = -1;
         bool have0 = false, havel = false;
         for (int blk : pk.cam_block) {

@@ -243,7 +243,7 @@ def test_full_length_euroc_replay_with_the_association_in_the_loop(gpu, seq):
 
 
 def test_host_threads_with_their_own_estimators_reproduce_the_single_thread_run(gpu):
-    """Every entry point issues its work on the calling thread's own stream (tcv_capi.hip util_stream; destroyed when the thread ends):
+    """Every entry point issues its work on the calling thread's own stream (tcv_runtime.cpp util_stream; destroyed when the thread ends):
     three host threads, each driving its own four estimators in lock step, run side by side on the device -- two generations of them, so
     that the second one's streams are created after the first one's were given back -- and each reproduces the single-thread run bit
     for bit (same batches, hence same plans and the same additions; only what else is on the device differs)."""
