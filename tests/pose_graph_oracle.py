@@ -149,7 +149,9 @@ class Graph:
 def solve(g, opt=None, ceres=None):
     """ceres::Solve of :522 and what follows it.  opt: REFERENCE_OPTIONS overrides; ceres: CERES_DEFAULTS overrides.
     Returns dict(t, R, x, summary) with summary = dict(iterations=[records], termination, termination_code, initial_cost, final_cost,
-    yaw_drift, r_drift, t_drift, num_free_nodes, num_edges)."""
+    yaw_drift, r_drift, t_drift, num_free_nodes, num_edges).  A record of a valid step also carries what its decisions compare
+    (decision_margin below): model_cost_change, step_norm and x_norm of the parameter test, and gradient_max after an accepted step
+    (the first record: at entry)."""
     C = dict(CERES_DEFAULTS, **(ceres or {}))
     G = Graph(g, opt)
     x = G.x0()
@@ -166,6 +168,7 @@ def solve(g, opt=None, ceres=None):
         its.append(dict(cost=cost, cost_candidate=0.0, rho=0.0, radius=C["initial_trust_region_radius"], step=1))
         scale = 1.0 / (1.0 + np.sqrt((J * J).sum(0)))      # jacobi scaling, fixed at iteration 0
         gmax = float(np.max(np.abs(J.T @ r)))
+        its[0]["gradient_max"] = gmax
         radius, dec, invalid, it = C["initial_trust_region_radius"], 2.0, 0, 0
         done = gmax <= C["gradient_tolerance"]
         if done:
@@ -205,20 +208,22 @@ def solve(g, opt=None, ceres=None):
             dxn = np.linalg.norm((xc - x)[free]); xn = np.linalg.norm(x[free])
             cc = cost - cand
             rho = cc / mcc
+            rec = dict(cost_candidate=cand, rho=rho, radius=radius, model_cost_change=mcc, step_norm=float(dxn), x_norm=float(xn))
             if dxn <= C["parameter_tolerance"] * (xn + C["parameter_tolerance"]):
-                its.append(dict(cost=cost, cost_candidate=cand, rho=rho, radius=radius, step=0)); summary["termination"] = "CONVERGENCE_PARAMETER"; break
+                its.append(dict(rec, cost=cost, step=0)); summary["termination"] = "CONVERGENCE_PARAMETER"; break
             if abs(cc) <= C["function_tolerance"] * cost:
-                its.append(dict(cost=cost, cost_candidate=cand, rho=rho, radius=radius, step=0)); summary["termination"] = "CONVERGENCE_FUNCTION"; break
+                its.append(dict(rec, cost=cost, step=0)); summary["termination"] = "CONVERGENCE_FUNCTION"; break
             if rho > C["min_relative_decrease"]:
                 x = xc
                 J, r, cost = G.linearize(x)
-                its.append(dict(cost=cost, cost_candidate=cand, rho=rho, radius=radius, step=1))
+                gmax = float(np.max(np.abs(J.T @ r)))
+                its.append(dict(rec, cost=cost, step=1, gradient_max=gmax))
                 radius = min(C["max_trust_region_radius"], radius / max(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) ** 3))
                 dec = 2.0
-                if float(np.max(np.abs(J.T @ r))) <= C["gradient_tolerance"]:
+                if gmax <= C["gradient_tolerance"]:
                     summary["termination"] = "CONVERGENCE_GRADIENT"; break
             else:
-                its.append(dict(cost=cost, cost_candidate=cand, rho=rho, radius=radius, step=0))
+                its.append(dict(rec, cost=cost, step=0))
                 radius /= dec; dec *= 2.0
     N = G.N
     R = np.array([ypr2R(x[i, 0], G.ypr[i, 1], G.ypr[i, 2]) for i in range(N)])
@@ -228,6 +233,38 @@ def solve(g, opt=None, ceres=None):
     summary.update(iterations=its, termination_code=TERMINATION_CODE[summary["termination"]], initial_cost=its[0]["cost"] + fixed_cost,
                    final_cost=cost + fixed_cost, yaw_drift=float(yaw_drift), r_drift=r_drift, t_drift=t_drift)
     return dict(t=x[:, 1:].copy(), R=R, x=x, summary=summary)
+
+
+def decision_margin(summary, ceres=None):
+    """How close a solve came to deciding otherwise: the smallest |quantity / threshold - 1| over every floating-point comparison the loop
+    made, as (margin, what, record).  In the order of the loop, per record of a valid step: step_norm against parameter_tolerance * (x_norm +
+    parameter_tolerance); |cost change| against function_tolerance * cost; rho against min_relative_decrease; after an accepted step (and
+    at entry) gradient_max against gradient_tolerance.  A comparison the loop did not reach, or whose threshold is zero, is left out.
+    An invalid step (a pivot or model_cost_change not positive) is a margin of 0: it compares against zero."""
+    C = dict(CERES_DEFAULTS, **(ceres or {}))
+    best = (np.inf, "none", 0)
+
+    def see(q, thr, what, n):
+        nonlocal best
+        if thr > 0.0 and abs(q / thr - 1.0) < best[0]:
+            best = (abs(q / thr - 1.0), what, n)
+
+    its = summary["iterations"]
+    for n, rec in enumerate(its):
+        if rec["step"] < 0:
+            return 0.0, "invalid step", n
+        if n > 0:
+            cost_before = its[n - 1]["cost"] if rec["step"] == 1 else rec["cost"]      # (an accepted step's record holds the new cost)
+            see(rec["step_norm"], C["parameter_tolerance"] * (rec["x_norm"] + C["parameter_tolerance"]), "parameter_tolerance", n)
+            if n == len(its) - 1 and summary["termination"] == "CONVERGENCE_PARAMETER":
+                break
+            see(abs(cost_before - rec["cost_candidate"]), C["function_tolerance"] * cost_before, "function_tolerance", n)
+            if n == len(its) - 1 and summary["termination"] == "CONVERGENCE_FUNCTION":
+                break
+            see(rec["rho"], C["min_relative_decrease"], "min_relative_decrease", n)
+        if "gradient_max" in rec:
+            see(rec["gradient_max"], C["gradient_tolerance"], "gradient_tolerance", n)
+    return best
 
 
 # ------------------------------------------------------------------------------------------------ seeded test edges
@@ -288,3 +325,46 @@ def test_graphs():
     cur = rng.choice(np.arange(60, 300), 40, replace=False)
     G["n300"] = make_graph(13, 300, [(int(c), int(rng.integers(1, c - 30))) for c in sorted(cur)], drift=0.005, loop_noise=0.01)
     return G
+
+
+# ------------------------------------------------------------------------------------------------ graphs of a chosen shape
+def shape_graph(seed, nb, nk, **make_graph_kw):
+    """A graph whose elimination order is (free, band, border) = (nb + nk, nb, nk): node 0 constant, nodes 1 .. nb the band, each of the
+    last nk nodes the newer end of one loop whose older end is the free node 1 + (3 k mod nb).  Without a border a loop (two when nb > 6) to
+    the constant node 0 gives the problem a residual and makes no border; without any loop the solve would end at entry."""
+    n = 1 + nb + nk
+    loops = []
+    for k in range(nk):
+        cur, old = 1 + nb + k, 1 + (3 * k) % nb
+        loops.append((cur, old if old < cur else 1))
+    if nk == 0:
+        loops.append((nb, 0))
+        if nb > 6:
+            loops.append((nb // 2 + 1, 0))
+    return make_graph(seed, n, loops, **dict(dict(drift=0.01, loop_noise=0.005), **make_graph_kw))
+
+
+# (nb, nk) on and next to every size built into the kernel; the unknowns are nbs = 4 nb in the band, m = 4 nk in the border, the border
+# has M1 = m + 1 rows with the right-hand side (csrc/tcv_pose_graph.hip: PG_LD 20, PG_KC 32, PG_PANEL_COLS 301, PG_PANEL_ROWS 320, Schur
+# tiles of 64, 256 threads)
+BOUNDARY_SHAPES = [
+    (1, 0), (2, 0), (4, 0),              # nbs 4, 8, 16 < PG_LD: narrower than the half-bandwidth, one partial substitution chunk
+    (5, 0), (6, 0),                      # nbs 20: exactly one chunk; 24: one and a partial one
+    (8, 1), (9, 16),                     # nbs 32 = PG_KC, 36; (8, 1) the smallest border
+    (75, 0), (76, 0),                    # nbs 300: the last size of one panel; 304: a second panel of three columns, a node across the seam
+    (80, 0), (81, 0),                    # nbs 320 = PG_PANEL_ROWS, 324
+    (150, 0), (151, 0),                  # nbs 600, 604: a third panel of two columns
+    (1, 2), (5, 5),                      # the border larger than / as large as the band
+    (8, 15), (8, 16), (8, 17),           # m 60, 64, 68 around one Schur tile
+    (8, 63), (8, 64), (9, 65),           # M1 253, 257, 261 around the 256-thread row loops
+    (12, 128), (8, 256),                 # m 512; m 1024 with TCV_POSE_GRAPH_MAX_LOOPS loops
+    (76, 17), (81, 64),                  # a panel seam and a tile edge in one graph
+]
+# seed per shape: every decision of the oracle's solve at least 1 % from its threshold (tests/test_pose_graph_cpu.py)
+BOUNDARY_SEEDS = {shape: 100 + i for i, shape in enumerate(BOUNDARY_SHAPES)}
+BOUNDARY_SEEDS.update({(12, 128): 300, (8, 256): 301})
+
+
+def boundary_graphs():
+    """name -> graph for BOUNDARY_SHAPES"""
+    return {"b%d_k%d" % (nb, nk): shape_graph(BOUNDARY_SEEDS[(nb, nk)], nb, nk) for (nb, nk) in BOUNDARY_SHAPES}

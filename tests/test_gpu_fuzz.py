@@ -63,5 +63,11 @@ def test_factor_evaluators_on_random_inputs(gpu):
     assert run("fuzz_factors", 500, 0) == 0
 
 
+def test_pose_graphs_on_random_structures(gpu):
+    """200 seeded graphs, each alone and sixteen at a time in ragged batches (tests/test_pose_graph_cpu.py holds the same seed range to
+    decisions 1 % clear of their thresholds on the oracle alone)"""
+    assert run("fuzz_pose_graph", 200, 0) == 0
+
+
 def test_native_estimator_on_stress_streams(gpu):
     assert run("fuzz_estimator", 6, 0, 40) == 0

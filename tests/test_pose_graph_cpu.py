@@ -244,3 +244,74 @@ def test_elimination_order_band_and_border(pg):
     assert list(np.where(st["position"] < 0)[0]) == [0, 1, 2, 3] and st["fixed_edges"] == 7 == len(ref.fixed) and st["border"] == 2
     st = pg.plan_stats(G["n300"])
     assert st["border"] == 40 and st["band"] == 259 and st["scratch_bytes"] < 4 << 20
+
+
+# ------------------------------------------------------------------------- what the boundary and fuzz tests of the GPU suite rest on
+MARGIN = 0.01      # derived, not measured: the GPU file's relative cost gate (2.3e-13) moves a cost-change ratio next to the 1e-6 function tolerance
+#                    by at most about 5e-7 relative, and every other decision by less; 1 % is 2e4 times that
+
+
+def test_boundary_graphs_have_the_intended_shapes(pg):
+    """the table of pose_graph_oracle.BOUNDARY_SHAPES is only worth something if the host's order really produces these shapes"""
+    G = PO.boundary_graphs()
+    assert len(G) == len(PO.BOUNDARY_SHAPES) == 25
+    for (nb, nk), (name, g) in zip(PO.BOUNDARY_SHAPES, G.items()):
+        st = pg.plan_stats(g)
+        assert (st["free"], st["band"], st["border"]) == (nb + nk, nb, nk), (name, st)
+        assert len(g["t"]) == 1 + nb + nk and len(g["loops"]) <= pg.MAX_LOOPS
+    sizes = {(4 * nb, 4 * nk) for nb, nk in PO.BOUNDARY_SHAPES}
+    assert {nbs for nbs, _ in sizes} >= {4, 8, 16, 20, 24, 32, 36, 300, 304, 320, 324, 600, 604}
+    assert {m for _, m in sizes} >= {4, 60, 64, 68, 252, 256, 260, 512, 1024}
+
+
+def test_boundary_graphs_decide_clear_of_every_threshold():
+    """every comparison of the oracle's loop at least 1 % from its threshold, so that the device may not legitimately decide otherwise;
+    no invalid step; a graph that fails this gets another seed in pose_graph_oracle.BOUNDARY_SEEDS, none is skipped on the GPU"""
+    for name, g in PO.boundary_graphs().items():
+        s = PO.solve(g)["summary"]
+        margin, what, record = PO.decision_margin(s)
+        print("%-10s records %d %-22s margin %.3g (%s, record %d)" % (name, len(s["iterations"]), s["termination"], margin, what, record))
+        assert all(i["step"] >= 0 for i in s["iterations"]) and 2 <= len(s["iterations"]) <= 6, name
+        assert s["termination"] in ("CONVERGENCE_FUNCTION", "CONVERGENCE_PARAMETER", "NO_CONVERGENCE"), (name, s["termination"])
+        assert margin >= MARGIN, (name, margin, what, record)
+
+
+def test_decision_margin_sees_each_threshold():
+    """decision_margin on records made by hand: each comparison is found, in the loop's order, and not past the one that ended the solve"""
+    first = dict(cost=1.0, cost_candidate=0.0, rho=0.0, radius=1e4, step=1, gradient_max=1.0)
+    rec = dict(cost=0.5, cost_candidate=0.5, rho=0.9, radius=1e4, step=1, model_cost_change=0.55, step_norm=1.0, x_norm=10.0, gradient_max=1.0)
+    S = lambda *its, term="NO_CONVERGENCE": dict(iterations=list(its), termination=term)
+    assert PO.decision_margin(S(first, rec))[0] > 0.99
+    assert PO.decision_margin(S(dict(first, gradient_max=1.005e-10)))[:2] == (pytest.approx(0.005), "gradient_tolerance")
+    assert PO.decision_margin(S(first, dict(rec, gradient_max=0.998e-10)))[1:] == ("gradient_tolerance", 1)
+    assert PO.decision_margin(S(first, dict(rec, rho=1.003e-3)))[:2] == (pytest.approx(0.003), "min_relative_decrease")
+    assert PO.decision_margin(S(first, dict(rec, cost_candidate=1.0 - 1.004e-6)))[:2] == (pytest.approx(0.004, rel=1e-3), "function_tolerance")
+    assert PO.decision_margin(S(first, dict(rec, step_norm=1.002e-7)))[:2] == (pytest.approx(0.002, rel=1e-3), "parameter_tolerance")
+    # a rejected record carries the unchanged cost; the record that ends on the function tolerance is not asked for its rho
+    end = dict(rec, cost=1.0, cost_candidate=1.0 - 0.5e-6, rho=1.0001e-3, step=0)
+    assert PO.decision_margin(S(first, end, term="CONVERGENCE_FUNCTION"))[:2] == (pytest.approx(0.5, rel=1e-3), "function_tolerance")
+    assert PO.decision_margin(S(first, dict(end, step=-1)))[0] == 0.0
+
+
+def test_fuzz_population_decides_clear_of_the_thresholds():
+    """tests/dev/fuzz_pose_graph.py over the seed range of its GPU gate (tests/test_gpu_fuzz.py), the oracle alone: at most 2 % of the cases
+    within 1 % of a threshold (those the fuzzer lists and skips), every termination it claims to cover present, no invalid step"""
+    import sys
+    dev = os.path.join(ROOT, "tests", "dev")
+    sys.path.insert(0, dev)
+    try:
+        import fuzz_pose_graph as F
+    finally:
+        sys.path.remove(dev)
+    assert (F.MARGIN, F.MAX_SKIPPED) == (MARGIN, 0.02)
+    pop = F.population(200, 0)
+    close = [(seed, what, m) for seed, _, what, _, m in pop if m[0] < MARGIN]
+    tally = {}
+    for c in pop:
+        tally[c[3]["summary"]["termination"]] = tally.get(c[3]["summary"]["termination"], 0) + 1
+    print("terminations:", tally, " within the band:", close)
+    assert len(close) <= 0.02 * len(pop), close
+    assert not any(i["step"] < 0 for c in pop for i in c[3]["summary"]["iterations"])
+    assert all(tally.get(k, 0) >= 10 for k in ("CONVERGENCE_GRADIENT", "CONVERGENCE_FUNCTION", "CONVERGENCE_PARAMETER", "NO_CONVERGENCE")), tally
+    shapes = [(len(c[3]["summary"]["iterations"]), c[3]["summary"]["num_free_nodes"]) for c in pop]
+    assert max(f for _, f in shapes) >= 100 and min(f for _, f in shapes) <= 1
