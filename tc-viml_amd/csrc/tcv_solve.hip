@@ -925,6 +925,7 @@ __device__ __noinline__ double linearize(TCV_CTX_PARAMS, const lds_d *x, bool fi
     if (P.prior_n > 0 && ABL(C, AB_PRIOR_A)) {
         const int n = P.prior_n, k0 = C.W->prior_k0, nr = n - k0;      // J0 | r0 without their leading zero rows (tcv_packed.h)
         cst_d *J0g = dp + C.W->d_prior, *r0 = J0g + nr * n, *x0 = r0 + nr;
+        // (the three-way choice in_lds / staged / global is mirrored by prior_paths() of tests/prior_path_cases.py: keep the two in step)
         const bool in_lds = ((nr * n + 1) & ~1) + 2 * n <= C.stage_cap;
         // chain mode: a J0 that does not fit goes through the pool in two column pieces (priors too tall for two pieces take the HBM/L2 path below)
         const int pcap = CHAIN ? (P.c_pool - 2 * n - 2) / nr - 1 : 0;
@@ -948,6 +949,7 @@ __device__ __noinline__ double linearize(TCV_CTX_PARAMS, const lds_d *x, bool fi
         if (staged) {
             // J0 does not fit the pool in one piece: columns [0, ns) and [ns, n) are staged one after the other.  The big
             // piece comes second and stays resident for the J0' r pass, so only the small one is read twice.
+            // (the split nb | ns is mirrored by prior_paths() of tests/prior_path_cases.py)
             int nb = min(n, pcap + 1);
             if ((nr & 1) && ((n - nb) & 1)) nb--;      // keep the second piece 16-byte aligned: nr * (n - nb) even
             const int ns = n - nb;
@@ -963,7 +965,11 @@ __device__ __noinline__ double linearize(TCV_CTX_PARAMS, const lds_d *x, bool fi
                 __syncthreads();
                 if (rown) {
                     int j = 0;
-                    for (; j + 7 < cn; j += 8) {      // eight columns' loads in flight, the two accumulators updated in the original order
+                    // eight columns' loads in flight.  r takes the even columns of a piece and r2 the odd ones, counted from the piece's first
+                    // column: with an even ns that is the order of the one-piece path (prior_row_lds) term by term, so r keeps its bits; with an
+                    // odd ns the second piece starts on an odd column of J0 and the two accumulators swap roles there (r: the even columns below
+                    // ns, then the ODD columns from ns on) -- the same sum in another rounding order (tests/test_gpu_prior_paths.py, ns = 1)
+                    for (; j + 7 < cn; j += 8) {
                         double a8[8], d8[8];
 #pragma unroll
                         for (int u = 0; u < 8; u++) { a8[u] = Jp[row + nr * (j + u)]; d8[u] = pdx2[c0 + j + u]; }
@@ -2455,6 +2461,7 @@ __global__ void __launch_bounds__(NT) __attribute__((disable_tail_calls)) __attr
         if (P.prior_n > 0 && ABL(C, AB_SETUP)) {
             const int n = P.prior_n, nr = n - W->prior_k0;      // J0 without its leading zero rows: nr x n, column-major (tcv_packed.h)
             cst_d *J0g = C.dp + W->d_prior;
+            // (lds_cap, in_lds and ldj are mirrored by prior_paths() of tests/prior_path_cases.py)
             const int lds_cap = (C.ntiles << 8) + (CHAIN ? P.c_pool : 0);
             const bool in_lds = nr * n <= lds_cap;
             // J0 in LDS: every lane forms 2 x 2 blocks of entries (columns 2a, 2a+1 against 2b, 2b+1, b <= a), so that four loaded values feed

@@ -91,7 +91,9 @@ def test_prior_with_an_odd_number_of_stored_rows(gpu):
 
 
 def test_prior_without_zero_rows(gpu):
-    """k0 = 0: the golden prior with its zero rows replaced by a weak diagonal (75 stored rows)"""
+    """k0 = 0: the golden prior with its zero rows replaced by a weak diagonal (75 stored rows).  A one-window batch has the whole LDS of
+    its CU, so J0 is staged in ONE piece here; the two-piece staging of such a prior (batches larger than the chip) and the paths that read
+    J0 from global memory are the cases of tests/test_gpu_prior_paths.py."""
     pre, main, z = golden_windows()
     p = main["prior"]
     J0 = np.array(p["J0"], dtype=float)
