@@ -145,7 +145,7 @@ __device__ __noinline__ int jacobi_eig(lds_d *M, VP *V, int d, int ld, lds_d *ro
 // symmetric so rows are contiguous; the reflectors are written to a packed side buffer);  (2) every eigenvalue of T by
 // multisection on Sturm counts (absolute accuracy eps |T|, the class of the tridiagonal QR inside
 // Eigen::SelfAdjointEigenSolver that the reference calls);  (3) every eigenvector of T from the twisted factorisation of
-// T - lambda I (Fernando / Parlett), one lane per eigenvector, in the matrix's own storage;  (4) modified Gram-Schmidt inside
+// T - lambda I (Fernando / Parlett), two lanes per eigenvector, in the matrix's own storage and the global scratch;  (4) modified Gram-Schmidt inside
 // clusters of close eigenvalues (the near-null gauge directions);  (5) back-transformation by the reflectors, three or four lanes
 // per column, no barriers.  Returns false (caller falls back to the Jacobi sweep) if the result fails the orthogonality / trace
 // checks.  A is overwritten by the eigenvectors (columns, ascending eigenvalues in lam), Hq takes (n - 2)(n - 1) / 2 + 1 doubles
@@ -184,6 +184,40 @@ __device__ __forceinline__ double fast_rcp(double q) {
     r = fma(fma(-q, r, 1.0), r, r);
     return r;
 }
+// The 64-lane xor butterfly (partners lane ^ 32, 16, 8, 4, 2, 1 in that order, every lane ends with the result) without ds_bpermute: the
+// exchange with lane ^ 32 and lane ^ 16 is v_permlane32_swap / v_permlane16_swap of a value with itself (one result holds the lower half's or
+// the even rows' value in both halves, the other the upper half's or the odd rows': their combination is own (op) partner on one side and
+// partner (op) own on the other), lane ^ 8 is row_ror:8, lane ^ 4 two bank-masked row shifts, lane ^ 2 and lane ^ 1 quad_perm.  The operation
+// must be commutative bit for bit (+, fmax of non-negative values): then every lane holds what the __shfl_xor butterfly gave it.
+template <int CTRL, int BANKS>
+__device__ __forceinline__ double dpp_into(double old, double v) {
+    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+    const unsigned olo = (unsigned)__double2loint(old), ohi = (unsigned)__double2hiint(old);
+    return lane_pair(__builtin_amdgcn_update_dpp(olo, lo, CTRL, 0xf, BANKS, false), __builtin_amdgcn_update_dpp(ohi, hi, CTRL, 0xf, BANKS, false));
+}
+template <int O> __device__ __forceinline__ double xor_partner(double v) {      // the value of lane ^ O, O = 8, 4, 2, 1
+    if (O == 8) return down_dpp<0x128>(v);                                      // row_ror:8
+    if (O == 4) return dpp_into<0x114, 0xA>(dpp_into<0x104, 0x5>(v, v), v);     // banks 0, 2 from lane + 4 (row_shl:4), banks 1, 3 from lane - 4 (row_shr:4)
+    if (O == 2) return down_dpp<0x4E>(v);                                       // quad_perm [2,3,0,1]
+    return down_dpp<0xB1>(v);                                                   // quad_perm [1,0,3,2]
+}
+template <class OP> __device__ __forceinline__ double wave_all_xor(double v, OP op) {
+    {
+        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+        const auto sl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), sh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        v = op(lane_pair(sl[0], sh[0]), lane_pair(sl[1], sh[1]));
+    }
+    {
+        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+        const auto sl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), sh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        v = op(lane_pair(sl[0], sh[0]), lane_pair(sl[1], sh[1]));
+    }
+    v = op(v, xor_partner<8>(v)); v = op(v, xor_partner<4>(v)); v = op(v, xor_partner<2>(v)); v = op(v, xor_partner<1>(v));
+    return v;
+}
+struct OpAdd { __device__ __forceinline__ double operator()(double a, double b) const { return a + b; } };
+struct OpMax { __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); } };
+struct OpMin { __device__ __forceinline__ double operator()(double a, double b) const { return fmin(a, b); } };
 // eigenvalue k of the symmetric tridiagonal (dv, e2 = squared off-diagonal) by (LPE + 1)-section on Sturm counts: LPE lanes per
 // eigenvalue test LPE interior points per trip, GPW eigenvalues per wavefront.  512 threads: 7-section, ten eigenvalues per wavefront
 // (lanes 60..63 idle), 22 trips: 7^-22 < 4^-30 of the Gershgorin interval (the recurrence is the cost, so fewer trips on more lanes is
@@ -553,10 +587,23 @@ __device__ __noinline__ void eig_backtransform_wy(const lds_d *Hq_, lds_d *Z_, c
 }
 
 __device__ __forceinline__ double rank2(double a, double vr, double wc, double wr, double vc) { return a - (vr * wc + wr * vc); }
+// the scalars of a Householder step from alpha = x[0] and xn2 = |x[1:]|^2: beta = -sign(alpha) |x|, tau = (beta - alpha) / beta, scale = 1 / (alpha - beta)
+__device__ __forceinline__ void householder_scalars(double alpha, double xn2, double &beta, double &tau, double &scale) {
+    tau = 0.0; beta = alpha; scale = 0.0;
+    if (xn2 > 0.0) {
+        const double nn = alpha * alpha + xn2;
+        double y = __builtin_amdgcn_rsq(nn);                 // |x| = nn * rsqrt(nn), two Newton steps
+        y = y * fma(-0.5 * nn * y, y, 1.5);
+        y = y * fma(-0.5 * nn * y, y, 1.5);
+        beta = -copysign(nn * y, alpha);
+        tau = (beta - alpha) * fast_rcp(beta);
+        scale = fast_rcp(alpha - beta);
+    }
+}
 template <int NT>
 // (disable_tail_calls on every function that calls a non-inlined one: with the IR `tail` marker on a call the callee saves and restores
 // every callee-saved VGPR it touches -- up to 112 scratch stores and loads per call; without it the callees save nothing, tcv_solve.hip)
-__device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag(lds_d *A_, lds_d *Hq_, lds_d *sm_, lds_d *lam_, int n_, int ld_, int tid, gbl_d *dbg, int flags_) {
+__device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag(lds_d *A_, lds_d *Hq_, lds_d *sm_, lds_d *lam_, int n_, int ld_, int tid, gbl_d *dbg, int flags_, gbl_d *scrv) {
     lds_d *A = uni_lds<2>(A_), *Hq = uni_lds<2>(Hq_), *sm = uni_lds<2>(sm_), *lam = uni_lds<2>(lam_);
     const int n = uni_i<2>(n_), ld = uni_i<2>(ld_), flags = uni_i<2>(flags_);
     const bool old_search = (flags & 1) != 0;
@@ -564,10 +611,22 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag
     lds_d *Z = A;                          // the eigenvectors overwrite the matrix: after the tridiagonalisation only T (dv, ev), the
                                            // reflectors (packed in Hq) and tau are needed
     lds_d *dv = sm, *ev = sm + 80, *tauv = sm + 160, *vbuf = sm + 240, *pbuf = sm + 320, *red = sm + 400, *e2 = sm + 416;
-    lds_d *ubuf = sm + 512, *xold = sm + 608, *xnb = sm + 704;
+    lds_d *ubuf = sm + 512, *xold = sm + 608, *xnb = sm + 704, *hsc = sm + 708;      // (sm + 706 .. 719 are spare: 706, 707 trace and sum lambda, 708 .. 710 the next step's scalars)
     const int lane = tid & 63, wave = tid >> 6;
-    double trace = 0;
-    for (int i = 0; i < n; i++) trace += A[i * ld + i];
+    // trace(A') and, later, the sum of the eigenvalues feed the diagnostics and the round-2 gate only: one lane of the last wavefront forms
+    // each (same order of summation, the loads eight at a time) and leaves it in a spare double of sm
+    lds_d *spare = sm + 706;               // [0] trace, [1] sum lambda
+    if (tid == NT - 64) {
+        double tr = 0;
+        for (int i0 = 0; i0 < n; i0 += 8) {
+            double a[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) a[u] = A[min(i0 + u, n - 1) * (ld + 1)];
+#pragma unroll
+            for (int u = 0; u < 8; u++) if (i0 + u < n) tr += a[u];
+        }
+        spare[0] = tr;
+    }
     long long t_last = clock64();
 #ifdef TCV_PROFILE
 #define EMARK(id) do { const long long t_ = clock64(); if (tid == 0 && dbg) dbg[8 + (id)] += (double)(t_ - t_last); t_last = t_; } while (0)
@@ -622,18 +681,11 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag
         // the first half of the step (scalars, v, p, p'v) needs one lane per row: only the wavefronts that hold rows run it (the others would
         // execute the whole scalar chain for nothing); tau reaches the second half through tauv[i]
         if (tid < ((m + 63) & ~63)) {
-            const double xn2 = xnb[i & 1];
-            const double alpha = xrow[0];
-            double tau = 0.0, beta = alpha, scale = 0.0;
-            if (xn2 > 0.0) {
-                const double nn = alpha * alpha + xn2;
-                double y = __builtin_amdgcn_rsq(nn);                 // |x| = nn * rsqrt(nn), two Newton steps
-                y = y * fma(-0.5 * nn * y, y, 1.5);
-                y = y * fma(-0.5 * nn * y, y, 1.5);
-                beta = -copysign(nn * y, alpha);
-                tau = (beta - alpha) * fast_rcp(beta);
-                scale = fast_rcp(alpha - beta);
-            }
+            double tau, beta, scale;
+            // beta, tau and 1 / (alpha - beta) of every step but the first were formed inside the update of the step before (below), from the
+            // values this step would read: |x[1:]|^2 and alpha = the new A22[0][1]
+            if (i > 0) { beta = hsc[0]; tau = hsc[1]; scale = hsc[2]; }
+            else householder_scalars(xrow[0], xnb[0], beta, tau, scale);
             double pv = 0;
             if (r < m) {
                 const double a0 = A[(i + 1 + r) * ld + (i + 1)];
@@ -662,7 +714,16 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag
             // J column slots per lane (8 J >= m): three static sizes, so that the small trailing blocks of the late steps do not pay for ten
             // clamped loads and masked updates per lane -- the skipped slots held nothing (c >= m): the same sums, bit for bit
             const int part8 = tid & 7;
-#define TCV_R2_BODY(J, JV)                                                                                                           \
+            // The next step's scalar chain (rsq, two Newton steps, two reciprocals: ~250 cycles of dependent instructions that every wavefront
+            // with rows would otherwise run behind the barrier) is run here by one lane: lane 0 of every 8-lane group holds |x'[1:]|^2, its
+            // neighbour alpha' = x'[1] -- bit for bit the values the next step reads.  The lane is taken from the LAST wavefront that has rows
+            // in this update: it has a row pass less than wavefront 0 unless the padded block is a multiple of 32 rows.
+            const int chain_tid = 64 * min(NW - 1, (((m + 7) & ~7) >> 3) - 1);
+#define TCV_R2_NEXT_SCALARS(x2, xn0) do {                                                                                                \
+                const double an_ = down_dpp<0x101>(xn0);      /* lane + 1: column 1 */                                               \
+                if (tid == chain_tid && m > 1) { double b_, t_, s_; householder_scalars(an_, x2, b_, t_, s_); hsc[0] = b_; hsc[1] = t_; hsc[2] = s_; } \
+            } while (0)
+#define TCV_R2_BODY(J, JV)                                                                                                          \
             if ((tid & ~63) >> 3 < ((m + 7) & ~7)) {      /* a wavefront whose first row lies beyond the block has nothing to update */ \
                 /* what depends on the column only -- v, w = p + K v and the new first row x' -- once per step, not once per row pass. */ \
                 /* Column slots j < JV lie inside the block for every lane (8 JV <= the smallest m of the regime): no masks.  A slot */ \
@@ -683,7 +744,7 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag
                     x2 = in ? fma(xn[j], xn[j], x2) : x2;                                                                            \
                 }                                                                                                                    \
                 x2 += down_dpp<0x101>(x2); x2 += down_dpp<0x102>(x2); x2 += down_dpp<0x104>(x2);                                     \
-                if (tid == 8) xnb[(i + 1) & 1] = x2;      /* (lane 0 of the group of row 1) */                                       \
+                TCV_R2_NEXT_SCALARS(x2, xn[0]);                                                                                      \
                 for (int rr = tid >> 3; rr < ((m + 7) & ~7); rr += NT / 8) {                                                         \
                     const int rc = min(rr, m - 1);                                                                                   \
                     const double vr = vbuf[rc], wr = pbuf[rc] + K * vr;                                                              \
@@ -705,6 +766,7 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag
             }
             if (m > 40) { TCV_R2_BODY(10, 5) } else if (m > 16) { TCV_R2_BODY(5, 2) } else { TCV_R2_BODY(2, 0) }
 #undef TCV_R2_BODY
+#undef TCV_R2_NEXT_SCALARS
         }
         SMARK(m > 40 ? 2 : (m > 16 ? 3 : 4));
         __syncthreads();
@@ -713,17 +775,26 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag
     if (tid == 0) { dv[n - 1] = A[(n - 1) * ld + n - 1]; ev[n - 1] = 0.0; }
     __syncthreads();
     for (int i = tid; i < n; i += NT) e2[i] = ev[i] * ev[i];
-    // Gershgorin interval, |T| and the pivot floor (every thread, redundantly)
+    // Gershgorin interval, |T| and the pivot floor
+    // one lane per row, then min / max over the lanes: exact operations, so the grouping does not matter (n <= 80: the rows sit in the
+    // first two wavefronts; dv[0] itself is a candidate like in the row-by-row form)
     double gl = dv[0], gu = dv[0], emax2 = 0;
-    for (int i = 0; i < n; i++) {
-        const double rad = (i > 0 ? fabs(ev[i - 1]) : 0.0) + (i + 1 < n ? fabs(ev[i]) : 0.0);
-        gl = fmin(gl, dv[i] - rad); gu = fmax(gu, dv[i] + rad);
-        if (i + 1 < n) emax2 = fmax(emax2, ev[i] * ev[i]);
+    if (tid < 128) {
+        if (tid < n) {
+            const int i = tid;
+            const double em = ev[max(i - 1, 0)], e0 = ev[i], d = dv[i];
+            const double rad = (i > 0 ? fabs(em) : 0.0) + (i + 1 < n ? fabs(e0) : 0.0);
+            gl = fmin(gl, d - rad); gu = fmax(gu, d + rad);
+            if (i + 1 < n) emax2 = fmax(emax2, e0 * e0);
+        }
+        gl = wave_all_xor(gl, OpMin()); gu = wave_all_xor(gu, OpMax()); emax2 = wave_all_xor(emax2, OpMax());
+        if (lane == 0) { red[3 * wave] = gl; red[3 * wave + 1] = gu; red[3 * wave + 2] = emax2; }
     }
+    __syncthreads();
+    gl = fmin(red[0], red[3]); gu = fmax(red[1], red[4]); emax2 = fmax(red[2], red[5]);
     const double tnorm = fmax(fabs(gl), fabs(gu));
     const double pivmin = 1e-290 * fmax(1.0, emax2);
     gl -= 2.2e-16 * tnorm * n + pivmin; gu += 2.2e-16 * tnorm * n + pivmin;
-    __syncthreads();
     EMARK(0);
     // ---- (2) eigenvalues by multisection
     if (old_search) {
@@ -732,87 +803,177 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag
     } else eig_values_above_eps<NT>(dv, e2, ubuf, (lds_i *)vbuf, lam, n, gu, tnorm, tid);      // ubuf + xold: 192 doubles >= 2 n; vbuf + pbuf: 160 doubles >= 257 ints
     __syncthreads();
     EMARK(1);
-    // ---- (3) eigenvectors of T: twisted factorisation, one lane per eigenvector (column k of Z as workspace)
+    // ---- (3) eigenvectors of T: twisted factorisation, two lanes per eigenvector (column k of Z and of the global scratch as workspace)
     // eigenvalues <= eps are zeroed by the thresholding of marginalization_factor.cpp:284-293: their vectors are never
     // used, and inside that (possibly large, rank-deficient) null cluster they are not even defined -> zero columns
     double resid = 0.0;
-    if (tid < n && !(lam[tid] > 1e-8)) {
-        for (int i = 0; i < n; i++) Z[i * ld + tid] = 0.0;
-    } else if (tid < n) {
-        const int k = tid;
+    // Two lanes per eigenvector k, in different wavefronts: lane k forms the forward pivots D+ (into column k of Z, as before) while lane
+    // 128 + k forms the backward pivots D- into the workgroup's global scratch (entry i of eigenvector k at scrv[80 i + k]: idle unless the
+    // Jacobi safety net runs; the stores are not waited for).  Behind a barrier both lanes find the twist index from the stored pivots --
+    // the same values, the same comparisons as the running form --, behind a second one lane k sweeps z upwards from the twist index in
+    // place and lane 128 + k downwards (D- from the scratch, z into the rows of Z that D+ has left), and behind a third lane k adds the lower
+    // half's squares to its norm in the order of the one-lane form (1, rows rbest - 1 .. 0, rows rbest + 1 .. n - 1) and scales the column.
+    // The independent loads (pivots, e, the reciprocals of the pivots) go four or eight at a time; every recurrence keeps its operations.
+    {
+        static_assert(NT >= 256, "the second lane of eigenvector k is lane 128 + k");
+        const bool roleA = tid < n, roleB = tid >= 128 && tid - 128 < n;
+        const int k = roleA ? tid : (roleB ? tid - 128 : 0);
         const double l = lam[k];
-        double dp = dv[0] - l;
-        if (fabs(dp) < pivmin) dp = -pivmin;
-        Z[k] = dp;
-        for (int i = 0; i + 1 < n; i++) {
-            dp = fma(-e2[i], fast_rcp(dp), dv[i + 1] - l);
+        const bool live = (roleA || roleB) && (l > 1e-8);
+        gbl_d *dmc = scrv + k;
+        lds_d *zc = Z + k;
+        if (roleA && !live) {
+            for (int i = 0; i < n; i++) zc[i * ld] = 0.0;
+        } else if (roleA) {
+            double dp = dv[0] - l;
             if (fabs(dp) < pivmin) dp = -pivmin;
-            Z[(i + 1) * ld + k] = dp;
-        }
-        // backward pivots D-: the first pass finds the twist index (smallest |gamma|), the second one -- the same recurrence, bit for
-        // bit -- leaves D-_(rbest+1 .. n-1) in the rows of the column that D+ no longer needs (a second n x n workspace would not fit
-        // an 80 KB workgroup)
-        double dm = dv[n - 1] - l;
-        if (fabs(dm) < pivmin) dm = -pivmin;
-        double gbest = fabs(Z[(n - 1) * ld + k] + dm - (dv[n - 1] - l));
-        int rbest = n - 1;
-        for (int i = n - 2; i >= 0; i--) {
-            dm = fma(-e2[i], fast_rcp(dm), dv[i] - l);
+            zc[0] = dp;
+            for (int i = 0; i + 1 < n; i++) {
+                dp = fma(-e2[i], fast_rcp(dp), dv[i + 1] - l);
+                if (fabs(dp) < pivmin) dp = -pivmin;
+                zc[(i + 1) * ld] = dp;
+            }
+        } else if (live) {
+            double dm = dv[n - 1] - l;
             if (fabs(dm) < pivmin) dm = -pivmin;
-            const double g = fabs(Z[i * ld + k] + dm - (dv[i] - l));
-            if (g < gbest) { gbest = g; rbest = i; }
-        }
-        if (rbest < n - 1) {
-            dm = dv[n - 1] - l;
-            if (fabs(dm) < pivmin) dm = -pivmin;
-            Z[(n - 1) * ld + k] = dm;
-            for (int i = n - 2; i > rbest; i--) {
+            dmc[(n - 1) * MARG_MAX_N] = dm;
+            for (int i = n - 2; i >= 0; i--) {
                 dm = fma(-e2[i], fast_rcp(dm), dv[i] - l);
                 if (fabs(dm) < pivmin) dm = -pivmin;
-                Z[i * ld + k] = dm;
+                dmc[i * MARG_MAX_N] = dm;
             }
         }
-        double z = 1.0, nrm2 = 1.0;
-        for (int i = rbest - 1; i >= 0; i--) {          // z_i = -(e_i / D+_i) z_{i+1}
-            z = -ev[i] * fast_rcp(Z[i * ld + k]) * z;
-            Z[i * ld + k] = z;
-            nrm2 += z * z;
+        __syncthreads();
+        double gbest = 0.0;
+        int rbest = n - 1;
+        if (live) {
+            gbest = fabs(zc[(n - 1) * ld] + dmc[(n - 1) * MARG_MAX_N] - (dv[n - 1] - l));
+            for (int i0 = n - 2; i0 >= 0; i0 -= 8) {
+                double dp[8], dm[8], dd[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) { const int i = max(i0 - u, 0); dp[u] = zc[i * ld]; dm[u] = dmc[i * MARG_MAX_N]; dd[u] = dv[i]; }
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const double g = fabs(dp[u] + dm[u] - (dd[u] - l));
+                    if (i0 - u >= 0 && g < gbest) { gbest = g; rbest = i0 - u; }
+                }
+            }
         }
-        z = 1.0;
-        for (int i = rbest; i + 1 < n; i++) {           // z_{i+1} = -(e_i / D-_{i+1}) z_i
-            z = -ev[i] * fast_rcp(Z[(i + 1) * ld + k]) * z;
-            Z[(i + 1) * ld + k] = z;
-            nrm2 += z * z;
+        __syncthreads();
+        double nrm2 = 1.0;
+        if (live && roleA) {
+            double z = 1.0;
+            int i = rbest - 1;
+            for (; i >= 3; i -= 4) {                    // z_i = -(e_i / D+_i) z_{i+1}
+                double c[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) c[u] = zc[(i - u) * ld];
+#pragma unroll
+                for (int u = 0; u < 4; u++) c[u] = -ev[i - u] * fast_rcp(c[u]);
+#pragma unroll
+                for (int u = 0; u < 4; u++) { z = c[u] * z; zc[(i - u) * ld] = z; nrm2 += z * z; }
+            }
+            for (; i >= 0; i--) {
+                z = -ev[i] * fast_rcp(zc[i * ld]) * z;
+                zc[i * ld] = z;
+                nrm2 += z * z;
+            }
+        } else if (live) {
+            double z = 1.0;
+            int i = rbest;
+            for (; i + 4 < n; i += 4) {                 // z_{i+1} = -(e_i / D-_{i+1}) z_i
+                double c[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) c[u] = dmc[(i + 1 + u) * MARG_MAX_N];
+#pragma unroll
+                for (int u = 0; u < 4; u++) c[u] = -ev[i + u] * fast_rcp(c[u]);
+#pragma unroll
+                for (int u = 0; u < 4; u++) { z = c[u] * z; zc[(i + 1 + u) * ld] = z; }
+            }
+            for (; i + 1 < n; i++) {
+                z = -ev[i] * fast_rcp(dmc[(i + 1) * MARG_MAX_N]) * z;
+                zc[(i + 1) * ld] = z;
+            }
         }
-        Z[rbest * ld + k] = 1.0;
-        const double sc = 1.0 / sqrt(nrm2);
-        for (int i = 0; i < n; i++) Z[i * ld + k] *= sc;
-        resid = gbest * sc;      // (T - lambda) z = gamma_r e_r with z_r = 1: the residual of the normalised pair is |gamma_r| / |z|
+        __syncthreads();
+        if (live && roleA) {
+            for (int i0 = rbest + 1; i0 < n; i0 += 8) {
+                double zz[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) zz[u] = zc[min(i0 + u, n - 1) * ld];
+#pragma unroll
+                for (int u = 0; u < 8; u++) if (i0 + u < n) nrm2 += zz[u] * zz[u];
+            }
+            zc[rbest * ld] = 1.0;
+            const double sc = 1.0 / sqrt(nrm2);
+            for (int i0 = 0; i0 < n; i0 += 8) {
+                double zz[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) zz[u] = zc[min(i0 + u, n - 1) * ld];
+#pragma unroll
+                for (int u = 0; u < 8; u++) if (i0 + u < n) zc[(i0 + u) * ld] = zz[u] * sc;
+            }
+            resid = gbest * sc;      // (T - lambda) z = gamma_r e_r with z_r = 1: the residual of the normalised pair is |gamma_r| / |z|
+        }
     }
     __syncthreads();
     EMARK(2);
     // ---- (4) modified Gram-Schmidt among RETAINED eigenvectors whose eigenvalues are closer than 1e-10 |T| (the
     // twisted vectors of such neighbours lose orthogonality like eps |T| / gap); wave 0, lanes over the entries
+    if (tid == NT - 64) {      // sum lambda for the diagnostics, off the path of wavefront 0 (see trace above)
+        double s = 0;
+        for (int i0 = 0; i0 < n; i0 += 8) {
+            double a[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) a[u] = lam[min(i0 + u, n - 1)];
+#pragma unroll
+            for (int u = 0; u < 8; u++) if (i0 + u < n) s += a[u];
+        }
+        spare[1] = s;
+    }
+    // The lane owns rows lane and lane + 64 of every column (n <= 80), so a column never leaves the lane that wrote it: column k stays in
+    // two registers through both passes, the next column j is loaded while the butterfly of the current one runs, and the butterfly
+    // exchanges on the VALU (wave_all_xor).  Which k join the cluster of their predecessor comes from one ballot per 64 eigenvalues
+    // instead of an LDS read per k: join(k) = both retained and not further apart than ctol; the cluster starts at the last k that did not join.
     if (wave == 0) {
         const double ctol = 1e-10 * tnorm;
-        int start = -1;
-        for (int k = 0; k < n; k++) {
-            if (!(lam[k] > 1e-8)) continue;
-            if (start < 0 || lam[k] - lam[k - 1] > ctol || !(lam[k - 1] > 1e-8)) { start = k; continue; }
-            for (int pass = 0; pass < 2; pass++)
-                for (int j = start; j < k; j++) {
+        const bool has1 = lane < n, has2 = lane + 64 < n;
+        const int r1 = min(lane, n - 1), r2 = min(lane + 64, n - 1);
+        const double la1 = lam[r1], lb1 = lam[max(r1 - 1, 0)], la2 = lam[r2], lb2 = lam[max(r2 - 1, 0)];
+        const unsigned long long jm1 = __ballot(has1 && lane >= 1 && la1 > 1e-8 && lb1 > 1e-8 && !(la1 - lb1 > ctol));
+        const unsigned long long jm2 = __ballot(has2 && la2 > 1e-8 && lb2 > 1e-8 && !(la2 - lb2 > ctol));
+        int start = 0;
+        for (int w = 0; w < 2; w++) {
+            unsigned long long jm = w ? jm2 : jm1;
+            while (jm) {
+                const int k = 64 * w + __ffsll((long long)jm) - 1;
+                jm &= jm - 1;
+                const int kp = k - 1;      // (k >= 1: eigenvalue 0 never joins)
+                if (!(((kp < 64 ? jm1 >> kp : jm2 >> (kp - 64)) & 1ull))) start = kp;
+                lds_d *zk = Z + k;
+                double k1 = zk[r1 * ld], k2 = zk[r2 * ld];
+                int j = start;
+                double n1 = Z[r1 * ld + j], n2 = Z[r2 * ld + j];
+                for (int t = 2 * (k - start); t > 0; t--) {      // two passes over the columns start .. k - 1
+                    const double a1 = n1, a2 = n2;
+                    j = (j + 1 == k) ? start : j + 1;
+                    n1 = Z[r1 * ld + j]; n2 = Z[r2 * ld + j];
                     double dot = 0;
-                    for (int r = lane; r < n; r += 64) dot += Z[r * ld + j] * Z[r * ld + k];
-                    for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
-                    for (int r = lane; r < n; r += 64) Z[r * ld + k] -= dot * Z[r * ld + j];
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    if (has1) dot += a1 * k1;
+                    if (has2) dot += a2 * k2;
+                    dot = wave_all_xor(dot, OpAdd());
+                    if (has1) k1 -= dot * a1;
+                    if (has2) k2 -= dot * a2;
                 }
-            double nn = 0;
-            for (int r = lane; r < n; r += 64) { const double t = Z[r * ld + k]; nn += t * t; }
-            for (int o = 32; o > 0; o >>= 1) nn += __shfl_xor(nn, o);
-            const double sc = 1.0 / sqrt(nn);
-            for (int r = lane; r < n; r += 64) Z[r * ld + k] *= sc;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                double nn = 0;
+                if (has1) nn += k1 * k1;
+                if (has2) nn += k2 * k2;
+                nn = wave_all_xor(nn, OpAdd());
+                const double sc = 1.0 / sqrt(nn);
+                if (has1) zk[r1 * ld] = k1 * sc;
+                if (has2) zk[r2 * ld] = k2 * sc;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            }
         }
     }
     __syncthreads();
@@ -823,7 +984,7 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag
     {
         int c0 = 0;
         if (!old_search) { while (c0 < n && !(lam[c0] > 1e-8)) c0++; }
-        if (!(flags & 2)) eig_backtransform_wy<NT>(Hq, Z, tauv, vbuf, n, ld, tid, c0);      // vbuf .. xnb: 480 doubles, all dead by now
+        if (!(flags & 2)) eig_backtransform_wy<NT>(Hq, Z, tauv, vbuf, n, ld, tid, c0);      // tbuf = the first 256 doubles of vbuf .. sm + 705, dead by now (sm + 706, 707 are not: trace and sum lambda, read below)
         else if (NT >= 512 || n - c0 <= 16 * NW) eig_backtransform<4>(Hq, Z, tauv, n, ld, tid, c0);
         else eig_backtransform<3>(Hq, Z, tauv, n, ld, tid, c0);
     }
@@ -834,27 +995,46 @@ __device__ __noinline__ __attribute__((disable_tail_calls)) bool sym_eig_tridiag
     double dev = 0;
     {
         lds_d *u1 = vbuf, *u2 = pbuf;          // n-vectors (n <= 80)
+        // the retained columns as a bit mask (one ballot per 64 eigenvalues) instead of a read of lam[k] per k, and the loads of both loops
+        // eight at a time; the sums take their terms in the order of the plain loops
+        const unsigned long long rm1 = __ballot(lane < n && lam[min(lane, n - 1)] > 1e-8), rm2 = __ballot(lane + 64 < n && lam[min(lane + 64, n - 1)] > 1e-8);
         if (tid < n) {
             double a1 = 0, a2 = 0;
-            for (int k = 0; k < n; k++) if (lam[k] > 1e-8) { const double zz = Z[tid * ld + k]; a1 += zz; a2 += (k & 1) ? -zz : zz; }
+            const lds_d *zr = Z + tid * ld;
+            for (int k0 = 0; k0 < n; k0 += 8) {
+                const unsigned bits = (unsigned)((k0 < 64 ? rm1 >> k0 : rm2 >> (k0 - 64)) & 0xffull);
+                if (!bits) continue;
+                double zz[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) zz[u] = zr[min(k0 + u, n - 1)];
+#pragma unroll
+                for (int u = 0; u < 8; u++) if ((bits >> u) & 1u) { a1 += zz[u]; a2 += ((k0 + u) & 1) ? -zz[u] : zz[u]; }
+            }
             u1[tid] = a1; u2[tid] = a2;
         }
         __syncthreads();
         if (tid < n && lam[tid] > 1e-8) {
             double t1 = 0, t2 = 0;
-            for (int r2 = 0; r2 < n; r2++) { const double zz = Z[r2 * ld + tid]; t1 += zz * u1[r2]; t2 += zz * u2[r2]; }
+            const lds_d *zc = Z + tid;
+            for (int r0 = 0; r0 < n; r0 += 8) {
+                double zz[8], w1[8], w2[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) { const int r2 = min(r0 + u, n - 1); zz[u] = zc[r2 * ld]; w1[u] = u1[r2]; w2[u] = u2[r2]; }
+#pragma unroll
+                for (int u = 0; u < 8; u++) if (r0 + u < n) { t1 += zz[u] * w1[u]; t2 += zz[u] * w2[u]; }
+            }
             dev = fmax(fabs(t1 - 1.0), fabs(t2 - ((tid & 1) ? -1.0 : 1.0)));
         }
     }
-    for (int o = 32; o > 0; o >>= 1) { dev = fmax(dev, __shfl_xor(dev, o)); resid = fmax(resid, __shfl_xor(resid, o)); }
+    dev = wave_all_xor(dev, OpMax()); resid = wave_all_xor(resid, OpMax());      // (both non-negative: fmax commutes bit for bit)
     __syncthreads();
     if (lane == 0) { red[wave] = dev; red[8 + wave] = resid; }
     __syncthreads();
     dev = 0; resid = 0;
 #pragma unroll
     for (int w = 0; w < NW; w++) { dev = fmax(dev, red[w]); resid = fmax(resid, red[8 + w]); }
-    double sl = 0;
-    for (int i = 0; i < n; i++) sl += lam[i];
+    double sl = 0, trace = 0;
+    if (old_search || (tid == 0 && dbg)) { trace = spare[0]; sl = spare[1]; }
     __syncthreads();
     EMARK(5);
     if (tid == 0 && dbg) { dbg[0] = dev; dbg[1] = sl; dbg[2] = trace; dbg[3] = tnorm; dbg[4] = lam[0]; dbg[5] = lam[n - 1]; }
@@ -1688,7 +1868,7 @@ __global__ void __launch_bounds__(MARG_NT) __attribute__((disable_tail_calls)) _
         // over the diagonalised A' at the end: the LDS holds one n x n matrix)
         int sweeps2 = 0;
         {
-            const bool ok = sym_eig_tridiag<MARG_NT>(As, R2, sm, rot, n, ldn, tid, out + MARG_DIAG_EIG_CHECK, Aarg.eig_flags);    // rot: 160 doubles >= n eigenvalues
+            const bool ok = sym_eig_tridiag<MARG_NT>(As, R2, sm, rot, n, ldn, tid, out + MARG_DIAG_EIG_CHECK, Aarg.eig_flags, scr + MARG_SCR_V);    // rot: 160 doubles >= n eigenvalues
             if (ok) {
                 if (tid < n) lam[tid] = rot[tid];
             } else {
