@@ -1352,7 +1352,9 @@ __device__ __forceinline__ double readlane_f64(double v, int srclane) {
 // Cholesky of one 16x16 diagonal tile by ONE wavefront, one matrix row per lane held in registers
 // (lane & 15 = row; the 16-lane groups 0, 2, 3 compute redundantly, so there is no divergence).  The pivot and the
 // pivot column are broadcast with v_readlane (SGPR operands of the FMAs): nothing on the pivot chain touches LDS.
-// Only the first cmax columns are pivots (the rest: rhs row / padding).
+// Only the first cmax columns are pivots (the rest: rhs row / padding).  This loop, with its exit test per pivot, runs the PARTIAL last tile of
+// a window; a tile whose 16 columns are all pivots runs diag_tile_wave_full below (same operations on the same operands, a third of the
+// instructions: profiles/chol_pivot_chain.txt).
 // Group 1 (lanes 16..31) carries the rows of the IDENTITY through the same column operations (x <- x L^-T, the trick of the chain's T
 // step): they end as the rows of L^-T, whose strictly upper part goes to the unused upper triangle of the tile (its diagonal is 1 / l_kk =
 // invd) -- for nothing on the pivot chain -- and turns the panel solve below the tile into a product on the matrix cores.
@@ -1373,7 +1375,8 @@ __device__ __forceinline__ bool diag_tile_wave(lds_d *TK, int cmax, lds_d *invd,
                 sqrt_rsqrt(d, l, y);
                 const double lk = (r == k && !idrow) ? l : t[k] * y;
                 t[k] = lk;
-                if (k + 1 < 16) {       // next pivot first: its rsqrt chain overlaps the rest of this column's updates
+                if (k + 1 < 16) {       // column k + 1 first: the next pivot waits for it alone.  (No overlap comes of it here: the pivot's exit test
+                                        // ends the basic block, and the next v_rsq_f64 stands behind all of this column's updates in the code object.)
                     t[k + 1] -= lk * readlane_f64(lk, k + 1);
                     d = readlane_f64(t[k + 1], k + 1);
                 }
@@ -1388,6 +1391,103 @@ __device__ __forceinline__ bool diag_tile_wave(lds_d *TK, int cmax, lds_d *invd,
         for (int c = 0; c < 16; c++) if (idrow ? (c > r) : (c <= r)) TK[sw(r, c)] = t[c];
     }
     return ok;
+}
+
+// acc -= (lane N of src's own 16-lane row) * mul as ONE instruction: row_newbcast is the one DPP control the 64-bit operations of gfx950 take,
+// and it is the broadcast v_readlane performs inside an aligned 16-lane group (two v_readlane and a v_fma_f64 otherwise).  fma(b, -a, c) and
+// fma(-a, b, c) are the same bits.  A VALU result needs two wait states before a DPP operand reads it and the compiler's hazard recogniser does
+// not look into inline assembly: every statement starts with its own s_nop 1.  Every lane of the row must be active.
+template <int N>
+__device__ __forceinline__ void fnma_row_bcast(double &acc, double src, double mul) {
+    asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, -%2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(mul), "n"(N));
+}
+// the trailing columns K + 2 .. 15 of one pivot: t[c] -= lk * (lane c of m's row), one wait for all of them
+#define TCV_TB_F(N) "v_fmac_f64_dpp %[t" #N "], %[m], -%[a] row_newbcast:" #N " row_mask:0xf bank_mask:0xf\n\t"
+#define TCV_TB_O(N) [t##N] "+v"(t[N])
+#define TCV_TB_F15 TCV_TB_F(15)
+#define TCV_TB_F14 TCV_TB_F(14) TCV_TB_F15
+#define TCV_TB_F13 TCV_TB_F(13) TCV_TB_F14
+#define TCV_TB_F12 TCV_TB_F(12) TCV_TB_F13
+#define TCV_TB_F11 TCV_TB_F(11) TCV_TB_F12
+#define TCV_TB_F10 TCV_TB_F(10) TCV_TB_F11
+#define TCV_TB_F9 TCV_TB_F(9) TCV_TB_F10
+#define TCV_TB_F8 TCV_TB_F(8) TCV_TB_F9
+#define TCV_TB_F7 TCV_TB_F(7) TCV_TB_F8
+#define TCV_TB_F6 TCV_TB_F(6) TCV_TB_F7
+#define TCV_TB_F5 TCV_TB_F(5) TCV_TB_F6
+#define TCV_TB_F4 TCV_TB_F(4) TCV_TB_F5
+#define TCV_TB_F3 TCV_TB_F(3) TCV_TB_F4
+#define TCV_TB_F2 TCV_TB_F(2) TCV_TB_F3
+#define TCV_TB_O15 TCV_TB_O(15)
+#define TCV_TB_O14 TCV_TB_O(14), TCV_TB_O15
+#define TCV_TB_O13 TCV_TB_O(13), TCV_TB_O14
+#define TCV_TB_O12 TCV_TB_O(12), TCV_TB_O13
+#define TCV_TB_O11 TCV_TB_O(11), TCV_TB_O12
+#define TCV_TB_O10 TCV_TB_O(10), TCV_TB_O11
+#define TCV_TB_O9 TCV_TB_O(9), TCV_TB_O10
+#define TCV_TB_O8 TCV_TB_O(8), TCV_TB_O9
+#define TCV_TB_O7 TCV_TB_O(7), TCV_TB_O8
+#define TCV_TB_O6 TCV_TB_O(6), TCV_TB_O7
+#define TCV_TB_O5 TCV_TB_O(5), TCV_TB_O6
+#define TCV_TB_O4 TCV_TB_O(4), TCV_TB_O5
+#define TCV_TB_O3 TCV_TB_O(3), TCV_TB_O4
+#define TCV_TB_O2 TCV_TB_O(2), TCV_TB_O3
+#define TCV_TB_CASE(K, C0) if constexpr (K0 == K) asm("s_nop 1\n\t" TCV_TB_F##C0 : TCV_TB_O##C0 : [m] "v"(m), [a] "v"(a));
+template <int K0>
+__device__ __forceinline__ void trail_row_bcast(double (&t)[16], double m, double a) {
+    TCV_TB_CASE(0, 2) TCV_TB_CASE(1, 3) TCV_TB_CASE(2, 4) TCV_TB_CASE(3, 5) TCV_TB_CASE(4, 6) TCV_TB_CASE(5, 7) TCV_TB_CASE(6, 8)
+    TCV_TB_CASE(7, 9) TCV_TB_CASE(8, 10) TCV_TB_CASE(9, 11) TCV_TB_CASE(10, 12) TCV_TB_CASE(11, 13) TCV_TB_CASE(12, 14) TCV_TB_CASE(13, 15)
+}
+#undef TCV_TB_CASE
+
+// One pivot of a FULL tile (all 16 columns are pivots): no branch and no change of the exec mask.  The pivot test is OR-ed into `bad` off the
+// chain (after a bad pivot the rest of the tile is garbage, NaN included: the caller gives the factorisation up and nothing reads the tiles or
+// invd before the next linearisation rewrites them).  In the code object the next pivot's v_rsq_f64 stands in front of this pivot's trailing
+// FMAs, which cover its latency.  d, l and y are uniform over the wavefront -- the identity rows scale by y too -- so the
+// pivot and column K + 1, which the next pivot waits for, keep v_readlane; the other trailing columns take their multiplier L[c][K] by row
+// broadcast from m, the matrix rows' column in every 16-lane row (the identity rows of group 1 need group 0's: v_permlane16_swap of the value
+// with itself leaves the even rows' lanes in both rows of a pair, and the groups 2, 3 hold the matrix too).  Lane K keeps y_K for invd.
+template <int K>
+__device__ __forceinline__ void diag_pivot_full(double (&t)[16], double &d, double &yk, bool &bad, int r, bool idrow) {
+    bad |= !(d > 0.0) | !(d < 1e300);
+    double l, y;
+    sqrt_rsqrt(d, l, y);
+    const bool dg = (r == K) && !idrow;
+    const double lk = dg ? l : t[K] * y;
+    t[K] = lk;
+    if constexpr (K + 1 < 16) {
+        t[K + 1] -= lk * readlane_f64(lk, K + 1);
+        d = readlane_f64(t[K + 1], K + 1);
+    }
+    if constexpr (K + 2 < 16) {
+        const unsigned lo = (unsigned)__double2loint(lk), hi = (unsigned)__double2hiint(lk);
+        const double m = lane_pair(__builtin_amdgcn_permlane16_swap(lo, lo, false, false)[0], __builtin_amdgcn_permlane16_swap(hi, hi, false, false)[0]);
+        trail_row_bcast<K>(t, m, lk);
+    }
+    yk = dg ? y : yk;
+}
+__device__ __forceinline__ bool diag_tile_wave_full(lds_d *TK, lds_d *invd, int lane) {
+    const int r = lane & 15;
+    const bool idrow = (lane >> 4) == 1;
+    double t[16];
+#pragma unroll
+    for (int c = 0; c < 16; c++) { const double tv = TK[sw(r, c)]; t[c] = idrow ? ((r == c) ? 1.0 : 0.0) : tv; }
+    bool bad = false;
+    double yk = 0.0;
+    double d = readlane_f64(t[0], 0);
+#define TCV_DP(K) diag_pivot_full<K>(t, d, yk, bad, r, idrow);
+    TCV_DP(0) TCV_DP(1) TCV_DP(2) TCV_DP(3) TCV_DP(4) TCV_DP(5) TCV_DP(6) TCV_DP(7) TCV_DP(8) TCV_DP(9) TCV_DP(10) TCV_DP(11) TCV_DP(12) TCV_DP(13) TCV_DP(14) TCV_DP(15)
+#undef TCV_DP
+    if (lane < 16) invd[lane] = yk;      // the addresses and values of the loop's per-pivot stores, once
+    if (lane < 32) {
+#pragma unroll
+        for (int c = 0; c < 16; c++) if (idrow ? (c > r) : (c <= r)) TK[sw(r, c)] = t[c];
+    }
+    return !bad;
+}
+__device__ __forceinline__ bool diag_tile(lds_d *TK, int cmax, lds_d *invd, int lane) {
+    if (cmax == 16) return diag_tile_wave_full(TK, invd, lane);
+    return diag_tile_wave(TK, cmax, invd, lane);
 }
 
 // panel below a factored diagonal tile on the matrix cores: X L_KK' = A_IK, with the L_KK^-T the diagonal factorisation left behind in the
@@ -1486,7 +1586,7 @@ __device__ __noinline__ bool chol_tiles(TCV_CTX_PARAMS, int nt, int nc) {
     lds_d *tiles = C.tiles;
     if (wave == 0) {
         const int cmax0 = min(16, nc);
-        if (!diag_tile_wave(tiles + tbase(0, 0), cmax0, C.invdiag, lane) && lane == 0) *C.flag = 1;
+        if (!diag_tile(tiles + tbase(0, 0), cmax0, C.invdiag, lane) && lane == 0) *C.flag = 1;
     }
     __syncthreads();
     TCV_MARK(C, PH_CHOL_DIAG);
@@ -1532,7 +1632,7 @@ __device__ __noinline__ bool chol_tiles(TCV_CTX_PARAMS, int nt, int nc) {
                 update_tile<MFMA>(tiles, K + 1, K + 1, K, lane);
                 if (cnext > 0) {
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    if (!diag_tile_wave(tiles + tbase(K + 1, K + 1), cnext, C.invdiag + 16 * (K + 1), lane) && lane == 0) *C.flag = 1;
+                    if (!diag_tile(tiles + tbase(K + 1, K + 1), cnext, C.invdiag + 16 * (K + 1), lane) && lane == 0) *C.flag = 1;
                 }
             }
             // the other tiles: the first DIAG_COST * (NW - 1) go round-robin to waves 1.., the rest to all waves; every
@@ -1562,12 +1662,12 @@ __device__ __noinline__ bool chol_tiles(TCV_CTX_PARAMS, int nt, int nc) {
 
 // ---- back substitution L^T y = z (z = the factored rhs row) -----------------------------------------
 // Column sweep: thread c keeps t_c = z_c - sum_{r > tile} L[r][c] y_r in a register.  Per tile row K (descending): the
-// 16 lanes that own its columns solve the 16 x 16 triangular system among themselves (v_readlane broadcasts), publish
+// 16 lanes that own its columns solve the 16 x 16 triangular system among themselves (DPP row broadcasts), publish
 // y_K, and after ONE barrier every thread folds tile row K into its own t_c.
 template <int NT>
 __device__ __noinline__ void back_subst(TCV_CTX_PARAMS, int nc) {
     Ctx<NT> C = ctx_from_args<NT>(TCV_CTX_FORWARD);
-    const int tid = C.tid, lane = tid & 63;
+    const int tid = C.tid;
     lds_d *tiles = C.tiles, *y = C.ycam;
     const int c = tid, Kc = c >> 4, cc = c & 15;
     double t = tiles[tix(nc, min(c, nc - 1))];
@@ -1576,19 +1676,18 @@ __device__ __noinline__ void back_subst(TCV_CTX_PARAMS, int nc) {
         const int cmax = min(16, nc - 16 * K);
         if (Kc == K) {     // the 16 lanes holding columns 16K .. 16K+15 (one aligned 16-lane group of one wave)
             const lds_d *TK = tiles + tbase(K, K);
-            const int g0 = lane & ~15;
             double lrow[16];
 #pragma unroll
             for (int j = 0; j < 16; j++) { const double tv = TK[sw(j, cc)]; lrow[j] = (cc <= j) ? tv : 0.0; }      // L[j][cc]
             const double inv = C.invdiag[c < nc ? c : 0];
-#pragma unroll
-            for (int j = 15; j >= 0; j--) {
-                if (j < cmax) {
-                    const double yj = readlane_f64(t * inv, g0 + j);     // lane j of the group: its t is final
-                    if (cc == j) t = yj;
-                    else if (cc < j) t -= lrow[j] * yj;
-                }
-            }
+            // y_j = t * inv of lane j (its t is final) reaches the group by row broadcast inside the FMA: a multiply and one v_fmac_f64_dpp per step.
+            // Lane j keeps its product off the chain; what the FMA leaves in the lanes cc >= j is never read again (lrow[j] is zero above the
+            // diagonal, and their y is kept already).
+            double yk = t;
+#define TCV_BS(J) if (J < cmax) { const double p = t * inv; yk = (cc == J) ? p : yk; fnma_row_bcast<J>(t, p, lrow[J]); }
+            TCV_BS(15) TCV_BS(14) TCV_BS(13) TCV_BS(12) TCV_BS(11) TCV_BS(10) TCV_BS(9) TCV_BS(8) TCV_BS(7) TCV_BS(6) TCV_BS(5) TCV_BS(4) TCV_BS(3) TCV_BS(2) TCV_BS(1) TCV_BS(0)
+#undef TCV_BS
+            t = yk;
             if (cc < cmax) y[c] = t;
         }
         __syncthreads();
