@@ -3,6 +3,7 @@
 // replaced by `tcvshim::`.
 //
 //   g++ -std=c++14 -Iinclude examples/estimator_shim_classes.cpp -Ltc-viml_amd -ltcv_hip -Wl,-rpath,$PWD/tc-viml_amd -o shim2
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <unordered_map>
@@ -86,6 +87,33 @@ int main() {
             options.max_num_iterations = 4;
             Solve(options, &problem, &summary);
             std::printf("prior-only window: cost %.6g -> %.6g\n", summary.initial_cost, summary.final_cost);
+        }
+        // ceres::Covariance (include/tcv_covariance.h): how well the IMU factor alone ties the newest pose to a fixed older frame.  (The
+        // window above has no prior and no lines: nothing fixes its gauge, and Compute would report it rank deficient.)
+        {
+            Problem problem;
+            problem.SetGravity(G);
+            for (int i = 0; i < 2; i++) {
+                problem.AddParameterBlock(para_Pose[i], 7, new PoseLocalParameterization());
+                problem.AddParameterBlock(para_SpeedBias[i], 9);
+            }
+            problem.SetParameterBlockConstant(para_Pose[0]);
+            problem.SetParameterBlockConstant(para_SpeedBias[0]);
+            problem.AddResidualBlock(new IMUFactor(pre), nullptr, para_Pose[0], para_SpeedBias[0], para_Pose[1], para_SpeedBias[1]);
+            problem.SetFrames({para_Pose[0], para_Pose[1]}, {para_SpeedBias[0], para_SpeedBias[1]});
+            Covariance covariance;
+            if (!covariance.Compute({{para_Pose[1], para_Pose[1]}, {para_Pose[1], para_SpeedBias[1]}}, &problem)) throw std::runtime_error("Covariance::Compute: rank deficient");
+            double c6[36], c7[49], cross[6 * 9], cross_t[9 * 6];
+            covariance.GetCovarianceBlockInTangentSpace(para_Pose[1], para_Pose[1], c6);
+            covariance.GetCovarianceBlock(para_Pose[1], para_Pose[1], c7);
+            covariance.GetCovarianceBlockInTangentSpace(para_Pose[1], para_SpeedBias[1], cross);
+            covariance.GetCovarianceBlockInTangentSpace(para_SpeedBias[1], para_Pose[1], cross_t);
+            bool zero_last = true, symmetric = true;
+            for (int i = 0; i < 7; i++) zero_last = zero_last && c7[6 * 7 + i] == 0.0 && c7[i * 7 + 6] == 0.0;
+            for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) symmetric = symmetric && c6[6 * i + j] == c6[6 * j + i] && c7[7 * i + j] == c6[6 * i + j];
+            for (int i = 0; i < 6; i++) for (int j = 0; j < 9; j++) symmetric = symmetric && cross[9 * i + j] == cross_t[6 * j + i];
+            std::printf("covariance of the newest pose: sigma_p %.6g %.6g %.6g sigma_theta %.6g %.6g %.6g; ambient 7 x 7 last row and column zero: %d; symmetric: %d\n",
+                        std::sqrt(c6[0]), std::sqrt(c6[7]), std::sqrt(c6[14]), std::sqrt(c6[21]), std::sqrt(c6[28]), std::sqrt(c6[35]), (int)zero_last, (int)symmetric);
         }
         delete marginalization_info;
     } catch (const std::exception &e) {

@@ -6,6 +6,7 @@
 //     IMUFactor, ProjectionFactor, LineProjectionFactor, MarginalizationFactor        ->  tcvshim::... (value holders, no Evaluate)
 //     PoseLocalParameterization                                                       ->  tcvshim::PoseLocalParameterization (a tag)
 //     MarginalizationInfo, ResidualBlockInfo                                          ->  tcvshim::...
+//     ceres::Covariance (Compute, GetCovarianceBlock[InTangentSpace])                 ->  tcvshim::Covariance (include/tcv_covariance.h)
 //
 // The factor set is closed (the solver's kernels implement exactly these factors), so `AddResidualBlock` is overloaded per factor
 // type instead of taking a generic CostFunction*.  Vector / matrix arguments are accepted from anything with `.data()` (Eigen
@@ -20,9 +21,11 @@
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "tcv.h"
+#include "tcv_covariance.h"
 
 namespace tcvshim {
 
@@ -110,6 +113,7 @@ class Problem {                                                           // cer
     void AddResidualBlock(ProjectionFactor *f, LossFunction *loss, double *pose_i, double *pose_j, double *ex, double *inv_depth) {
         detail::check(tcv_problem_add_projection_factor(p_, f->pts_i, f->pts_j, ProjectionFactor::sqrt_info(), loss ? loss->scale() : 0.0, pose_i, pose_j, ex,
                                                         inv_depth), "AddResidualBlock(ProjectionFactor)");
+        ex_ = ex;
         own(owned_cost_, f); if (loss) own(owned_loss_, loss);
     }
     void AddResidualBlock(ProjectionTdFactor *f, LossFunction *loss, double *pose_i, double *pose_j, double *ex, double *inv_depth, double *td) {
@@ -117,6 +121,7 @@ class Problem {                                                           // cer
         detail::check(tcv_problem_add_projection_td_factor(p_, f->pts_i, f->pts_j, f->velocity_i, f->velocity_j, f->td_i, f->td_j, f->row_i, f->row_j,
                                                            ProjectionFactor::sqrt_info(), loss ? loss->scale() : 0.0, pose_i, pose_j, ex, inv_depth, td),
                       "AddResidualBlock(ProjectionTdFactor)");
+        ex_ = ex; td_ = td;
         own(owned_cost_, f); if (loss) own(owned_loss_, loss);
     }
     void AddResidualBlock(LineProjectionFactor *f, LossFunction *loss, double *pose) {
@@ -139,11 +144,27 @@ class Problem {                                                           // cer
         if (rc != TCV_OK && rc != TCV_ERR_NUMERIC) detail::check(rc, "tcv_problem_evaluate");
         return rc == TCV_OK;
     }
+    // The frame table (tcv_problem_set_frames): para_Pose[i] / para_SpeedBias[i], oldest frame first.  tcvshim::Covariance names blocks by
+    // what they are, and the gauge fix needs it too; ceres::Problem has no counterpart.
+    void SetFrames(const std::vector<double *> &pose, const std::vector<double *> &speedbias) {
+        detail::check(tcv_problem_set_frames(p_, (int)pose.size(), pose.data(), speedbias.empty() ? nullptr : speedbias.data()), "tcv_problem_set_frames");
+        frame_pose_ = pose; frame_sb_ = speedbias;
+    }
+    // (kind, index, ambient size) of a camera-side parameter block for tcv_covariance_block; false: not one the covariance knows
+    bool CovarianceRole(const double *a, int *kind, int *index, int *ambient) const {
+        for (size_t i = 0; i < frame_pose_.size(); i++) if (frame_pose_[i] == a) { *kind = TCV_COV_POSE; *index = (int)i; *ambient = 7; return true; }
+        for (size_t i = 0; i < frame_sb_.size(); i++) if (frame_sb_[i] == a) { *kind = TCV_COV_SPEED_BIAS; *index = (int)i; *ambient = 9; return true; }
+        if (a && a == ex_) { *kind = TCV_COV_EXTRINSIC; *index = 0; *ambient = 7; return true; }
+        if (a && a == td_) { *kind = TCV_COV_TD; *index = 0; *ambient = 1; return true; }
+        return false;
+    }
     tcv_problem *handle() { return p_; }
 
   private:
     template <class T, class U> static void own(std::vector<T *> &v, U *x) { T *b = x; for (auto *y : v) if (y == b) return; v.push_back(b); }
     tcv_problem *p_ = nullptr;
+    std::vector<double *> frame_pose_, frame_sb_;
+    const double *ex_ = nullptr, *td_ = nullptr;
     std::vector<CostFunction *> owned_cost_;
     std::vector<LocalParameterization *> owned_param_;
     std::vector<LossFunction *> owned_loss_;
@@ -181,6 +202,75 @@ inline void Solve(const Solver::Options &o, Problem *problem, Solver::Summary *s
         for (int i = 0; i < s.num_iterations && i < TCV_MAX_TRACE; i++) summary->iterations.push_back({s.cost[i]});
     }
 }
+
+// ceres::Covariance on the device (tcv_problem_compute_covariance): the marginal covariance of camera-side parameter blocks at their
+// current values.  Blocks are named by address like in Ceres; the problem must carry its frame table (Problem::SetFrames).  Compute
+// returns false for a rank-deficient problem (Ceres: "Covariance::Compute failed"), the getters then return false too.
+class Covariance {
+  public:
+    struct Options { bool apply_loss_function = true; double min_relative_pivot = TCV_COVARIANCE_MIN_RELATIVE_PIVOT; };
+    Covariance() {}
+    explicit Covariance(const Options &o) : options_(o) {}
+    bool Compute(const std::vector<std::pair<const double *, const double *>> &covariance_blocks, Problem *problem) {
+        const size_t n = covariance_blocks.size();
+        entries_.assign(n, Entry());
+        std::vector<tcv_covariance_block> rq(n);
+        std::vector<double *> out(n);
+        for (size_t k = 0; k < n; k++) {
+            Entry &e = entries_[k];
+            e.a = covariance_blocks[k].first; e.b = covariance_blocks[k].second;
+            if (!problem->CovarianceRole(e.a, &rq[k].kind_i, &rq[k].index_i, &e.ga) || !problem->CovarianceRole(e.b, &rq[k].kind_j, &rq[k].index_j, &e.gb))
+                throw std::runtime_error("tcvshim::Covariance: not a camera-side parameter block of the problem's frame table (Problem::SetFrames)");
+            e.la = e.ga == 7 ? 6 : e.ga; e.lb = e.gb == 7 ? 6 : e.gb;
+            e.v.assign((size_t)e.la * e.lb, 0.0);
+            out[k] = e.v.data();
+        }
+        tcv_covariance_options o;
+        tcv_covariance_options_default(&o);
+        o.apply_loss_function = options_.apply_loss_function ? 1 : 0;
+        o.min_relative_pivot = options_.min_relative_pivot;
+        int status = 0;
+        detail::check(tcv_problem_compute_covariance(problem->handle(), &o, rq.data(), (int)n, out.data(), &status), "tcv_problem_compute_covariance");
+        ok_ = status == TCV_COVARIANCE_OK;
+        return ok_;
+    }
+    // row-major local size x local size (a pose: 6 x 6)
+    bool GetCovarianceBlockInTangentSpace(const double *a, const double *b, double *out) const {
+        bool transposed = false;
+        const Entry *e = find(a, b, &transposed);
+        if (!e || !ok_) return false;
+        for (int i = 0; i < e->la; i++) for (int j = 0; j < e->lb; j++) {
+            if (transposed) out[j * e->la + i] = e->v[(size_t)i * e->lb + j];
+            else out[i * e->lb + j] = e->v[(size_t)i * e->lb + j];
+        }
+        return true;
+    }
+    // row-major ambient size x ambient size: lifted through PoseLocalParameterization::ComputeJacobian (identity on the top six rows, a zero
+    // last row), so a pose block comes back 7 wide with a zero last row / column
+    bool GetCovarianceBlock(const double *a, const double *b, double *out) const {
+        bool transposed = false;
+        const Entry *e = find(a, b, &transposed);
+        if (!e || !ok_) return false;
+        const int ra = transposed ? e->gb : e->ga, rb = transposed ? e->ga : e->gb;
+        for (int i = 0; i < ra * rb; i++) out[i] = 0.0;
+        for (int i = 0; i < e->la; i++) for (int j = 0; j < e->lb; j++) {
+            if (transposed) out[j * rb + i] = e->v[(size_t)i * e->lb + j];
+            else out[i * rb + j] = e->v[(size_t)i * e->lb + j];
+        }
+        return true;
+    }
+
+  private:
+    struct Entry { const double *a = nullptr, *b = nullptr; int ga = 0, gb = 0, la = 0, lb = 0; std::vector<double> v; };
+    const Entry *find(const double *a, const double *b, bool *transposed) const {
+        for (auto &e : entries_) if (e.a == a && e.b == b) { *transposed = false; return &e; }
+        for (auto &e : entries_) if (e.a == b && e.b == a) { *transposed = true; return &e; }
+        return nullptr;
+    }
+    Options options_;
+    std::vector<Entry> entries_;
+    bool ok_ = false;
+};
 
 struct ResidualBlockInfo {                                                 // marginalization_factor.h:15-35
     ResidualBlockInfo(CostFunction *c, LossFunction *l, std::vector<double *> blocks, std::vector<int> drop)

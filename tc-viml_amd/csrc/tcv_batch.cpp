@@ -86,6 +86,7 @@ static void batch_free(tcv_batch *b) {
     if (b->ev1) hipEventDestroy(b->ev1);
     if (b->marg_free) b->marg_free(b);
     tcv_eval_free(b);
+    if (b->cov_free) b->cov_free(b);
     delete b;
 }
 

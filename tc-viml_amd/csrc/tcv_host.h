@@ -222,6 +222,9 @@ struct tcv_batch {
     void (*marg_free)(tcv_batch *) = nullptr;
     // evaluation (tcv_batch_evaluate)
     void *eval = nullptr;                 // tcv_eval_host.cpp EvalState: owner lists, staging and output buffers, made at the first evaluation
+    // marginal covariance (include/tcv_covariance.h)
+    void *cov = nullptr;                  // tcv_cov_host.cpp CovState: owner lists, work and result buffers, made at the first computation
+    void (*cov_free)(tcv_batch *) = nullptr;
     // relocalisation (tcv_relo.hip): the windows whose problem carries tcv_problem_set_relocalization; n_relo = 0: nothing below is used
     int n_relo = 0;
     std::vector<int> relo_win;            // window of every table entry
