@@ -115,6 +115,30 @@ int main() {
             std::printf("covariance of the newest pose: sigma_p %.6g %.6g %.6g sigma_theta %.6g %.6g %.6g; ambient 7 x 7 last row and column zero: %d; symmetric: %d\n",
                         std::sqrt(c6[0]), std::sqrt(c6[7]), std::sqrt(c6[14]), std::sqrt(c6[21]), std::sqrt(c6[28]), std::sqrt(c6[35]), (int)zero_last, (int)symmetric);
         }
+        // ... and of a feature (include/tcv_landmark_covariance.h): the same window with the point factor, the extrinsic held constant
+        {
+            Problem problem;
+            problem.SetGravity(G);
+            for (int i = 0; i < 2; i++) {
+                problem.AddParameterBlock(para_Pose[i], 7, new PoseLocalParameterization());
+                problem.AddParameterBlock(para_SpeedBias[i], 9);
+            }
+            problem.AddParameterBlock(para_Ex_Pose[0], 7, new PoseLocalParameterization());
+            problem.SetParameterBlockConstant(para_Pose[0]);
+            problem.SetParameterBlockConstant(para_SpeedBias[0]);
+            problem.SetParameterBlockConstant(para_Ex_Pose[0]);
+            problem.AddResidualBlock(new IMUFactor(pre), nullptr, para_Pose[0], para_SpeedBias[0], para_Pose[1], para_SpeedBias[1]);
+            problem.AddResidualBlock(new ProjectionFactor(pts_i, pts_j), new CauchyLoss(1.0), para_Pose[0], para_Pose[1], para_Ex_Pose[0], para_Feature[0]);
+            problem.SetFrames({para_Pose[0], para_Pose[1]}, {para_SpeedBias[0], para_SpeedBias[1]});
+            Covariance covariance;
+            if (!covariance.Compute({{para_Feature[0], para_Feature[0]}, {para_Feature[0], para_Pose[1]}}, &problem)) throw std::runtime_error("Covariance::Compute: rank deficient");
+            double var = 0.0, row[6], col7[7];
+            covariance.GetCovarianceBlock(para_Feature[0], para_Feature[0], &var);
+            covariance.GetCovarianceBlockInTangentSpace(para_Feature[0], para_Pose[1], row);
+            covariance.GetCovarianceBlock(para_Pose[1], para_Feature[0], col7);
+            std::printf("variance of the feature's inverse depth: %.6g (sigma %.6g at %.3g); with the newest pose's x: %.6g; ambient 7 x 1 last entry zero: %d\n", var, std::sqrt(var),
+                        para_Feature[0][0], row[0], (int)(col7[6] == 0.0 && col7[0] == row[0]));
+        }
         delete marginalization_info;
     } catch (const std::exception &e) {
         std::printf("error: %s\n", e.what());

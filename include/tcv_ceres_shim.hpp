@@ -26,6 +26,7 @@
 
 #include "tcv.h"
 #include "tcv_covariance.h"
+#include "tcv_landmark_covariance.h"
 
 namespace tcvshim {
 
@@ -113,7 +114,7 @@ class Problem {                                                           // cer
     void AddResidualBlock(ProjectionFactor *f, LossFunction *loss, double *pose_i, double *pose_j, double *ex, double *inv_depth) {
         detail::check(tcv_problem_add_projection_factor(p_, f->pts_i, f->pts_j, ProjectionFactor::sqrt_info(), loss ? loss->scale() : 0.0, pose_i, pose_j, ex,
                                                         inv_depth), "AddResidualBlock(ProjectionFactor)");
-        ex_ = ex;
+        ex_ = ex; feature(inv_depth);
         own(owned_cost_, f); if (loss) own(owned_loss_, loss);
     }
     void AddResidualBlock(ProjectionTdFactor *f, LossFunction *loss, double *pose_i, double *pose_j, double *ex, double *inv_depth, double *td) {
@@ -121,7 +122,7 @@ class Problem {                                                           // cer
         detail::check(tcv_problem_add_projection_td_factor(p_, f->pts_i, f->pts_j, f->velocity_i, f->velocity_j, f->td_i, f->td_j, f->row_i, f->row_j,
                                                            ProjectionFactor::sqrt_info(), loss ? loss->scale() : 0.0, pose_i, pose_j, ex, inv_depth, td),
                       "AddResidualBlock(ProjectionTdFactor)");
-        ex_ = ex; td_ = td;
+        ex_ = ex; td_ = td; feature(inv_depth);
         own(owned_cost_, f); if (loss) own(owned_loss_, loss);
     }
     void AddResidualBlock(LineProjectionFactor *f, LossFunction *loss, double *pose) {
@@ -158,9 +159,13 @@ class Problem {                                                           // cer
         if (a && a == td_) { *kind = TCV_COV_TD; *index = 0; *ambient = 1; return true; }
         return false;
     }
+    // an inverse-depth block: the fourth block of a point factor (include/tcv_landmark_covariance.h)
+    bool IsFeature(const double *a) const { for (auto *f : features_) if (f == a) return true; return false; }
     tcv_problem *handle() { return p_; }
 
   private:
+    void feature(double *a) { if (!IsFeature(a)) features_.push_back(a); }
+    std::vector<double *> features_;
     template <class T, class U> static void own(std::vector<T *> &v, U *x) { T *b = x; for (auto *y : v) if (y == b) return; v.push_back(b); }
     tcv_problem *p_ = nullptr;
     std::vector<double *> frame_pose_, frame_sb_;
@@ -203,9 +208,11 @@ inline void Solve(const Solver::Options &o, Problem *problem, Solver::Summary *s
     }
 }
 
-// ceres::Covariance on the device (tcv_problem_compute_covariance): the marginal covariance of camera-side parameter blocks at their
-// current values.  Blocks are named by address like in Ceres; the problem must carry its frame table (Problem::SetFrames).  Compute
-// returns false for a rank-deficient problem (Ceres: "Covariance::Compute failed"), the getters then return false too.
+// ceres::Covariance on the device (tcv_problem_compute_covariance, tcv_problem_compute_landmark_covariance): the marginal covariance of
+// camera-side parameter blocks and of the features' inverse depths at their current values.  Blocks are named by address like in Ceres;
+// the problem must carry its frame table (Problem::SetFrames).  Pairs (camera block, camera block), (feature, the same feature),
+// (feature, camera block) and (camera block, feature) are served; a pair of two DIFFERENT features throws.  Compute returns false for a
+// rank-deficient problem (Ceres: "Covariance::Compute failed"), the getters then return false too.
 class Covariance {
   public:
     struct Options { bool apply_loss_function = true; double min_relative_pivot = TCV_COVARIANCE_MIN_RELATIVE_PIVOT; };
@@ -214,24 +221,64 @@ class Covariance {
     bool Compute(const std::vector<std::pair<const double *, const double *>> &covariance_blocks, Problem *problem) {
         const size_t n = covariance_blocks.size();
         entries_.assign(n, Entry());
-        std::vector<tcv_covariance_block> rq(n);
-        std::vector<double *> out(n);
+        std::vector<tcv_covariance_block> rq;                 // the camera-side pairs
+        std::vector<double *> out;
+        std::vector<double *> feats;                          // the distinct features of the pairs that name one
+        std::vector<tcv_landmark_cross_block> cross;          // the distinct camera-side blocks of those pairs
+        struct Lm { size_t entry; int feat, cross; };         // cross < 0: the feature's variance
+        std::vector<Lm> lm;
+        const char *not_cam = "tcvshim::Covariance: not a camera-side parameter block of the problem's frame table (Problem::SetFrames)";
         for (size_t k = 0; k < n; k++) {
             Entry &e = entries_[k];
             e.a = covariance_blocks[k].first; e.b = covariance_blocks[k].second;
-            if (!problem->CovarianceRole(e.a, &rq[k].kind_i, &rq[k].index_i, &e.ga) || !problem->CovarianceRole(e.b, &rq[k].kind_j, &rq[k].index_j, &e.gb))
-                throw std::runtime_error("tcvshim::Covariance: not a camera-side parameter block of the problem's frame table (Problem::SetFrames)");
+            const bool fa = problem->IsFeature(e.a), fb = problem->IsFeature(e.b);
+            if (fa || fb) {
+                if (fa && fb && e.a != e.b) throw std::runtime_error("tcvshim::Covariance: the covariance between two different features is not supported");
+                const double *f = fa ? e.a : e.b;
+                size_t fi = 0;
+                while (fi < feats.size() && feats[fi] != f) fi++;
+                if (fi == feats.size()) feats.push_back(const_cast<double *>(f));
+                int ci = -1;
+                e.ga = e.gb = 1;
+                if (!(fa && fb)) {
+                    tcv_landmark_cross_block c;
+                    if (!problem->CovarianceRole(fa ? e.b : e.a, &c.kind, &c.index, fa ? &e.gb : &e.ga)) throw std::runtime_error(not_cam);
+                    for (ci = 0; ci < (int)cross.size() && (cross[ci].kind != c.kind || cross[ci].index != c.index); ci++) {}
+                    if (ci == (int)cross.size()) cross.push_back(c);
+                    if (cross.size() > TCV_LANDMARK_COVARIANCE_MAX_CROSS) throw std::runtime_error("tcvshim::Covariance: more than TCV_LANDMARK_COVARIANCE_MAX_CROSS camera-side blocks paired with features");
+                }
+                lm.push_back({k, (int)fi, ci});
+            } else {
+                tcv_covariance_block r;
+                if (!problem->CovarianceRole(e.a, &r.kind_i, &r.index_i, &e.ga) || !problem->CovarianceRole(e.b, &r.kind_j, &r.index_j, &e.gb)) throw std::runtime_error(not_cam);
+                rq.push_back(r);
+            }
             e.la = e.ga == 7 ? 6 : e.ga; e.lb = e.gb == 7 ? 6 : e.gb;
             e.v.assign((size_t)e.la * e.lb, 0.0);
-            out[k] = e.v.data();
+            if (!fa && !fb) out.push_back(e.v.data());
         }
         tcv_covariance_options o;
         tcv_covariance_options_default(&o);
         o.apply_loss_function = options_.apply_loss_function ? 1 : 0;
         o.min_relative_pivot = options_.min_relative_pivot;
-        int status = 0;
-        detail::check(tcv_problem_compute_covariance(problem->handle(), &o, rq.data(), (int)n, out.data(), &status), "tcv_problem_compute_covariance");
-        ok_ = status == TCV_COVARIANCE_OK;
+        int status = TCV_COVARIANCE_OK, lm_status = TCV_COVARIANCE_OK;
+        if (!rq.empty()) detail::check(tcv_problem_compute_covariance(problem->handle(), &o, rq.data(), (int)rq.size(), out.data(), &status), "tcv_problem_compute_covariance");
+        if (!lm.empty()) {      // one call for every feature against every camera-side block that a pair names
+            const size_t nf = feats.size();
+            std::vector<double> var(nf);
+            std::vector<std::vector<double>> rows(cross.size(), std::vector<double>(nf * 9));
+            std::vector<double *> rp;
+            for (auto &r : rows) rp.push_back(r.data());
+            detail::check(tcv_problem_compute_landmark_covariance(problem->handle(), &o, feats.data(), (int)nf, cross.data(), (int)cross.size(), var.data(), rp.data(), &lm_status),
+                          "tcv_problem_compute_landmark_covariance");
+            for (auto &q : lm) {
+                Entry &e = entries_[q.entry];
+                if (q.cross < 0) { e.v[0] = var[q.feat]; continue; }
+                const size_t w = e.v.size();      // 1 x w or w x 1: the same w numbers
+                for (size_t j = 0; j < w; j++) e.v[j] = rows[q.cross][(size_t)q.feat * w + j];
+            }
+        }
+        ok_ = status == TCV_COVARIANCE_OK && lm_status == TCV_COVARIANCE_OK;
         return ok_;
     }
     // row-major local size x local size (a pose: 6 x 6)

@@ -41,6 +41,17 @@ enum {
 enum { RQ_M = 0, RQ_NREQ = 1, RQ_COL = 2, RQ_REQ = 2 + COV_MAX_DIM };
 inline int cov_rq_stride(int n_req) { return RQ_REQ + 4 * n_req; }
 
+// ---- landmark phase (include/tcv_landmark_covariance.h; tcv_cov.hip phase 7), only in the instantiation the landmark call launches.
+// Slot table, per plan (ints, CovArgs::ltab + ltab_base[plan]), beside the owner lists:
+//   [ lsptr (nland + 1) | slot (3 ints): first tangent index of the block, offset of its h_l slot in the J region, width ]
+//   the slots of landmark l are lsptr[l] .. lsptr[l + 1], in ascending tangent order: the first one is the first non-zero row of w_l
+// The landmarks are walked in chunks of COV_LM_CHUNK, one thread per landmark; y_l = L^-1 w_l of a chunk lives in the workgroup's
+// CovArgs::ylm (COV_MAX_DIM x COV_LM_CHUNK: row k of landmark t at k * COV_LM_CHUNK + t).
+// Results, landmarks in plan order: CovArgs::lm_var + window * lm_lmax: var(lambda_l);  CovArgs::lm_cross + window * lm_lmax * lm_mstride:
+// rows of lm_mstride doubles, row l, entry c = cov(lambda_l, solved column c of the window's request table) -- the host cuts the
+// requested blocks out of the rows
+enum { COV_LM_CHUNK = 256, LT_SLOT = 3 };
+
 // LDS doubles of a workgroup: first the evaluation phase (states | reduction scratch | prior dx | prior residual | sqrt_info workspace, as
 // tcv_eval.h), then -- over the same space -- the packed lower triangle of S, row-major (its diagonal keeps S_kk); behind it the pivot
 // of the current column and diag(L)
@@ -72,6 +83,12 @@ struct CovArgs {
     int nwin, state_stride, rq_stride, n_req;
     int apply_loss, lds_area;
     double min_relative_pivot;
+    // landmark phase (null / 0 in the plain call)
+    const long long *ltab_base;   // per plan: offset of its slot table in `ltab`
+    const int *ltab;
+    double *ylm;                  // per workgroup COV_MAX_DIM x COV_LM_CHUNK
+    double *lm_var, *lm_cross;    // per window lm_lmax / lm_lmax x lm_mstride
+    int lm_lmax, lm_mstride;      // largest landmark count / largest number of solved columns of the batch
 };
 
 }  // namespace tcv

@@ -15,6 +15,11 @@
 //   5. one thread per requested unit column e_p: y_p = L^-1 e_p by forward substitution (L in LDS, y in HBM)
 //   6. the requested entries (S^-1)_pq = y_p . y_q, summed in ascending row order (steps 5 and 6 in twice the working precision too) -- the backward substitution folded into a dot product,
 //      which makes block (i, j) the exact transpose of block (j, i) and every diagonal block exactly symmetric
+//   7. (LM instantiation only: tcv_batch_compute_landmark_covariance) the inverse depths, in chunks of COV_LM_CHUNK landmarks, one
+//      thread per landmark: w_l = h_l / H_ll scattered into tangent order, y_l = L^-1 w_l by forward substitution from the first
+//      non-zero row (L in LDS, y_l in HBM), var = 1 / H_ll + sum_k y_l[k]^2, k ascending; then cov(lambda_l, column p) = -sum_k y_l[k] y_p[k]
+//      for the columns step 5 solved, one thread per entry.  Every sum in twice the working precision; the dot products of the substitution
+//      and of the cross entries as four interleaved partial sums (dd_dot4 below): an order that depends on the plan alone
 // A window that fails the gate gets status 1 (2: NaN / Inf) and zero blocks.
 #include <hip/hip_runtime.h>
 
@@ -41,7 +46,32 @@ __device__ __forceinline__ void dd_fma(double &hi, double &lo, double a, double 
     dd_add(hi, lo, p, pe);
 }
 
-__global__ void __launch_bounds__(256) covariance_kernel(CovArgs A) {
+// init + sum_{k0 <= k < k1} a(k) b(k) for phase 7, in twice the working precision and rounded once, as four interleaved partial sums: the
+// operands of a group are loaded before its first product, so that a group costs one round trip to the y buffers, not one per term, and
+// four chains run side by side.  Groups of eight, then one of four, go to partial sums 0 .. 3 in turn; a tail of up to three terms goes to
+// partial sum 0; the partial sums are added as (0 + 1) + (2 + 3).  The order depends on k0 and k1 alone.
+template <class FA, class FB> __device__ __forceinline__ double dd_dot4(double init, int k0, int k1, FA a, FB b) {
+    double h0 = init, l0 = 0.0, h1 = 0.0, l1 = 0.0, h2 = 0.0, l2 = 0.0, h3 = 0.0, l3 = 0.0;
+    int k = k0;
+    for (; k + 7 < k1; k += 8) {
+        const double a0 = a(k), a1 = a(k + 1), a2 = a(k + 2), a3 = a(k + 3), a4 = a(k + 4), a5 = a(k + 5), a6 = a(k + 6), a7 = a(k + 7);
+        const double b0 = b(k), b1 = b(k + 1), b2 = b(k + 2), b3 = b(k + 3), b4 = b(k + 4), b5 = b(k + 5), b6 = b(k + 6), b7 = b(k + 7);
+        dd_fma(h0, l0, a0, b0); dd_fma(h1, l1, a1, b1); dd_fma(h2, l2, a2, b2); dd_fma(h3, l3, a3, b3);
+        dd_fma(h0, l0, a4, b4); dd_fma(h1, l1, a5, b5); dd_fma(h2, l2, a6, b6); dd_fma(h3, l3, a7, b7);
+    }
+    if (k + 3 < k1) {
+        const double a0 = a(k), a1 = a(k + 1), a2 = a(k + 2), a3 = a(k + 3), b0 = b(k), b1 = b(k + 1), b2 = b(k + 2), b3 = b(k + 3);
+        dd_fma(h0, l0, a0, b0); dd_fma(h1, l1, a1, b1); dd_fma(h2, l2, a2, b2); dd_fma(h3, l3, a3, b3);
+        k += 4;
+    }
+    for (; k < k1; k++) dd_fma(h0, l0, a(k), b(k));
+    dd_add(h0, l0, h1, l1);
+    dd_add(h2, l2, h3, l3);
+    dd_add(h0, l0, h2, l2);
+    return h0 + l0;
+}
+
+template <bool LM> __global__ void __launch_bounds__(256) covariance_kernel(CovArgs A) {
     extern __shared__ __attribute__((aligned(16))) double cov_lds_raw[];
     const int tid = threadIdx.x;
     lds_d *lds = (lds_d *)cov_lds_raw;
@@ -247,6 +277,11 @@ __global__ void __launch_bounds__(256) covariance_kernel(CovArgs A) {
         const int m = rq[RQ_M], n_req = rq[RQ_NREQ];
         if (st != COV_STATUS_OK) {
             for (int i = tid; i < n_req * COV_BLOCK_DOUBLES; i += 256) out[i] = 0.0;
+            if (LM) {
+                gbl_d *lv = (gbl_d *)(A.lm_var + (size_t)win * A.lm_lmax), *lc = (gbl_d *)(A.lm_cross + (size_t)win * A.lm_lmax * A.lm_mstride);
+                for (int i = tid; i < L; i += 256) lv[i] = 0.0;
+                for (int i = tid; i < L * A.lm_mstride; i += 256) lc[i] = 0.0;
+            }
             __syncthreads();
             continue;
         }
@@ -278,6 +313,49 @@ __global__ void __launch_bounds__(256) covariance_kernel(CovArgs A) {
             }
             out[e] = v + lo;
         }
+
+        // ---- 7. the landmarks, COV_LM_CHUNK at a time: one thread per landmark for y_l and the variance, then one thread per cross entry
+        if (LM) {
+            const int *lt = A.ltab + A.ltab_base[W->plan], *lslot = lt + L + 1;
+            gbl_d *YL = (gbl_d *)(A.ylm + (size_t)blockIdx.x * COV_MAX_DIM * COV_LM_CHUNK);
+            gbl_d *lvar = (gbl_d *)(A.lm_var + (size_t)win * A.lm_lmax), *lcross = (gbl_d *)(A.lm_cross + (size_t)win * A.lm_lmax * A.lm_mstride);
+            for (int l0 = 0; l0 < L; l0 += COV_LM_CHUNK) {
+                const int nl = L - l0 < COV_LM_CHUNK ? L - l0 : COV_LM_CHUNK;
+                if (tid < nl) {
+                    const int l = l0 + tid, s0 = lt[l], s1 = lt[l + 1];
+                    const int t0 = s1 > s0 ? lslot[s0 * LT_SLOT] : nc;
+                    const double ih = j_hll[2 * l], il = j_hll[2 * l + 1];
+                    for (int k = t0; k < nc; k++) YL[k * COV_LM_CHUNK + tid] = 0.0;
+                    for (int s = s0; s < s1; s++) {      // w = (h hi + lo) * (1 / H_ll hi + lo), rounded once
+                        const int *q = lslot + s * LT_SLOT;
+                        for (int j = 0; j < q[2]; j++) {
+                            const double hh = Jr[q[1] + j], hl = Jr[q[1] + 6 + j];
+                            const double t = hh * ih;
+                            const double rest = hh * il + hl * ih;
+                            const double tl = __builtin_fma(hh, ih, -t) + rest;
+                            YL[(q[0] + j) * COV_LM_CHUNK + tid] = t + tl;
+                        }
+                    }
+                    double vh = ih, vl = il;
+                    for (int i = t0; i < nc; i++) {
+                        const lds_d *row = tri + i * (i + 1) / 2;
+                        const double y = dd_dot4(YL[i * COV_LM_CHUNK + tid], t0, i, [&](int k) { return -row[k]; }, [&](int k) { return YL[k * COV_LM_CHUNK + tid]; }) / ldiag[i];
+                        YL[i * COV_LM_CHUNK + tid] = y;
+                        dd_fma(vh, vl, y, y);
+                    }
+                    lvar[l] = vh + vl;
+                }
+                __threadfence_block();
+                __syncthreads();
+                for (int e = tid; e < nl * m; e += 256) {
+                    const int c = e / nl, t = e - nl * c, l = l0 + t;
+                    const int s0 = lt[l], t0 = lt[l + 1] > s0 ? lslot[s0 * LT_SLOT] : nc, p = rq[RQ_COL + c];
+                    // (0.0 - x, not -x: an empty sum -- a landmark all of whose slots are constant -- is +0.0, like every other zero this call returns)
+                    lcross[(size_t)l * A.lm_mstride + c] = 0.0 - dd_dot4(0.0, t0 > p ? t0 : p, nc, [&](int k) { return YL[k * COV_LM_CHUNK + t]; }, [&](int k) { return Y[k * m + c]; });
+                }
+                __syncthreads();      // the chunk's y_l go to the next chunk
+            }
+        }
         __syncthreads();      // LDS and the staging area go to the next window
     }
 }
@@ -286,8 +364,16 @@ __global__ void __launch_bounds__(256) covariance_kernel(CovArgs A) {
 
 extern "C" int tcv_launch_covariance(const tcv::CovArgs *args, int grid, size_t lds_bytes, void *stream) {
     using namespace tcv;
-    hipError_t e = hipFuncSetAttribute((const void *)covariance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    hipError_t e = hipFuncSetAttribute((const void *)covariance_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(covariance_kernel, dim3(grid), dim3(256), lds_bytes, (hipStream_t)stream, *args);
+    hipLaunchKernelGGL(covariance_kernel<false>, dim3(grid), dim3(256), lds_bytes, (hipStream_t)stream, *args);
+    return (int)hipGetLastError();
+}
+// the instantiation with the landmark phase (tcv_batch_compute_landmark_covariance): the plain call's kernel stays as it was
+extern "C" int tcv_launch_landmark_covariance(const tcv::CovArgs *args, int grid, size_t lds_bytes, void *stream) {
+    using namespace tcv;
+    hipError_t e = hipFuncSetAttribute((const void *)covariance_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(covariance_kernel<true>, dim3(grid), dim3(256), lds_bytes, (hipStream_t)stream, *args);
     return (int)hipGetLastError();
 }
