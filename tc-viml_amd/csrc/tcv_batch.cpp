@@ -464,6 +464,28 @@ int tcv_batch_enter_stream(tcv_batch *b, void *hip_stream) {
     b->last_stream = st; b->pending = true;
     return TCV_OK;
 }
+// a per-plan side table of the batch (tcv_host.h PlanTable): the evaluation's and the covariance's owner lists, the landmark slot tables
+int tcv::plan_table_create(const tcv_batch *b, const std::function<int(int, std::vector<int> &)> &entry, const char *what_alloc, const char *what_upload, PlanTable *t) {
+    const int np = (int)b->plans.size();
+    std::vector<long long> base(np, -1);
+    std::vector<int> ints, one;
+    for (int w = 0; w < b->n; w++) {      // the first window of every distinct plan
+        const int pl = b->wins[w].plan;
+        if (base[pl] >= 0) continue;
+        base[pl] = (long long)ints.size();
+        if (int rc = entry(w, one)) return rc;
+        ints.insert(ints.end(), one.begin(), one.end());
+    }
+    const size_t head = sizeof(long long) * (size_t)np, bytes = head + sizeof(int) * std::max<size_t>(1, ints.size());
+    std::vector<char> img(bytes, 0);
+    std::memcpy(img.data(), base.data(), head);
+    if (!ints.empty()) std::memcpy(img.data() + head, ints.data(), sizeof(int) * ints.size());
+    void *d = nullptr;
+    if (hipError_t e = tcv::dev_malloc(&d, bytes)) return hip_fail(e, what_alloc);
+    if (int rc = tcv::staged_upload(d, img.data(), bytes, what_upload)) { tcv::dev_free(d); return rc; }
+    t->d = d; t->base = (long long *)d; t->ints = (int *)((char *)d + head);
+    return TCV_OK;
+}
 
 static int wall_clock_khz() {
     int dev = 0, khz = 0;

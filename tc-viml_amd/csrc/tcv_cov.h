@@ -2,13 +2,13 @@
 // marginal covariance S^-1 of the camera-side states, S = H_cc - sum_l h_l h_l' / H_ll the reduced camera system of H = J'J at the
 // evaluation point.  The kernel reads what the batch holds already (window headers, plans, pools of tcv_packed.h) plus two side tables
 // that live BESIDE the plans: the owner lists of S (one per distinct plan, built once per batch) and the request table (one per window,
-// rebuilt when the request list changes).  Host half: tcv_cov_host.cpp.
+// rebuilt when the request list changes).  Host half: tcv_cov_tables.cpp builds the tables, tcv_cov_host.cpp keeps the buffers.
 #pragma once
 #include "tcv_packed.h"
 
 namespace tcv {
 
-enum { COV_MAX_DIM = 184, COV_BLOCK_DOUBLES = 81, COV_MAX_BLOCKS = 512 };
+enum { COV_MAX_DIM = 184, COV_BLOCK_DOUBLES = 81 };
 enum { COV_STATUS_OK = 0, COV_STATUS_RANK = 1, COV_STATUS_NONFINITE = 2 };
 
 // ---- the staging area of one workgroup (doubles, CovArgs::stage)

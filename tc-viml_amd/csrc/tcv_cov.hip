@@ -362,18 +362,12 @@ template <bool LM> __global__ void __launch_bounds__(256) covariance_kernel(CovA
 
 }  // namespace tcv
 
-extern "C" int tcv_launch_covariance(const tcv::CovArgs *args, int grid, size_t lds_bytes, void *stream) {
+// covariance_kernel<true> carries the landmark phase (tcv_batch_compute_landmark_covariance); the plain call's kernel is covariance_kernel<false>
+extern "C" int tcv_launch_covariance(const tcv::CovArgs *args, int grid, size_t lds_bytes, void *stream, bool landmarks) {
     using namespace tcv;
-    hipError_t e = hipFuncSetAttribute((const void *)covariance_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    const auto kernel = !landmarks ? covariance_kernel<false> : covariance_kernel<true>;      // (instantiated in this order: the code object keeps its layout)
+    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(covariance_kernel<false>, dim3(grid), dim3(256), lds_bytes, (hipStream_t)stream, *args);
-    return (int)hipGetLastError();
-}
-// the instantiation with the landmark phase (tcv_batch_compute_landmark_covariance): the plain call's kernel stays as it was
-extern "C" int tcv_launch_landmark_covariance(const tcv::CovArgs *args, int grid, size_t lds_bytes, void *stream) {
-    using namespace tcv;
-    hipError_t e = hipFuncSetAttribute((const void *)covariance_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(covariance_kernel<true>, dim3(grid), dim3(256), lds_bytes, (hipStream_t)stream, *args);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds_bytes, (hipStream_t)stream, *args);
     return (int)hipGetLastError();
 }

@@ -16,11 +16,9 @@ using namespace tcv;
 extern "C" int tcv_launch_evaluate(const tcv::EvalArgs *args, size_t lds_bytes, void *stream);
 namespace {
 struct EvalState {
-    void *d_tab = nullptr;      // [offset of every plan's owner lists (long long) | the lists]
+    PlanTable tab;              // the owner lists of every plan
     void *d_out = nullptr;      // [scalars | residuals | block costs | gradient | staging], per window each
     double *d_scal = nullptr, *d_res = nullptr, *d_blk = nullptr, *d_grad = nullptr, *d_stage = nullptr;
-    long long *d_tab_base = nullptr;
-    int *d_tab_ints = nullptr;
     int res_stride = 0, blk_stride = 0, grad_stride = 0, stage_stride = 0;
     bool evaluated = false;
     tcv_evaluate_options last;
@@ -29,7 +27,7 @@ struct EvalState {
 void tcv_eval_free(tcv_batch *b) {
     EvalState *s = (EvalState *)b->eval;
     if (!s) return;
-    tcv::dev_free(s->d_tab); tcv::dev_free(s->d_out);
+    tcv::dev_free(s->tab.d); tcv::dev_free(s->d_out);
     delete s;
     b->eval = nullptr;
 }
@@ -41,16 +39,13 @@ static void eval_owner_lists(const tcv_batch *b, int w, std::vector<int> &out) {
     const Packed &pk = b->packed[w];
     const PlanHdr &H = b->plans[b->wins[w].plan];
     const int nl = H.nc + H.nland;
-    std::vector<int> cam_of(p.blocks.size(), -1), lm_of(p.blocks.size(), -1);
-    for (size_t c = 0; c < pk.cam_block.size(); c++) cam_of[pk.cam_block[c]] = (int)c;
-    for (size_t l = 0; l < pk.lm_block.size(); l++) lm_of[pk.lm_block[l]] = (int)l;
-    auto toff = [&](int blk) { return cam_of[blk] >= 0 ? pk.cam_loff[cam_of[blk]] : -1; };
+    const BlockMap map(p, pk);
     std::vector<std::vector<int>> own(nl);
     int off = 0;
     if (H.prior_n > 0) {
         const tcv_prior *pr = p.prior[0].prior;
         for (int k = 0; k < H.prior_nblk; k++) {
-            const int t = toff(p.prior[0].b[k]), local = pr->size[k] == 7 ? 6 : pr->size[k];
+            const int t = map.toff(p.prior[0].b[k]), local = pr->size[k] == 7 ? 6 : pr->size[k];
             for (int j = 0; j < local; j++) if (t >= 0 && pr->idx[k] + j < pr->n) own[t + j].push_back(off + pr->idx[k] + j);
         }
         off += H.prior_n;
@@ -58,7 +53,7 @@ static void eval_owner_lists(const tcv_batch *b, int w, std::vector<int> &out) {
     for (size_t f = 0; f < p.imu.size(); f++) {
         static const int col0[4] = {0, 6, 15, 21}, wid[4] = {6, 9, 6, 9};
         for (int k = 0; k < 4; k++) {
-            const int t = toff(p.imu[f].b[k]);
+            const int t = map.toff(p.imu[f].b[k]);
             for (int j = 0; j < wid[k]; j++) if (t >= 0) own[t + j].push_back(off + (int)f * EV_PIECE_IMU + col0[k] + j);
         }
     }
@@ -66,15 +61,15 @@ static void eval_owner_lists(const tcv_batch *b, int w, std::vector<int> &out) {
     for (size_t k = 0; k < pk.proj_order.size(); k++) {
         const ProjFac &f = p.proj[pk.proj_order[k]];
         for (int s = 0; s < 3; s++) {
-            const int t = toff(f.b[s]);
+            const int t = map.toff(f.b[s]);
             for (int j = 0; j < 6; j++) if (t >= 0) own[t + j].push_back(off + (int)k * EV_PIECE_PROJ + 6 * s + j);
         }
-        own[H.nc + lm_of[f.b[3]]].push_back(off + (int)k * EV_PIECE_PROJ + 18);
-        if (f.btd >= 0) { const int t = toff(f.btd); if (t >= 0) own[t].push_back(off + (int)k * EV_PIECE_PROJ + 19); }
+        own[H.nc + map.lm_of(f.b[3])].push_back(off + (int)k * EV_PIECE_PROJ + 18);
+        if (f.btd >= 0) { const int t = map.toff(f.btd); if (t >= 0) own[t].push_back(off + (int)k * EV_PIECE_PROJ + 19); }
     }
     off += EV_PIECE_PROJ * H.n_proj;
     for (size_t k = 0; k < p.line.size(); k++) {
-        const int t = toff(p.line[k].b);
+        const int t = map.toff(p.line[k].b);
         for (int j = 0; j < 6; j++) if (t >= 0) own[t + j].push_back(off + (int)k * EV_PIECE_LINE + j);
     }
     out.clear();
@@ -87,42 +82,18 @@ static void eval_owner_lists(const tcv_batch *b, int w, std::vector<int> &out) {
 static int eval_prepare(tcv_batch *b) {
     if (b->eval) return TCV_OK;
     std::unique_ptr<EvalState> s(new EvalState());
-    const int n = b->n, np = (int)b->plans.size();
-    std::vector<long long> base(np, -1);
-    std::vector<int> ints, one;
-    for (int w = 0; w < n; w++) {
-        const int pl = b->wins[w].plan;
-        if (base[pl] >= 0) continue;
-        base[pl] = (long long)ints.size();
-        eval_owner_lists(b, w, one);
-        ints.insert(ints.end(), one.begin(), one.end());
-    }
+    const int n = b->n;
     for (auto &H : b->plans) {
         s->res_stride = std::max(s->res_stride, eval_num_residuals(H)); s->blk_stride = std::max(s->blk_stride, eval_num_blocks(H));
         s->stage_stride = std::max(s->stage_stride, (eval_stage_doubles(H) + 1) & ~1);
     }
     s->res_stride = (s->res_stride + 1) & ~1; s->blk_stride = (s->blk_stride + 1) & ~1; s->grad_stride = b->delta_stride;
-    const size_t tab_head = sizeof(long long) * (size_t)np, tab_bytes = tab_head + sizeof(int) * std::max<size_t>(1, ints.size());
     const size_t per_win = (size_t)EV_SCALARS + s->res_stride + s->blk_stride + s->grad_stride + s->stage_stride;
-    struct Guard { EvalState *s; ~Guard() { if (s) { tcv::dev_free(s->d_tab); tcv::dev_free(s->d_out); } } } guard{s.get()};
-    hipError_t e = tcv::dev_malloc(&s->d_tab, tab_bytes);
-    if (e == hipSuccess) e = tcv::dev_malloc(&s->d_out, sizeof(double) * per_win * (size_t)n);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc (evaluation buffers)");
-    {
-        tcv::StagedTransfer up(tcv::util_stream(), tab_bytes);
-        if (!up.host) { set_error("hipHostMalloc (upload staging) failed"); return TCV_ERR_HIP; }
-        std::memcpy(up.host, base.data(), tab_head);
-        if (!ints.empty()) std::memcpy((char *)up.host + tab_head, ints.data(), sizeof(int) * ints.size());
-        up.issued();
-        e = hipMemcpyAsync(s->d_tab, up.host, tab_bytes, hipMemcpyHostToDevice, up.st);
-        const hipError_t ew = up.wait();
-        if (e == hipSuccess) e = ew;
-        if (e != hipSuccess) return hip_fail(e, "upload of the evaluation tables");
-    }
-    s->d_tab_base = (long long *)s->d_tab; s->d_tab_ints = (int *)((char *)s->d_tab + tab_head);
+    if (int rc = plan_table_create(b, [&](int w, std::vector<int> &out) { eval_owner_lists(b, w, out); return (int)TCV_OK; },
+                                   "hipMalloc (evaluation buffers)", "upload of the evaluation tables", &s->tab)) return rc;
+    if (hipError_t e = tcv::dev_malloc(&s->d_out, sizeof(double) * per_win * (size_t)n)) { tcv::dev_free(s->tab.d); return hip_fail(e, "hipMalloc (evaluation buffers)"); }
     s->d_scal = (double *)s->d_out; s->d_res = s->d_scal + (size_t)n * EV_SCALARS; s->d_blk = s->d_res + (size_t)n * s->res_stride;
     s->d_grad = s->d_blk + (size_t)n * s->blk_stride; s->d_stage = s->d_grad + (size_t)n * s->grad_stride;
-    guard.s = nullptr;
     b->eval = s.release();
     return TCV_OK;
 }
@@ -144,7 +115,7 @@ extern "C" int tcv_batch_evaluate(tcv_batch *b, const tcv_evaluate_options *o, v
     std::memset(&a, 0, sizeof a);
     a.win = b->d_win; a.plans = b->d_plans; a.plan_base = b->d_plan_base; a.ipool = b->d_ipool; a.dpool = b->d_dpool;
     a.state = o->at == TCV_EVALUATE_AT_SOLUTION ? b->d_state : nullptr;
-    a.tab_base = s->d_tab_base; a.tab = s->d_tab_ints;
+    a.tab_base = s->tab.base; a.tab = s->tab.ints;
     a.scalars = s->d_scal;
     a.residuals = o->want_residuals ? s->d_res : nullptr; a.block_cost = o->want_block_costs ? s->d_blk : nullptr;
     a.gradient = o->want_gradient ? s->d_grad : nullptr; a.stage = s->d_stage;

@@ -1,12 +1,14 @@
 // Host-side data model behind the C-ABI of include/tcv.h: the ceres::Problem-shaped graph
 // (reference vins_estimator/src/estimator.cpp:1679-1886), the MarginalizationInfo-shaped prior
 // (factor/marginalization_factor.h:46-72) and the packer that turns a problem into the
-// device-resident plan + data of tcv_packed.h.
+// device-resident plan + data of tcv_packed.h; behind the batch, what the side tables beside its plans share
+// (PlanTable, BlockMap) and the covariance's table builders.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -244,6 +246,48 @@ int tcv_relo_launch(tcv_batch *b, hipStream_t st);                 // tcv_batch_
 // the batch's pending work there -- the gauge fix and the marginalisation read what the solve wrote -- and the stream joins the set
 // tcv_batch_synchronize waits for
 int tcv_batch_enter_stream(tcv_batch *b, void *hip_stream);
+namespace tcv {
+// A side table beside the plans of a batch (the owner lists of the gradient and of S, the landmark slot tables): one device allocation
+// [offset of every distinct plan's entry, in ints (long long) | the entries], at least one int behind the offsets.
+struct PlanTable { void *d = nullptr; long long *base = nullptr; int *ints = nullptr; };
+// entry(w, out) builds the entry of window w's plan (TCV_OK, or a status with the message set); it is asked once per distinct plan, for the
+// first window that uses it, in window order.  Allocates, uploads (staged_upload) and frees on failure; the caller frees t->d (dev_free).
+int plan_table_create(const tcv_batch *b, const std::function<int(int, std::vector<int> &)> &entry, const char *what_alloc, const char *what_upload, PlanTable *t);
+// problem block -> camera block / landmark of the packed window (-1: none) and tangent offset (-1: constant or no camera block)
+struct BlockMap {
+    const Packed &pk;
+    const size_t nb;
+    std::vector<int> of;      // [camera block of every problem block | landmark of every problem block]
+    BlockMap(const tcv_problem &p, const Packed &packed) : pk(packed), nb(p.blocks.size()), of(2 * nb, -1) {
+        for (size_t c = 0; c < pk.cam_block.size(); c++) of[pk.cam_block[c]] = (int)c;
+        for (size_t l = 0; l < pk.lm_block.size(); l++) of[nb + pk.lm_block[l]] = (int)l;
+    }
+    int cam_of(int blk) const { return of[blk]; }
+    int lm_of(int blk) const { return of[nb + blk]; }
+    int toff(int blk) const { return of[blk] >= 0 ? pk.cam_loff[of[blk]] : -1; }
+};
+}  // namespace tcv
+// The side tables of the marginal covariance (tcv_cov_tables.cpp; layouts: tcv_cov.h): no device call; TCV_OK or a status with the message set
+struct tcv_covariance_block;
+namespace tcv {
+// the problem block of one half of a request and its tangent width (either may be null)
+int cov_resolve(const tcv_problem &p, int kind, int index, int *blk, int *width);
+// The slots of h_l: per landmark (plan order) the distinct variable blocks of its point factors, in order of first appearance; of a window
+// whose owner lists were not refused.
+struct CovLmSlots {
+    std::vector<int> lmptr{0}, lmfac;           // the point factors (plan order) of landmark l: lmfac[lmptr[l] .. lmptr[l + 1]]
+    std::vector<int> sptr{0}, blk, off;         // the slots of landmark l: sptr[l] .. sptr[l + 1]; per slot its problem block and its offset in the J region
+    std::vector<std::vector<int>> items;        // per slot its hitem records
+    int jdoubles = 0;                           // doubles of the J region, the slots at its end
+};
+CovLmSlots cov_landmark_slots(const tcv_problem &p, const Packed &pk, const PlanHdr &H);
+// the owner lists of S for the plan of a window; refuses (TCV_ERR_UNSUPPORTED) a constant inverse depth and a factor that names one block twice
+int cov_owner_lists(const tcv_problem &p, const Packed &pk, const PlanHdr &H, std::vector<int> &out, int *jdoubles);
+// the plan's landmark slot table: lsptr, then the slots of every landmark in ascending tangent order
+std::vector<int> cov_slot_table(const tcv_problem &p, const Packed &pk, const CovLmSlots &slots);
+// the request tables of every window (RQ_*) for a request list, and the sizes of its blocks
+int cov_request_tables(const tcv_batch *b, const tcv_covariance_block *blocks, int n_req, std::vector<int> &rq, std::vector<int> &rows, std::vector<int> &cols);
+}  // namespace tcv
 int tcv_marg_sqrt_source(const tcv_batch *b, int window);   // index of that factor among the solve problem's IMU factors, -1 none
 int tcv_marg_attach(tcv_batch *b, tcv_problem *const *marg_problems, double *const *const *marg_drop, const int *marg_num_drop);
 int tcv_marg_run(tcv_batch *b, void *stream);

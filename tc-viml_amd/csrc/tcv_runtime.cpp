@@ -1,5 +1,5 @@
 // Process-level runtime of the library (tcv_runtime.h): the calling thread's error text, the device free list, the pinned staging pool,
-// the per-thread streams and their park, deferred releases, StagedTransfer / staged_download, and the small entry points of include/tcv.h
+// the per-thread streams and their park, deferred releases, StagedTransfer / staged_download / staged_upload, and the small entry points of include/tcv.h
 // that concern the process rather than a problem or a batch.  There is no CPU fallback: without a HIP device device_ready() says so.
 #include <hip/hip_runtime.h>
 
@@ -278,6 +278,16 @@ int staged_download(void *dst, const void *d_src, size_t bytes, const char *what
     if (e != hipSuccess) return hip_fail(e, what);
     std::memcpy(dst, dl.host, bytes);
     return TCV_OK;
+}
+int staged_upload(void *d_dst, const void *src, size_t bytes, const char *what) {
+    StagedTransfer up(util_stream(), bytes);
+    if (!up.host) { set_error("hipHostMalloc (upload staging) failed"); return TCV_ERR_HIP; }
+    std::memcpy(up.host, src, bytes);
+    up.issued();
+    hipError_t e = hipMemcpyAsync(d_dst, up.host, bytes, hipMemcpyHostToDevice, up.st);
+    const hipError_t ew = up.wait();
+    if (e == hipSuccess) e = ew;
+    return e == hipSuccess ? (int)TCV_OK : hip_fail(e, what);
 }
 }  // namespace tcv
 using namespace tcv;

@@ -48,6 +48,8 @@ private:
 };
 // blocking download through pinned staging on the calling thread's own stream (the default stream serialises the host threads of a process)
 int staged_download(void *dst, const void *d_src, size_t bytes, const char *what);
+// the other direction, same contract: `bytes` of host memory into device memory, TCV_OK or the hip_fail status under `what`
+int staged_upload(void *d_dst, const void *src, size_t bytes, const char *what);
 // a non-blocking stream of the calling thread on its current device, created on first use and kept: the one-shot entry points
 // (pre-integration, line association, gauge fix, the factor evaluators) launch there and wait for THAT stream, never for the device --
 // another host thread's batches keep running (several estimator groups per GPU, bench.py --mode replay)

@@ -202,6 +202,40 @@ def test_the_two_covariance_calls_share_a_batch_and_keep_their_own_results(gpu):
     assert np.all(ref_lm[1][0] ** 2 <= np.outer(ref_lm[0], cpp) * (1 + 1e-9))
 
 
+def test_the_landmark_call_first_on_a_fresh_batch_then_the_plain_call(gpu):
+    """the opposite order of the test above: the slot tables are built on a batch whose owner lists the same call has just made, and
+    both results equal, bit for bit, those of twin batches that made only one of the calls"""
+    w, kw = case("frames6_td")
+    cross = LO.cross_list(w)
+    rq = CC.requests("frames6_td")
+
+    def batch():
+        return gpu.Batch([hip(gpu, w, kw)[0]])
+    twin_cv, twin_lc, both = batch(), batch(), batch()
+    cv.compute(twin_cv, rq)
+    ref_blocks = [cv.block(twin_cv, 0, k) for k in range(len(rq))]
+    ref_lm = device(twin_lc, cross)
+    lm = device(both, cross)
+    cv.compute(both, rq)
+    assert same(lm, ref_lm) and lm[2][0] == ref_lm[2][0] == lc.OK
+    assert all(np.array_equal(cv.block(both, 0, k), ref_blocks[k]) for k in range(len(rq))) and cv.status(both)[0] == cv.status(twin_cv)[0] == cv.OK
+    assert same((lc.variances(both, 0), [lc.cross(both, 0, k) for k in range(len(cross))]), ref_lm)      # still there behind the plain call
+
+
+def test_two_plans_in_one_batch_every_window_has_the_bits_of_its_solo_run(gpu):
+    """frames4 + frames6_td: the smallest batch in which the second plan's offset is non-zero in the owner lists and in the slot tables"""
+    names = ("frames4", "frames6_td")
+    solo = [device(gpu.Batch([hip(gpu, *case(n))[0]]), COMMON) for n in names]
+    for order in ((0, 1), (1, 0)):
+        b = gpu.Batch([hip(gpu, *case(names[i]))[0] for i in order])
+        assert b.plan_stats()["num_plans"] == 2
+        lc.compute(b, COMMON)
+        st = lc.status(b)
+        for pos, i in enumerate(order):
+            assert st[pos] == solo[i][2][0] == lc.OK, (order, pos)
+            assert same((lc.variances(b, pos), [lc.cross(b, pos, k) for k in range(len(COMMON))]), solo[i]), (order, pos)
+
+
 @pytest.mark.parametrize("setting", ("chain", "dense", "cooperative"))
 def test_a_twin_batch_that_never_computes_a_landmark_covariance_ends_with_the_same_bits(gpu, setting):
     wins = [synth.window_at(synth.make_windows(42, 2, frame_shift=-1), k) for k in range(2)]
