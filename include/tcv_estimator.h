@@ -8,7 +8,8 @@
  *   removeFront :655-696) and the chaining of the marginalisation prior (:2027-2044, :2083-2113).
  * The solver itself is the C-ABI of tcv.h (device pre-integration, fused solve, gauge fix, marginalisation, line association).
  * Out of scope as in the rest of this library: image / line front end (the caller delivers tracked points and line tracks),
- * initialisation (the window is filled from caller-provided states).  ESTIMATE_TD (the online camera-IMU time offset,
+ * initialisation (the window is filled from caller-provided states; tcv_vi_alignment.h computes them from up-to-scale SfM poses and the
+ * IMU stream: the gyroscope bias, gravity, the scale and the metric Ps / Rs / Vs).  ESTIMATE_TD (the online camera-IMU time offset,
  * with the rolling-shutter terms TR / ROW) is in: its entry points are declared in tcv_estimator_td.h, included at the end of this file; cutting the IMU
  * stream at img_t + td stays with the caller, like the rest of estimator_node.cpp.  Relocalisation is in as well (setReloFrame, relo_Pose in the
  * window, the drift correction of double2vector's tail): tcv_estimator_relo.h, included at the end of this file; the pose graph that finds the loop stays out.
