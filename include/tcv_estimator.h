@@ -116,6 +116,12 @@ int tcv_estimator_finish_frame(tcv_estimator *e, double P[3], double q_xyzw[4], 
 int tcv_estimators_finish_frames(tcv_estimator *const *e, int n, double *P, double *q_xyzw, double *V, int *rc, tcv_estimator_stats *stats);
 /* Estimator::clearState() + setParameter() (estimator.cpp:126-189, :39-52; estimator_node.cpp:437-446 after a failure): drops the
  * window, the IMU buffers, every feature / line track, the marginalisation prior and the biases; configuration and line map stay.
+ * So do this library's own settings: the window tap and what tcv_estimator_set_time_offset set; td itself goes back to td0.
+ * After a reset tcv_estimator_get_stats reads all zero, tcv_estimator_frame_serial reports next_serial 0 and no slot in use,
+ * tcv_estimator_get_relocalization the record of an estimator that never relocalised (valid 0, drift_correct_r the identity), a pending
+ * relocalisation request is gone, and the same frames stepped through again give the bits of the first pass.  A tap that was on stays
+ * on, and the snapshot getters go on serving the last window optimised BEFORE the reset until the next tcv_estimators_optimize
+ * replaces it.
  * "Reset it" above means this call (or destroy + create). */
 int tcv_estimator_reset(tcv_estimator *e);
 int tcv_estimator_get_stats(const tcv_estimator *e, tcv_estimator_stats *out);
@@ -123,7 +129,7 @@ int tcv_estimator_get_stats(const tcv_estimator *e, tcv_estimator_stats *out);
  * window this estimator handed to the solver -- what OptimizationWithLine sees after vector2double and the graph construction
  * (estimator.cpp:1492-1535, :1683-1846): parameter arrays before and after the solve, factor lists, pre-integrations, the incoming prior.
  * tests/test_gpu_teacher.py re-solves every tapped window of a native replay with the CPU oracle.  The arrays of a snapshot belong to the
- * estimator and stay valid until its next tcv_estimators_optimize / reset / destroy.  The tap waits for device-resident inputs (prior,
+ * estimator and stay valid until its next tcv_estimators_optimize / destroy (a reset keeps them: see tcv_estimator_reset).  The tap waits for device-resident inputs (prior,
  * pre-integrations) to copy them: it costs a frame its overlap, never its results. */
 typedef struct tcv_window_snapshot {
     int n_frames, n_landmarks, n_imu, n_proj, n_line, marg_flag, estimate_extrinsic, line_exact_jacobian;

@@ -809,7 +809,7 @@ class HipBackend:
 
 
 # ----------------------------------------------------------------------------------------------------------------
-# the same window management in native code: include/tcv_estimator.h (tc-viml_amd/csrc/tcv_estimator.cpp)
+# the same window management in native code: include/tcv_estimator.h (tc-viml_amd/csrc/tcv_estimator.cpp, tcv_est_*.cpp)
 # ----------------------------------------------------------------------------------------------------------------
 class _EstimatorConfig(C.Structure):
     _fields_ = [("focal_length", C.c_double), ("min_parallax", C.c_double), ("init_depth", C.c_double),

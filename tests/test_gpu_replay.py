@@ -147,6 +147,69 @@ def test_native_estimator_reset_reproduces_a_fresh_estimator(gpu):
         assert [l["prior_n"] for l in a["log"]] == [l["prior_n"] for l in b["log"]]
 
 
+def _same(a, b):
+    """bit equality of nested dicts / lists / arrays / scalars"""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return isinstance(b, (list, tuple)) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if a is None or b is None:
+        return a is b
+    return np.array_equal(np.asarray(a), np.asarray(b))
+
+
+def test_native_estimator_reset_contract_with_the_tap_on(gpu):
+    """What include/tcv_estimator.h promises after tcv_estimator_reset: the statistics read zero, the frame serials restart, the
+    relocalisation record is that of an estimator that never relocalised, the tap stays on and its three getters go on serving the last
+    window optimised before the reset, and the same 13 frames (the eleventh fills the window: three are optimised) give the first pass's bits,
+    snapshots included."""
+    import ctypes as C
+    import relo_oracle
+    import td_oracle
+    tcv = gpu
+    L = tcv.lib()
+    SR = relo_oracle.snapshot_type(tcv)
+    L.tcv_estimator_set_window_tap.argtypes = [C.c_void_p, C.c_int]
+    L.tcv_estimator_get_window_snapshot.argtypes = [C.c_void_p, C.POINTER(td_oracle.Snapshot)]
+    L.tcv_estimator_get_window_snapshot_td.argtypes = [C.c_void_p, C.POINTER(td_oracle.SnapshotTd)]
+    L.tcv_estimator_get_window_snapshot_relo.argtypes = [C.c_void_p, C.POINTER(SR)]
+    ls = replay.NativeLockstep([replay.simulate_stream(43, 13, max_features=30)], num_iterations=8)
+
+    def snapshots():
+        S, T, R = td_oracle.Snapshot(), td_oracle.SnapshotTd(), SR()
+        tcv.check(L.tcv_estimator_get_window_snapshot(ls.ests[0], C.byref(S)))
+        tcv.check(L.tcv_estimator_get_window_snapshot_td(ls.ests[0], C.byref(T)))
+        tcv.check(L.tcv_estimator_get_window_snapshot_relo(ls.ests[0], C.byref(R)))
+        win, res = td_oracle.snapshot_window(tcv, S, T)
+        return win, res, (T.estimate_td, T.n_proj, T.td_in, T.td_out, T.TR, T.ROW, bool(T.proj_td_aux)), (R.has_relo, R.n_relo)
+
+    try:
+        tcv.check(L.tcv_estimator_set_window_tap(ls.ests[0], 1))
+        assert sum(ls.step(k) for k in range(13)) == 13 - replay.WINDOW_SIZE
+        first, snap = ls.results(), snapshots()
+        assert snap[1]["applied"] == 1 and snap[1]["iterations"] > 0
+        assert ls.frame_serials(0)[0] == 13
+        ls.reset()
+        assert _same(snapshots(), snap)                                  # the tap survives: still on, the last snapshot still served
+        st = replay._EstimatorStats()
+        tcv.check(L.tcv_estimator_get_stats(ls.ests[0], C.byref(st)))
+        assert [getattr(st, k) for k, _ in st._fields_] == [0] * len(st._fields_)
+        assert ls.frame_serials(0) == (0, [-1] * (replay.WINDOW_SIZE + 1), 0)
+        r = ls.relocalization(0)
+        assert (r["valid"], r["frame_index"], r["frame_serial"], r["relo_relative_yaw"]) == (0, 0, 0, 0.0)
+        assert np.array_equal(r["drift_correct_r"], np.eye(3))
+        assert not any(np.any(r[k]) for k in ("drift_correct_t", "relo_relative_t", "relo_relative_q", "relo_r", "relo_t"))
+        assert sum(ls.step(k) for k in range(13)) == 13 - replay.WINDOW_SIZE
+        again = ls.results()
+        assert _same(snapshots(), snap)
+    finally:
+        ls.close()
+    for a, b in zip(first, again):
+        assert len(a["t"]) == 13 - replay.WINDOW_SIZE
+        assert np.array_equal(a["p"], b["p"]) and np.array_equal(a["q"], b["q"]) and np.array_equal(a["v"], b["v"])
+        assert a["log"] == b["log"]
+
+
 def test_windows_of_a_replay_one_by_one_vs_oracle(gpu):
     """every window a replay hands to the solver (30 different graph structures: growing / sliding feature tracks, both
     marginalisation modes' priors, ~60 line factors) solved by the HIP path and by the C oracle from identical inputs: same

@@ -1,5 +1,5 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer over the HOST side of the product (review item 6 of round 2): tcv_pack.cpp,
-tcv_estimator.cpp, tcv_marg_host.cpp, tcv_runtime.cpp, tcv_problem.cpp, tcv_batch.cpp, tcv_eval_host.cpp and the host halves of the
+tcv_estimator.cpp, tcv_est_*.cpp, tcv_marg_host.cpp, tcv_runtime.cpp, tcv_problem.cpp, tcv_batch.cpp, tcv_eval_host.cpp and the host halves of the
 .hip files, built by
 `python tc-viml_amd/build.py --sanitize` (hipcc: the host pass is instrumented, the gfx950 pass is not -- GPU sanitizers are not
 available on this pool).  The instrumented library is driven without a device, in a child interpreter with the ASan runtime
