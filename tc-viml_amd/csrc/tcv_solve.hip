@@ -160,6 +160,43 @@ __device__ __forceinline__ double uni_d(double v) {
     r.y = __builtin_amdgcn_readfirstlane(u.y);
     return __builtin_bit_cast(double, r);
 }
+// The doubles the trust-region loop of solve_kernel carries from one phase call to the next.  As locals they sat in VGPRs (FP64 arithmetic
+// consumes them) and went to scratch memory around every call of a phase function: a store in front of it, a reload and a full memory wait
+// behind it (profiles/loop_state_ab.txt).  They live in red[40..55] instead, which nothing else uses in this build: a value is stored where it
+// is produced and read back (broadcast read, uni_d) where it is next used behind a call.  Every wavefront computes the same bits and lane 0
+// of each stores them to the one shared copy, so a wavefront always finds what it wrote itself -- PROVIDED no wavefront that runs ahead
+// replaces a value a slower one has yet to read: wherever a slot is rewritten without a barrier of a phase function between the last read
+// of the old value and the store of the new one, sync() comes first (the radius / cost / mu update at the end of an iteration, and the two
+// rare mu * 10 paths).  alpha and mu_next are not kept: they are recomputed from their operands (same operation, same bits).
+// The -DTCV_PROFILE build keeps its counters in the same doubles and the -DTCV_ABLATE builds remove the phases whose barriers the above
+// relies on: both keep the state in registers.
+enum { LS_COST, LS_RADIUS, LS_MU, LS_LIN_MU, LS_GG, LS_Q, LS_YG, LS_GDY, LS_DY2, LS_MCC, LS_STEP, LS_CA, LS_CB, LS_COST_C, LS_RHO, LS_XNORM, LS_COUNT };
+#if defined(TCV_PROFILE) || defined(TCV_ABLATE)
+struct LoopState {
+    double v[LS_COUNT];
+    __device__ __forceinline__ LoopState(lds_d *, int) {}
+    __device__ __forceinline__ double get(int i) const { return v[i]; }
+    __device__ __forceinline__ void set(int i, double x) { v[i] = uni_d(x); }
+    __device__ __forceinline__ void sync() const {}
+};
+#else
+struct LoopState {
+    lds_d *b;
+    bool w;
+    __device__ __forceinline__ LoopState(lds_d *red, int tid) : b(red + 40), w((tid & 63) == 0) { static_assert(40 + LS_COUNT <= 56, "red[56..63]: profile stamp, cooperative slot, flag"); }
+    __device__ __forceinline__ double get(int i) const { return uni_d(b[i]); }
+    __device__ __forceinline__ void set(int i, double x) { if (w) b[i] = x; }
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+};
+#endif
+// The thread index is the one per-lane value the loop needs behind every phase call (it is an argument of the next one): as a local it
+// went to scratch memory at the first call and came back in front of each one.  The wavefront's base index is uniform (a scalar register
+// survives a call) and the lane index is read from the hardware again where it is needed -- volatile, or the compiler keeps the first copy.
+__device__ __forceinline__ int lane_now() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
 template <int NT>
 __device__ __forceinline__ Ctx<NT> uniform_ctx(const Ctx<NT> &R) {
     Ctx<NT> C;
@@ -188,8 +225,9 @@ enum { SCR_HP = 8256, SCR_SQ = 16 * 225, SCR_LM = 1024 };      // the landmark/c
 // solve: as much L1 / L2 read traffic as everything else the kernel fetches, and a full memory wait in front of every phase.
 #define TCV_CTX_PARAMS cst_plan *aP_, cst_i *aip_, cst_d *adp_, cst_win *aW_, gbl_d *ascr_, gbl_d *aimu_, gbl_d *aspill_, gbl_d *aprof_, \
                        lds_d *atiles_, lds_d *astage_, lds_d *axs_, int and_, int antd_, int antiles_, int astagecap_, int atid_, unsigned askip_
-#define TCV_CTX_ARGS(K) (K).P, (K).ip, (K).dp, (K).W, (K).v_s, (K).g_imublk, (K).g_spill, (K).prof, (K).tiles, (K).stage, (K).xs, (K).nd, (K).ntd, \
-                        (K).ntiles, (K).stage_cap, (K).tid, (K).skip
+#define TCV_CTX_ARGS_TID(K, T) (K).P, (K).ip, (K).dp, (K).W, (K).v_s, (K).g_imublk, (K).g_spill, (K).prof, (K).tiles, (K).stage, (K).xs, (K).nd, (K).ntd, \
+                               (K).ntiles, (K).stage_cap, (T), (K).skip
+#define TCV_CTX_ARGS(K) TCV_CTX_ARGS_TID(K, (K).tid)
 #define TCV_CTX_FORWARD aP_, aip_, adp_, aW_, ascr_, aimu_, aspill_, aprof_, atiles_, astage_, axs_, and_, antd_, antiles_, astagecap_, atid_, askip_
 // global scratch behind v_s, LDS vectors behind xs: the ONE place that knows the layout (the kernels call these too)
 template <int NT>
@@ -213,7 +251,9 @@ __device__ __forceinline__ void ctx_lds_layout(Ctx<NT> &C, lds_d *xs, int nxl, b
     C.ycam = p; p += camw;
     C.invdiag = p; C.gcam = p; p += camw;
     C.red = p; p += 64;
-    C.flag = (lds_i *)(C.red + 62);   // red[] uses at most 5 * NT/64 = 40 doubles; 40..55 hold the profile build's counters, 56 its last time stamp
+    // red[]: 0..39 the block reductions (at most 5 * NT/64 doubles) and the line costs; 40..55 the trust-region loop's state (LoopState) -- in the
+    // -DTCV_PROFILE build its counters instead, with the last time stamp in 56; 61 the cooperative slot, 62 the flag; 57..60 and 63 are free
+    C.flag = (lds_i *)(C.red + 62);
     C.hd = p;                         // chain mode only (112 doubles)
     C.area = chain ? C.stage + c_stage_cap : p;
 }
@@ -1278,7 +1318,7 @@ __device__ __noinline__ void coop_helper(const SolveArgs &A, lds_d *lds, int g_,
         C.rc = p; C.sd = p + 88; p += 176;
         C.ycam = p; p += 176;
         C.invdiag = p; C.gcam = p; p += 176;
-        C.red = p; p += 64;
+        C.red = p; p += 64;      // (who uses which of the 64: ctx_lds_layout; the helpers run no trust-region loop, 40..55 stay unused here)
         C.flag = (lds_i *)(C.red + 62);
         C.hd = p; p += 112;
         C.area = C.stage + P.c_stage_cap;
@@ -2650,36 +2690,45 @@ __global__ void __launch_bounds__(NT) __attribute__((disable_tail_calls)) __attr
         // workgroup picks the window up.  Like in the reference this makes the iteration count timing dependent; 0 = no limit.
         const long long t_window = (A.max_ticks > 0) ? (long long)wall_clock64() : 0;
         const bool fixed = A.fixed_iterations != 0;
-        double radius = 1e4, mu = 1e-8, lin_mu = 1e-8;
+        // (from here to the end of the window the thread index is formed where it is used: lane_now())
+        const int wave_base = __builtin_amdgcn_readfirstlane(tid & ~63);
+#define TCV_TID (wave_base | lane_now())
+        // (the state block is set up for every window: the previous window's last reads lie in front of the barrier that ends its epilogue)
+        LoopState ls(K.red, TCV_TID);
+        ls.set(LS_RADIUS, 1e4); ls.set(LS_MU, 1e-8); ls.set(LS_LIN_MU, 1e-8);
+        ls.set(LS_GG, 0.0); ls.set(LS_Q, 0.0); ls.set(LS_YG, 0.0); ls.set(LS_GDY, 0.0); ls.set(LS_DY2, 0.0);
         bool reuse = false, tiles_valid = true;
         int invalid = 0, termination = 0, nrec = 1, status = 0;
-#define TCV_COOP_LIN(X, FIRST, ASM, MU) coop_lin(linearize_coop<NT>(TCV_CTX_ARGS(K), C.cx_ctl, C.cx_x, C.cx_exp, C.cx_h, C.cx_exp_stride, C.cx_seq, C.cx_timeout, X, FIRST, ASM, MU, win))
+#define TCV_COOP_LIN(X, FIRST, ASM, MU) coop_lin(linearize_coop<NT>(TCV_CTX_ARGS_TID(K, TCV_TID), C.cx_ctl, C.cx_x, C.cx_exp, C.cx_h, C.cx_exp_stride, C.cx_seq, C.cx_timeout, X, FIRST, ASM, MU, win))
         auto coop_lin = [&](const CoopLin &r) -> double { C.cx_seq = __builtin_amdgcn_readfirstlane(r.seq); return r.cost; };      // the master's sequence number lives in the kernel
-        double cost = uni_d(COOP ? TCV_COOP_LIN(K.xs, true, true, mu) : linearize<NT, CHAIN, TD>(TCV_CTX_ARGS(K), K.xs, true, true, mu));
+        {
+            const double cost = uni_d(COOP ? TCV_COOP_LIN(K.xs, true, true, 1e-8) : linearize<NT, CHAIN, TD>(TCV_CTX_ARGS_TID(K, TCV_TID), K.xs, true, true, 1e-8));
+            ls.set(LS_COST, cost);
+            if (TCV_TID == 0) { S->cost[0] = cost; S->step_ok[0] = 1; S->dogleg_case[0] = 0; S->radius[0] = 1e4; S->mu[0] = 1e-8; S->initial_cost = cost; }
+        }
         bool first = true;
-        const double initial_cost = cost;
-        if (tid == 0) { S->cost[0] = cost; S->step_ok[0] = 1; S->dogleg_case[0] = 0; S->radius[0] = radius; S->mu[0] = mu; }
-        double gg = 0, q = 0, alpha = 0, yg = 0, gdy = 0, dy2 = 0;
         // |x| and |x+ - x| in ambient space feed the parameter-tolerance test only: with the convergence tests off (fixed iterations) nothing
         // reads them, and the three reductions per iteration are not run
-        double xn2 = 0.0, dn2 = 0.0;
-        if (!fixed) { const Norms2 nn = ambient_norms<NT>(TCV_CTX_ARGS(K), K.xs, K.xs); xn2 = uni_d(nn.xn2); dn2 = uni_d(nn.dn2); }
-        double x_norm = uni_d(sqrt(xn2));
+        {
+            double xn2 = 0.0;
+            if (!fixed) { const Norms2 nn = ambient_norms<NT>(TCV_CTX_ARGS_TID(K, TCV_TID), K.xs, K.xs); xn2 = uni_d(nn.xn2); }
+            ls.set(LS_XNORM, sqrt(xn2));
+        }
         bool done = false;
         if (COOP && C.cx_seq < 0) { done = true; status = -9; termination = 5; }      // the helpers did not answer (timeout)
         if (!fixed && !done) {
-            const double gm = grad_max<NT>(TCV_CTX_ARGS(K));
+            const double gm = uni_d(grad_max<NT>(TCV_CTX_ARGS_TID(K, TCV_TID)));
             if (gm <= 1e-10) { termination = 1; done = true; }
         }
         int it = 0;
         while (!done) {
             if (it >= max_it) break;
             if (A.max_ticks > 0) {      // uniform decision: lane 0 of wave 0 reads the clock, everybody follows
-                if (tid == 0) *K.flag = ((long long)wall_clock64() - t_window > A.max_ticks) ? 7 : 0;
+                if (TCV_TID == 0) *K.flag = ((long long)wall_clock64() - t_window > A.max_ticks) ? 7 : 0;
                 __syncthreads();
-                const int over = *K.flag;
+                const int over = __builtin_amdgcn_readfirstlane(*K.flag);
                 __syncthreads();
-                if (tid == 0) *K.flag = 0;
+                if (TCV_TID == 0) *K.flag = 0;
                 if (over) break;
             }
             it++;
@@ -2687,34 +2736,39 @@ __global__ void __launch_bounds__(NT) __attribute__((disable_tail_calls)) __attr
             if (!reuse) {
                 reuse = true;
                 ls_ok = false;
-                while (mu < 1.0) {
-                    if (!tiles_valid || lin_mu != mu) {
-                        if (COOP) (void)TCV_COOP_LIN(K.xs, false, true, mu); else (void)linearize<NT, CHAIN, TD>(TCV_CTX_ARGS(K), K.xs, false, true, mu);
+                while (ls.get(LS_MU) < 1.0) {
+                    if (!tiles_valid || ls.get(LS_LIN_MU) != ls.get(LS_MU)) {
+                        const double mu = ls.get(LS_MU);
+                        if (COOP) (void)TCV_COOP_LIN(K.xs, false, true, mu); else (void)linearize<NT, CHAIN, TD>(TCV_CTX_ARGS_TID(K, TCV_TID), K.xs, false, true, mu);
                         if (COOP && C.cx_seq < 0) break;
-                        lin_mu = mu;
+                        ls.set(LS_LIN_MU, ls.get(LS_MU));
                     }
-                    const FinOut fo = finalize_and_solve<NT, MFMA, CHAIN>(TCV_CTX_ARGS(K), first, mu);
-                    const bool ok = fo.ok;
-                    gg = uni_d(fo.gg); q = uni_d(fo.q);
+                    const FinOut fo = finalize_and_solve<NT, MFMA, CHAIN>(TCV_CTX_ARGS_TID(K, TCV_TID), first, ls.get(LS_MU));
+                    // (what a phase returns arrives in VGPRs: a branch on it counts as divergent, and every counter and flag the loop changes behind
+                    // it -- it, nrec, invalid, termination, reuse -- becomes a per-lane value that goes to scratch memory around the calls.  The
+                    // conditions are uniform: read through the first lane they stay scalar.  The same for grad_max and the clock flag.)
+                    const bool ok = __builtin_amdgcn_readfirstlane((int)fo.ok) != 0;
+                    ls.set(LS_GG, uni_d(fo.gg)); ls.set(LS_Q, uni_d(fo.q));
                     first = false;
                     tiles_valid = false;
                     if (ok) { ls_ok = true; break; }
-                    mu = uni_d(mu * 10.0);
+                    const double mu10 = uni_d(ls.get(LS_MU) * 10.0);
+                    ls.sync();      // (a wavefront that is ahead must not replace mu before the others have read it)
+                    ls.set(LS_MU, mu10);
                 }
                 if (COOP && C.cx_seq < 0) { status = -9; termination = 5; break; }
                 if (ls_ok && ABL(C, AB_DOGLEG)) {
-                    alpha = uni_d(gg / q);
                     // dot products for the dogleg interpolation and the model decrease
                     double acc[3] = {0.0, 0.0, 0.0};
-                    for (int i = tid; i < nl; i += NT) {
+                    for (int i = TCV_TID; i < nl; i += NT) {
                         // (the scratch vectors by their fixed offsets behind v_s: one base pointer live across the calls instead of five)
                         const double y = (K.v_s + 4 * SCR_NL)[i], D = (K.v_s + 2 * SCR_NL)[i], gh = (K.v_s + 3 * SCR_NL)[i];
                         acc[0] += y * (gh * D);   // y' g_s
                         acc[1] += gh * D * y;     // ghat . (D y) = -ghat . gn
                         acc[2] += (D * y) * (D * y);
                     }
-                    block_sum_n<NT, 3>(acc, K.red, tid);
-                    yg = uni_d(acc[0]); gdy = uni_d(acc[1]); dy2 = uni_d(acc[2]);
+                    block_sum_n<NT, 3>(acc, K.red, TCV_TID);
+                    ls.set(LS_YG, uni_d(acc[0])); ls.set(LS_GDY, uni_d(acc[1])); ls.set(LS_DY2, uni_d(acc[2]));
                 }
             }
             TCV_MARK(C, PH_OTHER);
@@ -2722,6 +2776,9 @@ __global__ void __launch_bounds__(NT) __attribute__((disable_tail_calls)) __attr
             int dcase = 0;
             bool step_valid = false;
             if (ls_ok) {
+                // (read once behind the last call: plain registers as far as the Plus)
+                const double gg = ls.get(LS_GG), q = ls.get(LS_Q), yg = ls.get(LS_YG), gdy = ls.get(LS_GDY), dy2 = ls.get(LS_DY2);
+                const double radius = ls.get(LS_RADIUS), mu = ls.get(LS_MU), alpha = uni_d(gg / q);
                 // traditional dogleg in D-space: gn = -D y, Cauchy = -alpha ghat
                 const double gnorm = sqrt(gg), gn_norm = sqrt(dy2);
                 if (gn_norm <= radius) { ca = 0.0; cb = -1.0; step_norm = gn_norm; dcase = 1; }
@@ -2751,86 +2808,109 @@ __global__ void __launch_bounds__(NT) __attribute__((disable_tail_calls)) __attr
 #endif
             if (!step_valid) {
                 invalid++;
-                if (tid == 0 && nrec < MAX_TRACE) {
-                    S->cost[nrec] = cost; S->step_ok[nrec] = 0; S->dogleg_case[nrec] = -1; S->mu[nrec] = mu;
-                    S->radius[nrec] = radius; S->rho[nrec] = 0; S->model_cost_change[nrec] = model_cost_change;
+                if (TCV_TID == 0 && nrec < MAX_TRACE) {
+                    S->cost[nrec] = ls.get(LS_COST); S->step_ok[nrec] = 0; S->dogleg_case[nrec] = -1; S->mu[nrec] = ls.get(LS_MU);
+                    S->radius[nrec] = ls.get(LS_RADIUS); S->rho[nrec] = 0; S->model_cost_change[nrec] = model_cost_change;
                     S->cost_candidate[nrec] = 0; S->step_norm[nrec] = 0;
                 }
                 nrec++;
                 if (invalid >= 5) { termination = 5; break; }
-                mu = uni_d(mu * 10.0);
+                const double mu10 = uni_d(ls.get(LS_MU) * 10.0);
+                ls.sync();      // (mu was read above, by the dogleg too, with no barrier in between)
+                ls.set(LS_MU, mu10);
                 reuse = false;
                 continue;
             }
             invalid = 0;
+            ls.set(LS_MCC, model_cost_change); ls.set(LS_STEP, step_norm); ls.set(LS_CA, ca); ls.set(LS_CB, cb);
             TCV_MARK(C, PH_DOGLEG);
             // the step p = ca * (ghat / D) + cb * y is formed where it is used, from the vectors finalize_and_solve left behind its barriers:
             // no store of v_p, no barrier and no read-back in front of the Plus
-            if (ABL(C, AB_PLUS)) apply_plus<NT>(TCV_CTX_ARGS(K), K.xs, ca, cb, K.xc);
-            if (A.first_delta && it == 1)
-                for (int i = tid; i < nl; i += NT) { const double pi = dogleg_p(K.v_s, i, ca, cb); A.first_delta[(size_t)win * A.delta_stride + i] = pi * K.v_s[i]; }
+            if (ABL(C, AB_PLUS)) apply_plus<NT>(TCV_CTX_ARGS_TID(K, TCV_TID), K.xs, ca, cb, K.xc);
+            if (A.first_delta && it == 1) {
+                const double ca1 = ls.get(LS_CA), cb1 = ls.get(LS_CB);
+                for (int i = TCV_TID; i < nl; i += NT) { const double pi = dogleg_p(K.v_s, i, ca1, cb1); A.first_delta[(size_t)win * A.delta_stride + i] = pi * K.v_s[i]; }
+            }
             __syncthreads();
             TCV_MARK(C, PH_PLUS);
-            const double mu_next = uni_d(fmax(1e-8, 2.0 * mu / 10.0));
+            // mu_next = max(1e-8, 2 mu / 10) is formed again from mu wherever it is used: mu does not change before the end of the iteration
             const bool want_asm = (it < max_it) || !fixed;
-            const double cost_c = uni_d(COOP ? TCV_COOP_LIN(K.xc, false, want_asm, mu_next) : linearize<NT, CHAIN, TD>(TCV_CTX_ARGS(K), K.xc, false, want_asm, mu_next));
+            {
+                const double mu_next = uni_d(fmax(1e-8, 2.0 * ls.get(LS_MU) / 10.0));
+                const double cost_c = uni_d(COOP ? TCV_COOP_LIN(K.xc, false, want_asm, mu_next) : linearize<NT, CHAIN, TD>(TCV_CTX_ARGS_TID(K, TCV_TID), K.xc, false, want_asm, mu_next));
+                ls.set(LS_COST_C, cost_c);
+            }
             if (COOP && C.cx_seq < 0) { status = -9; termination = 5; break; }
             tiles_valid = want_asm;
-            lin_mu = mu_next;
-            if (!fixed && ABL(C, AB_NORMS)) { const Norms2 nn = ambient_norms<NT>(TCV_CTX_ARGS(K), K.xs, K.xc); xn2 = uni_d(nn.xn2); dn2 = uni_d(nn.dn2); }
+            ls.set(LS_LIN_MU, uni_d(fmax(1e-8, 2.0 * ls.get(LS_MU) / 10.0)));
+            double dn2 = 0.0;
+            if (!fixed && ABL(C, AB_NORMS)) { const Norms2 nn = ambient_norms<NT>(TCV_CTX_ARGS_TID(K, TCV_TID), K.xs, K.xc); dn2 = uni_d(nn.dn2); }
             TCV_MARK(C, PH_NORMS);
+            const double cost = ls.get(LS_COST), cost_c = ls.get(LS_COST_C);
+            {
+                const double mcc = ls.get(LS_MCC);
 #ifdef TCV_ABLATE
-            const double rho = ABL_ACCEPT(C) ? 1.0 : (cost - cost_c) / model_cost_change;
+                const double rho = ABL_ACCEPT(C) ? 1.0 : (cost - cost_c) / mcc;
 #else
-            const double rho = (cost - cost_c) / model_cost_change;
+                const double rho = (cost - cost_c) / mcc;
 #endif
-            if (tid == 0 && nrec < MAX_TRACE) {
-                S->model_cost_change[nrec] = model_cost_change; S->cost_candidate[nrec] = cost_c;
-                S->radius[nrec] = radius; S->mu[nrec] = mu; S->rho[nrec] = rho; S->step_norm[nrec] = step_norm;
-                S->dogleg_case[nrec] = dcase;
+                ls.set(LS_RHO, rho);
+                if (TCV_TID == 0 && nrec < MAX_TRACE) {
+                    S->model_cost_change[nrec] = mcc; S->cost_candidate[nrec] = cost_c;
+                    S->radius[nrec] = ls.get(LS_RADIUS); S->mu[nrec] = ls.get(LS_MU); S->rho[nrec] = rho; S->step_norm[nrec] = ls.get(LS_STEP);
+                    S->dogleg_case[nrec] = dcase;
+                }
             }
-            if (!fixed && sqrt(dn2) <= 1e-8 * (x_norm + 1e-8)) {
-                if (tid == 0 && nrec < MAX_TRACE) { S->cost[nrec] = cost; S->step_ok[nrec] = 0; }
+            if (!fixed && sqrt(dn2) <= 1e-8 * (ls.get(LS_XNORM) + 1e-8)) {
+                if (TCV_TID == 0 && nrec < MAX_TRACE) { S->cost[nrec] = cost; S->step_ok[nrec] = 0; }
                 nrec++; termination = 2; break;
             }
             const double cost_change = cost - cost_c;
             if (!fixed && fabs(cost_change) <= 1e-6 * cost) {
-                if (tid == 0 && nrec < MAX_TRACE) { S->cost[nrec] = cost; S->step_ok[nrec] = 0; }
+                if (TCV_TID == 0 && nrec < MAX_TRACE) { S->cost[nrec] = cost; S->step_ok[nrec] = 0; }
                 nrec++; termination = 3; break;
             }
-            if (rho > 1e-3) {
-                for (int i = tid; i < P.nx + L; i += NT) K.xs[i] = K.xc[i];
-                if (!fixed && ABL(C, AB_NORMS)) { const Norms2 nn = ambient_norms<NT>(TCV_CTX_ARGS(K), K.xc, K.xc); xn2 = uni_d(nn.xn2); dn2 = uni_d(nn.dn2); }
-                x_norm = uni_d(sqrt(xn2));
-                cost = cost_c;
+            // cost, radius and mu change below, and a rejected step goes straight on to the next dogleg (which replaces model_cost_change and
+            // step_norm).  No phase call separates that from this iteration's reads, so the new values are formed first and stored behind
+            // a barrier: every wavefront is through with the old ones by then.
+            if (ls.get(LS_RHO) > 1e-3) {
+                for (int i = TCV_TID; i < P.nx + L; i += NT) K.xs[i] = K.xc[i];
+                double xn2 = 0.0;
+                if (!fixed && ABL(C, AB_NORMS)) { const Norms2 nn = ambient_norms<NT>(TCV_CTX_ARGS_TID(K, TCV_TID), K.xc, K.xc); xn2 = uni_d(nn.xn2); }
+                ls.set(LS_XNORM, uni_d(sqrt(xn2)));
+                const double rho = ls.get(LS_RHO), cost_new = ls.get(LS_COST_C);
+                double radius = ls.get(LS_RADIUS);
                 if (rho < 0.25) radius = uni_d(radius * 0.5);
-                if (rho > 0.75) radius = uni_d(fmax(radius, 3.0 * step_norm));
-                mu = mu_next;
+                if (rho > 0.75) radius = uni_d(fmax(radius, 3.0 * ls.get(LS_STEP)));
+                const double mu_next = uni_d(fmax(1e-8, 2.0 * ls.get(LS_MU) / 10.0));
+                ls.sync();
+                ls.set(LS_COST, cost_new); ls.set(LS_RADIUS, radius); ls.set(LS_MU, mu_next);
                 reuse = false;
-                if (tid == 0 && nrec < MAX_TRACE) { S->cost[nrec] = cost; S->step_ok[nrec] = 1; }
+                if (TCV_TID == 0 && nrec < MAX_TRACE) { S->cost[nrec] = cost_new; S->step_ok[nrec] = 1; }
                 nrec++;
                 if (!fixed) {
-                    const double gm = grad_max<NT>(TCV_CTX_ARGS(K));
+                    const double gm = uni_d(grad_max<NT>(TCV_CTX_ARGS_TID(K, TCV_TID)));
                     if (gm <= 1e-10) { termination = 1; break; }
                 }
             } else {
-                radius = uni_d(radius * 0.5);
+                const double radius = uni_d(ls.get(LS_RADIUS) * 0.5);
+                ls.sync();
+                ls.set(LS_RADIUS, radius);
                 reuse = true;
                 tiles_valid = false;
-                if (tid == 0 && nrec < MAX_TRACE) { S->cost[nrec] = cost; S->step_ok[nrec] = 0; }
+                if (TCV_TID == 0 && nrec < MAX_TRACE) { S->cost[nrec] = cost; S->step_ok[nrec] = 0; }
                 nrec++;
             }
-            if (radius < 1e-32) { termination = 4; break; }
+            if (ls.get(LS_RADIUS) < 1e-32) { termination = 4; break; }
         }
         __syncthreads();
-        if (A.gauge_fix) gauge_epilogue<NT>(K.xs, K.dp + W->d_x, K.ip + P.o_frames, P.n_frames, tid);
-        for (int i = tid; i < P.nx + L; i += NT) A.state_out[(size_t)win * A.state_stride + i] = K.xs[i];
-        if (tid == 0) {
+        if (A.gauge_fix) gauge_epilogue<NT>(K.xs, K.dp + W->d_x, K.ip + P.o_frames, P.n_frames, TCV_TID);
+        for (int i = TCV_TID; i < P.nx + L; i += NT) A.state_out[(size_t)win * A.state_stride + i] = K.xs[i];
+        if (TCV_TID == 0) {
             S->num_iterations = nrec;
             S->termination = termination;
             S->status = status;
-            S->initial_cost = initial_cost;
-            S->final_cost = cost;
+            S->final_cost = ls.get(LS_COST);      // (initial_cost: stored with the first record)
         }
         __syncthreads();
         TCV_MARK(C, PH_OTHER);
@@ -2840,6 +2920,7 @@ __global__ void __launch_bounds__(NT) __attribute__((disable_tail_calls)) __attr
         __syncthreads();
 #endif
     }
+#undef TCV_TID
     if (COOP && C.cx_seq >= 0) {      // the helpers of this group leave with the master
         __syncthreads();
         coop_publish<NT>(C, nullptr, 0, 0.0, COOP_CMD_EXIT, 0, C.cx_seq + 1);
