@@ -149,8 +149,7 @@ extern "C" int tcv_vi_align(int n, const tcv_vi_align_desc *descs, const tcv_vi_
         std::memset(r.delta_bg, 0, sizeof r.delta_bg); std::memset(r.bg, 0, sizeof r.bg); std::memset(r.gravity_c0, 0, sizeof r.gravity_c0);
         std::memset(r.gravity, 0, sizeof r.gravity); std::memset(r.rot_diff, 0, sizeof r.rot_diff);
     }
-    if (hip_stream == TCV_STREAM_THREAD) hip_stream = (void *)util_stream();
-    hipStream_t st = (hipStream_t)hip_stream;
+    hipStream_t st = resolve_stream(hip_stream);
     const size_t b_hdr = sizeof(AlignHdr) * (size_t)n, b_R = 72 * (size_t)n_frames, b_T = 24 * (size_t)n_frames;
     g_al_timing[0] += ms_since(t0);
 

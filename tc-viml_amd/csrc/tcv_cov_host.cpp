@@ -39,7 +39,7 @@ struct LmState {
     std::vector<int> rq;                            // host copy of the request tables (first solved column of every block per window)
     std::vector<std::vector<int>> plan_of;          // per window: plan index of the l-th landmark in registration order
 };
-struct CovState {
+struct CovState : tcv::SideState {
     PlanTable tab;              // the owner lists of every plan
     void *d_work = nullptr;     // [staging | y] per workgroup
     ResultBuf res;              // doubles: the blocks
@@ -47,15 +47,12 @@ struct CovState {
     long long stage_stride = 0;
     int grid = 0, nc_max = 0;
     LmState lm;
+    ~CovState() override {
+        tcv::dev_free(tab.d); tcv::dev_free(d_work); tcv::dev_free(res.d);
+        tcv::dev_free(lm.tab.d); tcv::dev_free(lm.d_ylm); tcv::dev_free(lm.res.d);
+    }
 };
-void cov_free(tcv_batch *b) {
-    CovState *s = (CovState *)b->cov;
-    if (!s) return;
-    tcv::dev_free(s->tab.d); tcv::dev_free(s->d_work); tcv::dev_free(s->res.d);
-    tcv::dev_free(s->lm.tab.d); tcv::dev_free(s->lm.d_ylm); tcv::dev_free(s->lm.res.d);
-    delete s;
-    b->cov = nullptr;
-}
+CovState *cov_of(const tcv_batch *b) { return static_cast<CovState *>(b->cov.get()); }
 // what both calls ask of their options
 int check_options(const tcv_covariance_options *o, const char *who) {
     if (!(o->min_relative_pivot >= 0.0) || !std::isfinite(o->min_relative_pivot)) { set_error(std::string(who) + ": min_relative_pivot must be finite and >= 0"); return TCV_ERR_INVALID; }
@@ -96,24 +93,23 @@ std::vector<tcv_covariance_block> diagonal_requests(const tcv_landmark_cross_blo
 int cov_prepare(tcv_batch *b) {
     if (b->cov) return TCV_OK;
     std::unique_ptr<CovState> s(new CovState());
-    for (auto &H : b->plans) {
+    for (auto &H : b->in.plans) {
         if (H.nc > TCV_COVARIANCE_MAX_DIM) { set_error("covariance: more than TCV_COVARIANCE_MAX_DIM camera-side tangent dimensions"); return TCV_ERR_UNSUPPORTED; }
         s->nc_max = std::max(s->nc_max, H.nc);
     }
     auto entry = [&](int w, std::vector<int> &out) -> int {
-        const PlanHdr &H = b->plans[b->wins[w].plan];
+        const PlanHdr &H = b->in.plans[b->in.wins[w].plan];
         int jd = 0;
-        if (int rc = cov_owner_lists(*b->problems[w], b->packed[w], H, out, &jd)) return rc;
+        if (int rc = cov_owner_lists(*b->in.problems[w], b->in.packed[w], H, out, &jd)) return rc;
         s->stage_stride = std::max<long long>(s->stage_stride, ((long long)H.n_imu * (225 + IMU_REC) + jd + 1) & ~1LL);
         return TCV_OK;
     };
     if (int rc = plan_table_create(b, entry, "hipMalloc (covariance buffers)", "upload of the covariance tables", &s->tab)) return rc;
-    s->grid = std::min(b->n, std::max(1, b->n_cu));      // one workgroup per CU (LDS): a persistent grid walks the batch
+    s->grid = std::min(b->in.n, std::max(1, b->shape.n_cu));      // one workgroup per CU (LDS): a persistent grid walks the batch
     const size_t work = sizeof(double) * (size_t)s->grid * ((size_t)s->stage_stride + (size_t)COV_MAX_DIM * COV_MAX_DIM);
     if (hipError_t e = tcv::dev_malloc(&s->d_work, work)) { tcv::dev_free(s->tab.d); return hip_fail(e, "hipMalloc (covariance buffers)"); }
     s->d_stage = (double *)s->d_work; s->d_y = s->d_stage + (size_t)s->grid * s->stage_stride;
-    b->cov = s.release();
-    b->cov_free = cov_free;
+    b->cov = std::move(s);
     return TCV_OK;
 }
 // the plan index of every landmark in registration order: the landmarks of a problem are the fourth blocks of its point factors, the
@@ -130,8 +126,8 @@ int lm_prepare(tcv_batch *b, CovState *s) {
     LmState &m = s->lm;
     if (m.ready) return TCV_OK;
     auto entry = [&](int w, std::vector<int> &out) -> int {
-        const tcv_problem &p = *b->problems[w];
-        out = cov_slot_table(p, b->packed[w], cov_landmark_slots(p, b->packed[w], b->plans[b->wins[w].plan]));
+        const tcv_problem &p = *b->in.problems[w];
+        out = cov_slot_table(p, b->in.packed[w], cov_landmark_slots(p, b->in.packed[w], b->in.plans[b->in.wins[w].plan]));
         return TCV_OK;
     };
     PlanTable tab;
@@ -139,9 +135,9 @@ int lm_prepare(tcv_batch *b, CovState *s) {
     void *d_ylm = nullptr;
     if (hipError_t e = tcv::dev_malloc(&d_ylm, sizeof(double) * (size_t)s->grid * COV_MAX_DIM * COV_LM_CHUNK)) { tcv::dev_free(tab.d); return hip_fail(e, "hipMalloc (landmark covariance buffers)"); }
     m.tab = tab; m.d_ylm = d_ylm;
-    m.plan_of.resize(b->n);
+    m.plan_of.resize(b->in.n);
     m.lmax = 0;
-    for (int w = 0; w < b->n; w++) { m.plan_of[w] = registration_order(b->packed[w]); m.lmax = std::max(m.lmax, (int)m.plan_of[w].size()); }
+    for (int w = 0; w < b->in.n; w++) { m.plan_of[w] = registration_order(b->in.packed[w]); m.lmax = std::max(m.lmax, (int)m.plan_of[w].size()); }
     m.ready = true;
     return TCV_OK;
 }
@@ -153,7 +149,7 @@ bool same_requests(const ResultBuf &r, const tcv_covariance_block *blocks, int n
 }
 // a new result buffer [rq | status | `doubles` doubles] replaces the old one: the request tables go up; `zero`: status and doubles are cleared
 int result_replace(tcv_batch *b, ResultBuf &r, const std::vector<int> &rq, size_t doubles, bool zero, const std::string &what) {
-    const size_t rq_bytes = (sizeof(int) * rq.size() + 7) & ~(size_t)7, st_bytes = (sizeof(int) * (size_t)b->n + 7) & ~(size_t)7, tail = st_bytes + sizeof(double) * doubles;
+    const size_t rq_bytes = (sizeof(int) * rq.size() + 7) & ~(size_t)7, st_bytes = (sizeof(int) * (size_t)b->in.n + 7) & ~(size_t)7, tail = st_bytes + sizeof(double) * doubles;
     void *d = nullptr;
     hipError_t e = tcv::dev_malloc(&d, rq_bytes + tail);
     if (e != hipSuccess) return hip_fail(e, ("hipMalloc (" + what + " results)").c_str());
@@ -163,7 +159,7 @@ int result_replace(tcv_batch *b, ResultBuf &r, const std::vector<int> &rq, size_
         if (e == hipSuccess) e = hipStreamSynchronize(tcv::util_stream());
         if (e != hipSuccess) rc = hip_fail(e, ("hipMemset (" + what + " results)").c_str());
     }
-    if (rc == TCV_OK && b->pending) rc = tcv_batch_synchronize(b);      // a computation in flight still writes the old buffers
+    if (rc == TCV_OK) rc = b->settle();      // a computation in flight still writes the old buffers
     if (rc != TCV_OK) { tcv::dev_free(d); return rc; }
     tcv::dev_free(r.d);
     r.d = d; r.rq = (int *)d; r.status = (int *)((char *)d + rq_bytes); r.out = (double *)((char *)d + rq_bytes + st_bytes);
@@ -175,7 +171,7 @@ int result_replace(tcv_batch *b, ResultBuf &r, const std::vector<int> &rq, size_
 int new_requests(tcv_batch *b, CovState *s, bool landmarks, const tcv_covariance_block *blocks, int n_req) {
     LmState &m = s->lm;
     ResultBuf &r = landmarks ? m.res : s->res;
-    const size_t n = b->n, stride = cov_rq_stride(n_req);
+    const size_t n = b->in.n, stride = cov_rq_stride(n_req);
     std::vector<int> rq, rows, cols;
     if (int rc = cov_request_tables(b, blocks, n_req, rq, rows, cols)) return rc;
     int mstride = 0;
@@ -189,31 +185,31 @@ int new_requests(tcv_batch *b, CovState *s, bool landmarks, const tcv_covariance
 }
 // either call behind its own argument checks: prepare, tables, launch
 int compute(tcv_batch *b, const tcv_covariance_options *o, bool landmarks, const tcv_covariance_block *blocks, int n_req, void *hip_stream, const char *who) {
-    if (o->at_solution && !b->solved) { set_error(std::string(who) + ": at_solution = 1, but the batch has not been solved"); return TCV_ERR_INVALID; }
-    for (int w = 0; w < b->n; w++) if (int rc = check_requests(*b->problems[w], blocks, n_req)) return rc;
-    if (hip_stream == TCV_STREAM_THREAD) hip_stream = (void *)tcv::util_stream();
+    if (o->at_solution && !b->last.solved) { set_error(std::string(who) + ": at_solution = 1, but the batch has not been solved"); return TCV_ERR_INVALID; }
+    for (int w = 0; w < b->in.n; w++) if (int rc = check_requests(*b->in.problems[w], blocks, n_req)) return rc;
+    hip_stream = (void *)tcv::resolve_stream(hip_stream);
     if (int rc = cov_prepare(b)) return rc;
-    CovState *s = (CovState *)b->cov;
+    CovState *s = cov_of(b);
     if (landmarks) if (int rc = lm_prepare(b, s)) return rc;
     const LmState &m = s->lm;
     ResultBuf &r = landmarks ? s->lm.res : s->res;
     if (!same_requests(r, blocks, n_req)) if (int rc = new_requests(b, s, landmarks, blocks, n_req)) return rc;
     CovArgs a;
     std::memset(&a, 0, sizeof a);
-    a.win = b->d_win; a.plans = b->d_plans; a.plan_base = b->d_plan_base; a.ipool = b->d_ipool; a.dpool = b->d_dpool;
-    a.state = o->at_solution ? b->d_state : nullptr;
+    a.win = b->mem.d_win; a.plans = b->mem.d_plans; a.plan_base = b->mem.d_plan_base; a.ipool = b->mem.d_ipool; a.dpool = b->mem.d_dpool;
+    a.state = o->at_solution ? b->mem.d_state : nullptr;
     a.tab_base = s->tab.base; a.tab = s->tab.ints; a.rq = r.rq;
     a.stage = s->d_stage; a.ybuf = s->d_y; a.out = r.out; a.status = r.status;
     a.stage_stride = s->stage_stride;
-    a.nwin = b->n; a.state_stride = b->state_stride; a.rq_stride = cov_rq_stride(n_req); a.n_req = n_req;
-    a.apply_loss = o->apply_loss_function ? 1 : 0; a.lds_area = cov_lds_area(b->state_stride, s->nc_max);
+    a.nwin = b->in.n; a.state_stride = b->in.state_stride; a.rq_stride = cov_rq_stride(n_req); a.n_req = n_req;
+    a.apply_loss = o->apply_loss_function ? 1 : 0; a.lds_area = cov_lds_area(b->in.state_stride, s->nc_max);
     a.min_relative_pivot = o->min_relative_pivot;
     if (landmarks) {
         a.ltab_base = m.tab.base; a.ltab = m.tab.ints; a.ylm = (double *)m.d_ylm;
         a.lm_var = m.d_var; a.lm_cross = m.d_cross; a.lm_lmax = m.lmax; a.lm_mstride = m.mstride;
     }
-    if (int rc = tcv_batch_enter_stream(b, hip_stream)) return rc;
-    const int rc = tcv_launch_covariance(&a, s->grid, sizeof(double) * (size_t)cov_lds_doubles(b->state_stride, s->nc_max), hip_stream, landmarks);
+    if (int rc = b->flight.enter((hipStream_t)hip_stream)) return rc;
+    const int rc = tcv_launch_covariance(&a, s->grid, sizeof(double) * (size_t)cov_lds_doubles(b->in.state_stride, s->nc_max), hip_stream, landmarks);
     if (rc != 0) return hip_fail((hipError_t)rc, landmarks ? "landmark covariance kernel launch" : "covariance kernel launch");
     r.computed = true;
     return TCV_OK;
@@ -221,13 +217,12 @@ int compute(tcv_batch *b, const tcv_covariance_options *o, bool landmarks, const
 // the getters' gate: the call has been made, and its results are complete
 int computed(tcv_batch *b, bool landmarks, const char *who) {
     if (!b) { set_error(std::string(who) + ": null batch"); return TCV_ERR_INVALID; }
-    const CovState *s = (const CovState *)b->cov;
+    const CovState *s = cov_of(b);
     if (!s || !(landmarks ? s->lm.res : s->res).computed) {
         set_error(std::string(who) + (landmarks ? ": no landmark covariance has been computed on the batch" : ": no covariance has been computed on the batch"));
         return TCV_ERR_INVALID;
     }
-    if (b->pending) return tcv_batch_synchronize(b);
-    return TCV_OK;
+    return b->settle();
 }
 // one problem at the caller's current block values: a one-window batch on the calling thread's stream, destroyed on every path
 template <class Body> int one_window_batch(tcv_problem *p, Body &&body) {
@@ -256,9 +251,9 @@ extern "C" int tcv_batch_compute_covariance(tcv_batch *b, const tcv_covariance_o
 }
 extern "C" int tcv_batch_get_covariance(tcv_batch *b, int window, int k, double *out, int cap, int *rows, int *cols) {
     if (int rc = computed(b, false, "batch_get_covariance")) return rc;
-    const ResultBuf &r = ((CovState *)b->cov)->res;
+    const ResultBuf &r = cov_of(b)->res;
     const int n_req = (int)r.req.size();
-    if (window < 0 || window >= b->n || k < 0 || k >= n_req) { set_error("batch_get_covariance: window or block out of range"); return TCV_ERR_INVALID; }
+    if (window < 0 || window >= b->in.n || k < 0 || k >= n_req) { set_error("batch_get_covariance: window or block out of range"); return TCV_ERR_INVALID; }
     const int nel = r.rows[k] * r.cols[k];
     if (!out || cap < nel) { set_error("batch_get_covariance: the output array is missing or too small"); return TCV_ERR_INVALID; }
     double h[COV_BLOCK_DOUBLES];
@@ -270,8 +265,8 @@ extern "C" int tcv_batch_get_covariance(tcv_batch *b, int window, int k, double 
 }
 extern "C" int tcv_batch_get_covariance_all(tcv_batch *b, int k, double *out, int cap, int *rows, int *cols) {
     if (int rc = computed(b, false, "batch_get_covariance_all")) return rc;
-    const ResultBuf &r = ((CovState *)b->cov)->res;
-    const int n_req = (int)r.req.size(), n = b->n;
+    const ResultBuf &r = cov_of(b)->res;
+    const int n_req = (int)r.req.size(), n = b->in.n;
     if (k < 0 || k >= n_req) { set_error("batch_get_covariance_all: block out of range"); return TCV_ERR_INVALID; }
     const int nel = r.rows[k] * r.cols[k];
     if (!out || (long long)cap < (long long)nel * n) { set_error("batch_get_covariance_all: the output array is missing or too small"); return TCV_ERR_INVALID; }
@@ -283,9 +278,9 @@ extern "C" int tcv_batch_get_covariance_all(tcv_batch *b, int k, double *out, in
     return TCV_OK;
 }
 extern "C" int tcv_batch_covariance_status(tcv_batch *b, int *out, int n) {
-    if (b && (!out || n != b->n)) { set_error("batch_covariance_status: n must be the batch size"); return TCV_ERR_INVALID; }
+    if (b && (!out || n != b->in.n)) { set_error("batch_covariance_status: n must be the batch size"); return TCV_ERR_INVALID; }
     if (int rc = computed(b, false, "batch_covariance_status")) return rc;
-    return tcv::staged_download(out, ((CovState *)b->cov)->res.status, sizeof(int) * (size_t)n, "download of the covariance status");
+    return tcv::staged_download(out, cov_of(b)->res.status, sizeof(int) * (size_t)n, "download of the covariance status");
 }
 // ceres::Covariance for one problem at the caller's current block values
 extern "C" int tcv_problem_compute_covariance(tcv_problem *p, const tcv_covariance_options *o, const tcv_covariance_block *blocks, int n_blocks,
@@ -326,14 +321,14 @@ extern "C" int tcv_batch_compute_landmark_covariance(tcv_batch *b, const tcv_cov
 }
 extern "C" int tcv_batch_landmark_covariance_dims(tcv_batch *b, int window, int *n_landmarks) {
     if (!b || !n_landmarks) { set_error("batch_landmark_covariance_dims: null batch or output"); return TCV_ERR_INVALID; }
-    if (window < 0 || window >= b->n) { set_error("batch_landmark_covariance_dims: window out of range"); return TCV_ERR_INVALID; }
-    *n_landmarks = (int)b->packed[window].lm_block.size();
+    if (window < 0 || window >= b->in.n) { set_error("batch_landmark_covariance_dims: window out of range"); return TCV_ERR_INVALID; }
+    *n_landmarks = (int)b->in.packed[window].lm_block.size();
     return TCV_OK;
 }
 extern "C" int tcv_batch_get_landmark_variances(tcv_batch *b, int window, double *out, int cap, int *n) {
     if (int rc = computed(b, true, "batch_get_landmark_variances")) return rc;
-    const LmState &m = ((CovState *)b->cov)->lm;
-    if (window < 0 || window >= b->n) { set_error("batch_get_landmark_variances: window out of range"); return TCV_ERR_INVALID; }
+    const LmState &m = cov_of(b)->lm;
+    if (window < 0 || window >= b->in.n) { set_error("batch_get_landmark_variances: window out of range"); return TCV_ERR_INVALID; }
     const std::vector<int> &po = m.plan_of[window];
     const int L = (int)po.size();
     if (!out || cap < L) { set_error("batch_get_landmark_variances: the output array is missing or too small"); return TCV_ERR_INVALID; }
@@ -345,12 +340,12 @@ extern "C" int tcv_batch_get_landmark_variances(tcv_batch *b, int window, double
 }
 extern "C" int tcv_batch_get_landmark_variances_all(tcv_batch *b, double *out, int cap, int *stride) {
     if (int rc = computed(b, true, "batch_get_landmark_variances_all")) return rc;
-    const LmState &m = ((CovState *)b->cov)->lm;
-    const size_t nel = (size_t)b->n * m.lmax;
+    const LmState &m = cov_of(b)->lm;
+    const size_t nel = (size_t)b->in.n * m.lmax;
     if (!out || (long long)cap < (long long)nel) { set_error("batch_get_landmark_variances_all: the output array is missing or too small"); return TCV_ERR_INVALID; }
     std::vector<double> h(nel);
     if (nel > 0) if (int rc = tcv::staged_download(h.data(), m.d_var, sizeof(double) * nel, "download of the landmark variances")) return rc;
-    for (int w = 0; w < b->n; w++) {
+    for (int w = 0; w < b->in.n; w++) {
         const std::vector<int> &po = m.plan_of[w];
         double *o = out + (size_t)w * m.lmax;
         for (int l = 0; l < m.lmax; l++) o[l] = l < (int)po.size() ? h[(size_t)w * m.lmax + po[l]] : 0.0;
@@ -360,9 +355,9 @@ extern "C" int tcv_batch_get_landmark_variances_all(tcv_batch *b, double *out, i
 }
 extern "C" int tcv_batch_get_landmark_cross(tcv_batch *b, int window, int k, double *out, int cap, int *rows, int *cols) {
     if (int rc = computed(b, true, "batch_get_landmark_cross")) return rc;
-    const LmState &m = ((CovState *)b->cov)->lm;
+    const LmState &m = cov_of(b)->lm;
     const int n_cross = (int)m.res.req.size();
-    if (window < 0 || window >= b->n || k < 0 || k >= n_cross) { set_error("batch_get_landmark_cross: window or cross block out of range"); return TCV_ERR_INVALID; }
+    if (window < 0 || window >= b->in.n || k < 0 || k >= n_cross) { set_error("batch_get_landmark_cross: window or cross block out of range"); return TCV_ERR_INVALID; }
     const std::vector<int> &po = m.plan_of[window];
     const int L = (int)po.size(), wk = m.res.cols[k];
     if (!out || (long long)cap < (long long)L * wk) { set_error("batch_get_landmark_cross: the output array is missing or too small"); return TCV_ERR_INVALID; }
@@ -376,9 +371,9 @@ extern "C" int tcv_batch_get_landmark_cross(tcv_batch *b, int window, int k, dou
     return TCV_OK;
 }
 extern "C" int tcv_batch_landmark_covariance_status(tcv_batch *b, int *out, int n) {
-    if (b && (!out || n != b->n)) { set_error("batch_landmark_covariance_status: n must be the batch size"); return TCV_ERR_INVALID; }
+    if (b && (!out || n != b->in.n)) { set_error("batch_landmark_covariance_status: n must be the batch size"); return TCV_ERR_INVALID; }
     if (int rc = computed(b, true, "batch_landmark_covariance_status")) return rc;
-    return tcv::staged_download(out, ((CovState *)b->cov)->lm.res.status, sizeof(int) * (size_t)n, "download of the landmark covariance status");
+    return tcv::staged_download(out, cov_of(b)->lm.res.status, sizeof(int) * (size_t)n, "download of the landmark covariance status");
 }
 // one problem at the caller's current block values; the landmarks by address
 extern "C" int tcv_problem_compute_landmark_covariance(tcv_problem *p, const tcv_covariance_options *o, double *const *inv_depth_addresses, int n,

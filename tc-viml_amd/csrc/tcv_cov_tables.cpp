@@ -174,11 +174,11 @@ std::vector<int> cov_slot_table(const tcv_problem &p, const Packed &pk, const Co
     return lt;
 }
 int cov_request_tables(const tcv_batch *b, const tcv_covariance_block *blocks, int n_req, std::vector<int> &rq, std::vector<int> &rows, std::vector<int> &cols) {
-    const int n = b->n, stride = cov_rq_stride(n_req);
+    const int n = b->in.n, stride = cov_rq_stride(n_req);
     rq.assign((size_t)n * stride, 0); rows.assign(n_req, 0); cols.assign(n_req, 0);
     for (int w = 0; w < n; w++) {
-        const tcv_problem &p = *b->problems[w];
-        const BlockMap map(p, b->packed[w]);
+        const tcv_problem &p = *b->in.problems[w];
+        const BlockMap map(p, b->in.packed[w]);
         int *q = rq.data() + (size_t)w * stride, m = 0;
         std::map<int, int> col_of;      // first tangent index of a block -> its first solved column
         auto column = [&](int blk, int width) -> int {

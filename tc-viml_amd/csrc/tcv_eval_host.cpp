@@ -15,29 +15,24 @@ using namespace tcv;
 // =====================================================================================================
 extern "C" int tcv_launch_evaluate(const tcv::EvalArgs *args, size_t lds_bytes, void *stream);
 namespace {
-struct EvalState {
+struct EvalState : tcv::SideState {
     PlanTable tab;              // the owner lists of every plan
     void *d_out = nullptr;      // [scalars | residuals | block costs | gradient | staging], per window each
     double *d_scal = nullptr, *d_res = nullptr, *d_blk = nullptr, *d_grad = nullptr, *d_stage = nullptr;
     int res_stride = 0, blk_stride = 0, grad_stride = 0, stage_stride = 0;
     bool evaluated = false;
     tcv_evaluate_options last;
+    ~EvalState() override { tcv::dev_free(tab.d); tcv::dev_free(d_out); }
 };
+EvalState *eval_of(const tcv_batch *b) { return static_cast<EvalState *>(b->eval.get()); }
 }  // namespace
-void tcv_eval_free(tcv_batch *b) {
-    EvalState *s = (EvalState *)b->eval;
-    if (!s) return;
-    tcv::dev_free(s->tab.d); tcv::dev_free(s->d_out);
-    delete s;
-    b->eval = nullptr;
-}
 // Owner lists of the gradient for the plan of window w (tcv_eval.h): per tangent index (camera tangent space, then the landmarks) the
 // offsets of its J'r pieces in the window's piece region, in factor order -- prior, IMU, point (plan order), line.  A function of the
 // plan's tables alone (block table, factor tables, prior columns), rebuilt here from the problem the plan was packed from.
 static void eval_owner_lists(const tcv_batch *b, int w, std::vector<int> &out) {
-    const tcv_problem &p = *b->problems[w];
-    const Packed &pk = b->packed[w];
-    const PlanHdr &H = b->plans[b->wins[w].plan];
+    const tcv_problem &p = *b->in.problems[w];
+    const Packed &pk = b->in.packed[w];
+    const PlanHdr &H = b->in.plans[b->in.wins[w].plan];
     const int nl = H.nc + H.nland;
     const BlockMap map(p, pk);
     std::vector<std::vector<int>> own(nl);
@@ -82,19 +77,19 @@ static void eval_owner_lists(const tcv_batch *b, int w, std::vector<int> &out) {
 static int eval_prepare(tcv_batch *b) {
     if (b->eval) return TCV_OK;
     std::unique_ptr<EvalState> s(new EvalState());
-    const int n = b->n;
-    for (auto &H : b->plans) {
+    const int n = b->in.n;
+    for (auto &H : b->in.plans) {
         s->res_stride = std::max(s->res_stride, eval_num_residuals(H)); s->blk_stride = std::max(s->blk_stride, eval_num_blocks(H));
         s->stage_stride = std::max(s->stage_stride, (eval_stage_doubles(H) + 1) & ~1);
     }
-    s->res_stride = (s->res_stride + 1) & ~1; s->blk_stride = (s->blk_stride + 1) & ~1; s->grad_stride = b->delta_stride;
+    s->res_stride = (s->res_stride + 1) & ~1; s->blk_stride = (s->blk_stride + 1) & ~1; s->grad_stride = b->in.delta_stride;
     const size_t per_win = (size_t)EV_SCALARS + s->res_stride + s->blk_stride + s->grad_stride + s->stage_stride;
     if (int rc = plan_table_create(b, [&](int w, std::vector<int> &out) { eval_owner_lists(b, w, out); return (int)TCV_OK; },
                                    "hipMalloc (evaluation buffers)", "upload of the evaluation tables", &s->tab)) return rc;
     if (hipError_t e = tcv::dev_malloc(&s->d_out, sizeof(double) * per_win * (size_t)n)) { tcv::dev_free(s->tab.d); return hip_fail(e, "hipMalloc (evaluation buffers)"); }
     s->d_scal = (double *)s->d_out; s->d_res = s->d_scal + (size_t)n * EV_SCALARS; s->d_blk = s->d_res + (size_t)n * s->res_stride;
     s->d_grad = s->d_blk + (size_t)n * s->blk_stride; s->d_stage = s->d_grad + (size_t)n * s->grad_stride;
-    b->eval = s.release();
+    b->eval = std::move(s);
     return TCV_OK;
 }
 extern "C" void tcv_evaluate_options_default(tcv_evaluate_options *o) {
@@ -107,62 +102,61 @@ extern "C" void tcv_evaluate_options_default(tcv_evaluate_options *o) {
 extern "C" int tcv_batch_evaluate(tcv_batch *b, const tcv_evaluate_options *o, void *hip_stream) {
     if (!b || !o) { set_error("batch_evaluate: null batch or options"); return TCV_ERR_INVALID; }
     if (o->at != TCV_EVALUATE_AT_INITIAL && o->at != TCV_EVALUATE_AT_SOLUTION) { set_error("batch_evaluate: options.at must be TCV_EVALUATE_AT_INITIAL or TCV_EVALUATE_AT_SOLUTION"); return TCV_ERR_INVALID; }
-    if (o->at == TCV_EVALUATE_AT_SOLUTION && !b->solved) { set_error("batch_evaluate: at = solution, but the batch has not been solved"); return TCV_ERR_INVALID; }
-    if (hip_stream == TCV_STREAM_THREAD) hip_stream = (void *)tcv::util_stream();
+    if (o->at == TCV_EVALUATE_AT_SOLUTION && !b->last.solved) { set_error("batch_evaluate: at = solution, but the batch has not been solved"); return TCV_ERR_INVALID; }
+    hip_stream = (void *)tcv::resolve_stream(hip_stream);
     if (int rc = eval_prepare(b)) return rc;
-    EvalState *s = (EvalState *)b->eval;
+    EvalState *s = eval_of(b);
     EvalArgs a;
     std::memset(&a, 0, sizeof a);
-    a.win = b->d_win; a.plans = b->d_plans; a.plan_base = b->d_plan_base; a.ipool = b->d_ipool; a.dpool = b->d_dpool;
-    a.state = o->at == TCV_EVALUATE_AT_SOLUTION ? b->d_state : nullptr;
+    a.win = b->mem.d_win; a.plans = b->mem.d_plans; a.plan_base = b->mem.d_plan_base; a.ipool = b->mem.d_ipool; a.dpool = b->mem.d_dpool;
+    a.state = o->at == TCV_EVALUATE_AT_SOLUTION ? b->mem.d_state : nullptr;
     a.tab_base = s->tab.base; a.tab = s->tab.ints;
     a.scalars = s->d_scal;
     a.residuals = o->want_residuals ? s->d_res : nullptr; a.block_cost = o->want_block_costs ? s->d_blk : nullptr;
     a.gradient = o->want_gradient ? s->d_grad : nullptr; a.stage = s->d_stage;
-    a.nwin = b->n; a.state_stride = b->state_stride; a.res_stride = s->res_stride; a.blk_stride = s->blk_stride;
+    a.nwin = b->in.n; a.state_stride = b->in.state_stride; a.res_stride = s->res_stride; a.blk_stride = s->blk_stride;
     a.grad_stride = s->grad_stride; a.stage_stride = s->stage_stride;
     a.apply_loss = o->apply_loss_function ? 1 : 0;
-    if (int rc = tcv_batch_enter_stream(b, hip_stream)) return rc;
-    const int rc = tcv_launch_evaluate(&a, sizeof(double) * (size_t)eval_lds_doubles(b->state_stride), hip_stream);
+    if (int rc = b->flight.enter((hipStream_t)hip_stream)) return rc;
+    const int rc = tcv_launch_evaluate(&a, sizeof(double) * (size_t)eval_lds_doubles(b->in.state_stride), hip_stream);
     if (rc != 0) return hip_fail((hipError_t)rc, "evaluate kernel launch");
     s->evaluated = true; s->last = *o;
     return TCV_OK;
 }
 static int eval_local_size(const tcv_batch *b, int window) {
-    const tcv_problem &p = *b->problems[window];
-    const Packed &pk = b->packed[window];
+    const tcv_problem &p = *b->in.problems[window];
+    const Packed &pk = b->in.packed[window];
     int k = 0;
     for (size_t c = 0; c < pk.cam_block.size(); c++)
         if (pk.cam_loff[c] >= 0) { const ParamBlock &pb = p.blocks[pk.cam_block[c]]; k += pb.kind == KIND_POSE ? 6 : pb.size; }
-    return k + b->plans[b->wins[window].plan].nland;
+    return k + b->in.plans[b->in.wins[window].plan].nland;
 }
 extern "C" int tcv_batch_evaluation_dims(const tcv_batch *b, int window, int *num_residuals, int *num_residual_blocks, int *num_local) {
-    if (!b || window < 0 || window >= b->n) { set_error("batch_evaluation_dims: no batch / window out of range"); return TCV_ERR_INVALID; }
-    const PlanHdr &H = b->plans[b->wins[window].plan];
+    if (!b || window < 0 || window >= b->in.n) { set_error("batch_evaluation_dims: no batch / window out of range"); return TCV_ERR_INVALID; }
+    const PlanHdr &H = b->in.plans[b->in.wins[window].plan];
     if (num_residuals) *num_residuals = eval_num_residuals(H);
-    if (num_residual_blocks) *num_residual_blocks = eval_num_blocks(H) - 1 + (int)b->problems[window]->prior.size();
+    if (num_residual_blocks) *num_residual_blocks = eval_num_blocks(H) - 1 + (int)b->in.problems[window]->prior.size();
     if (num_local) *num_local = eval_local_size(b, window);
     return TCV_OK;
 }
 static int eval_ready(tcv_batch *b, const char *who) {
     if (!b) { set_error(std::string(who) + ": null batch"); return TCV_ERR_INVALID; }
-    if (!b->eval || !((EvalState *)b->eval)->evaluated) { set_error(std::string(who) + ": the batch has not been evaluated"); return TCV_ERR_INVALID; }
-    if (b->pending) return tcv_batch_synchronize(b);
-    return TCV_OK;
+    if (!eval_of(b) || !eval_of(b)->evaluated) { set_error(std::string(who) + ": the batch has not been evaluated"); return TCV_ERR_INVALID; }
+    return b->settle();
 }
 static bool eval_finite(const double *v, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(v[i])) return false; return true; }
 extern "C" int tcv_batch_get_evaluation(tcv_batch *b, int window, double *cost, double family_cost[4], double *gradient_max_norm,
                                         double *residuals, int residuals_cap, double *block_costs, int block_costs_cap, double *gradient,
                                         int gradient_cap) {
-    if (b && (window < 0 || window >= b->n)) { set_error("batch_get_evaluation: window out of range"); return TCV_ERR_INVALID; }
+    if (b && (window < 0 || window >= b->in.n)) { set_error("batch_get_evaluation: window out of range"); return TCV_ERR_INVALID; }
     if (int rc = eval_ready(b, "batch_get_evaluation")) return rc;
-    EvalState *s = (EvalState *)b->eval;
+    EvalState *s = eval_of(b);
     if ((residuals && !s->last.want_residuals) || (block_costs && !s->last.want_block_costs) || (gradient && !s->last.want_gradient)) {
         set_error("batch_get_evaluation: an output the last tcv_batch_evaluate was not asked for"); return TCV_ERR_INVALID;
     }
-    const PlanHdr &H = b->plans[b->wins[window].plan];
-    const tcv_problem &p = *b->problems[window];
-    const Packed &pk = b->packed[window];
+    const PlanHdr &H = b->in.plans[b->in.wins[window].plan];
+    const tcv_problem &p = *b->in.problems[window];
+    const Packed &pk = b->in.packed[window];
     const int nres = eval_num_residuals(H), nblk = eval_num_blocks(H) - 1 + (int)p.prior.size(), nloc = eval_local_size(b, window);
     if ((residuals && residuals_cap < nres) || (block_costs && block_costs_cap < nblk) || (gradient && gradient_cap < nloc)) {
         set_error("batch_get_evaluation: an output array is too small (tcv_batch_evaluation_dims)"); return TCV_ERR_INVALID;
@@ -210,9 +204,9 @@ extern "C" int tcv_batch_get_evaluation(tcv_batch *b, int window, double *cost, 
     return TCV_OK;
 }
 extern "C" int tcv_batch_get_evaluation_costs(tcv_batch *b, double *cost, double *family_cost, double *gradient_max_norm, int n) {
-    if (b && n != b->n) { set_error("batch_get_evaluation_costs: n must be the batch size"); return TCV_ERR_INVALID; }
+    if (b && n != b->in.n) { set_error("batch_get_evaluation_costs: n must be the batch size"); return TCV_ERR_INVALID; }
     if (int rc = eval_ready(b, "batch_get_evaluation_costs")) return rc;
-    EvalState *s = (EvalState *)b->eval;
+    EvalState *s = eval_of(b);
     std::vector<double> h((size_t)n * EV_SCALARS);
     if (int rc = tcv::staged_download(h.data(), s->d_scal, sizeof(double) * h.size(), "download of the evaluation")) return rc;
     bool ok = true;

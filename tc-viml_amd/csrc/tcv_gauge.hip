@@ -87,19 +87,18 @@ extern "C" int tcv_gauge_fix(int n, const double *R0, const double *P0, const do
 }
 
 extern "C" int tcv_batch_gauge_fix(tcv_batch *b, void *hip_stream) {
-    if (!b || !b->solved) { set_error("batch_gauge_fix: batch has not been solved"); return TCV_ERR_INVALID; }
-    if (b->gauge_in_solve) return TCV_OK;      // the last solve applied it in its epilogue (tcv_batch_set_fused_gauge_fix): same states, same bits
-    if (hip_stream == TCV_STREAM_THREAD) hip_stream = (void *)tcv::util_stream();
-    for (auto &H : b->plans)
+    if (!b || !b->last.solved) { set_error("batch_gauge_fix: batch has not been solved"); return TCV_ERR_INVALID; }
+    if (b->last.gauge_in_solve) return TCV_OK;      // the last solve applied it in its epilogue (tcv_batch_set_fused_gauge_fix): same states, same bits
+    const hipStream_t st = tcv::resolve_stream(hip_stream);
+    for (auto &H : b->in.plans)
         if (H.n_frames <= 0 || H.n_frames > 64) { set_error("batch_gauge_fix: problem carries no frame table (tcv_problem_set_frames)"); return TCV_ERR_INVALID; }
-    if (int rc = tcv_batch_enter_stream(b, hip_stream)) return rc;
+    if (int rc = b->flight.enter(st)) return rc;
     // relocalisation windows: double2vector's tail (estimator.cpp:1606-1624) from the un-fixed states, before pose 0 is overwritten (tcv_relo.hip)
-    if (b->n_relo > 0 && !b->relo_done) if (int rc = tcv_relo_launch(b, (hipStream_t)hip_stream)) return rc;
-    hipLaunchKernelGGL(gauge_batch_kernel, dim3(b->n), dim3(64), 0, (hipStream_t)hip_stream, b->d_win, b->d_plans, b->d_plan_base, b->d_ipool,
-                       b->d_dpool, b->d_state, b->state_stride);
+    if (const ReloState *r = tcv_relo_of(b)) if (!r->done) if (int rc = tcv_relo_launch(b, st)) return rc;
+    hipLaunchKernelGGL(gauge_batch_kernel, dim3(b->in.n), dim3(64), 0, st, b->mem.d_win, b->mem.d_plans, b->mem.d_plan_base, b->mem.d_ipool,
+                       b->mem.d_dpool, b->mem.d_state, b->in.state_stride);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "gauge kernel launch");
-    b->gauge_fixed = true;
     return TCV_OK;
 }
 
@@ -109,8 +108,8 @@ extern "C" int tcv_batch_gauge_fix(tcv_batch *b, void *hip_stream) {
 extern "C" int tcv_batch_set_fused_gauge_fix(tcv_batch *b, int on) {
     if (!b) return TCV_ERR_INVALID;
     if (on)
-        for (auto &H : b->plans)
+        for (auto &H : b->in.plans)
             if (H.n_frames <= 0 || H.n_frames > 64) { set_error("batch_set_fused_gauge_fix: problem carries no frame table (tcv_problem_set_frames)"); return TCV_ERR_INVALID; }
-    b->fuse_gauge = on != 0;
+    b->last.fuse_gauge = on != 0;
     return TCV_OK;
 }

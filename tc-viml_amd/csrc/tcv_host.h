@@ -1,8 +1,8 @@
 // Host-side data model behind the C-ABI of include/tcv.h: the ceres::Problem-shaped graph
 // (reference vins_estimator/src/estimator.cpp:1679-1886), the MarginalizationInfo-shaped prior
 // (factor/marginalization_factor.h:46-72) and the packer that turns a problem into the
-// device-resident plan + data of tcv_packed.h; behind the batch, what the side tables beside its plans share
-// (PlanTable, BlockMap) and the covariance's table builders.
+// device-resident plan + data of tcv_packed.h; behind the batch (tcv_batch.h, included at the end), what the side tables beside its
+// plans share (PlanTable, BlockMap) and the covariance's table builders.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -169,83 +169,6 @@ struct tcv_problem {
     double relo_prev[12] = {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1};
 };
 
-struct tcv_batch {
-    int n = 0;
-    std::vector<tcv_problem *> problems;
-    std::vector<tcv::Packed> packed;         // host copies of per-window maps (ints/doubles released after upload)
-    std::vector<tcv::PlanHdr> plans;
-    std::vector<long long> plan_base;
-    std::vector<tcv::WinHdr> wins;
-    int state_stride = 0, delta_stride = 0;
-    double input_bytes = 0, plan_bytes = 0;
-    // device
-    void *d_input = nullptr;                 // one allocation: [data pool | window headers | plan headers | plan offsets | plan ints | splice jobs | device-only tail: the regions of device-resident priors]
-    tcv::WinHdr *d_win = nullptr;
-    tcv::PlanHdr *d_plans = nullptr;
-    long long *d_plan_base = nullptr;
-    int *d_ipool = nullptr;
-    void *d_zero = nullptr;                  // one allocation, zeroed by one memset: [d_delta | d_scratch | d_summary | d_prof]
-    double *d_dpool = nullptr, *d_state = nullptr, *d_delta = nullptr, *d_scratch = nullptr;
-    tcv::DevSummary *d_summary = nullptr;
-    double *d_prof = nullptr;
-    int grid = 0, nthreads = 256;
-    size_t lds_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float solve_ms = 0, marg_ms = 0;
-    bool solved = false;
-    std::vector<double> h_state;
-    bool gauge_fixed = false;
-    bool fuse_gauge = false, gauge_in_solve = false;      // tcv_batch_set_fused_gauge_fix: the fix in the solve kernel's epilogue; whether the LAST solve applied it
-    hipStream_t last_stream = nullptr;     // stream of the last asynchronous call
-    std::vector<hipStream_t> streams;      // every stream with work of this batch in flight (tcv_batch_synchronize / batch_free wait for all of them; null: the device)
-    hipEvent_t ev_dl = nullptr;            // tcv_batch_download_states_begin: recorded behind the enqueued copy of the states
-    void *dl_staging = nullptr;            // its pinned buffer, until tcv_batch_download_states_end
-    hipEvent_t ev_order = nullptr;         // orders a call on a new stream behind the pending work of the previous one (tcv_batch_enter_stream)
-    hipEvent_t ev_inflight = nullptr;      // tcv_batch_get_priors_device_async: the work in flight is tracked by this event from then on, not by the streams it runs
-    bool wait_inflight = false;            // on (the batch outlives the call, a stream may go with its host thread); waited for by synchronize / destroy / the next call
-    bool pending = false;                  // asynchronous work issued since the last synchronize (batch_free waits before it recycles the buffers)
-    bool chain = false;                   // all plans use the chain layout (2 workgroups per CU)
-    int chain_lds = 0;                    // LDS doubles per chain-layout workgroup of this batch
-    double *d_imublk = nullptr, *d_spill = nullptr;   // chain mode: per-workgroup IMU J'J blocks and factored fronts
-    double *d_sqrt_out = nullptr;         // per window 225 doubles: the solve's sqrt_info of the IMU factor the marginalisation needs
-    bool sqrt_out_valid = false;          // the last solve wrote it (device-computed sqrt_info)
-    int spill_stride = 0;
-    int hcl_cap = 0;                      // doubles of the landmark/camera coupling store per workgroup (largest window of the batch)
-    // cooperative mode (tcv_packed.h COOP_*): helpers per window group (0: off), groups, scratch slots (= grid without it)
-    int coop_h = 0, coop_groups = 0, slots = 0;
-    int last_wg = 0;                              // workgroups per window of the last solve (1: single-workgroup kernel)
-    int n_cu = 0, coop_claim = 0, coop_dev = 0;   // CUs of the device; CUs this batch's cooperative launch in flight has claimed (tcv_batch_solve)
-    int coop_claim_xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0}, coop_rot = 0;   // the claim per XCD; XCD of the launch's first group (tcv_batch.cpp coop_admit)
-    int coop_exp_chunks = 0, coop_exp_stride = 0;
-    int *d_coop_ctl = nullptr;
-    double *d_coop_x = nullptr, *d_coop_exp = nullptr;
-    // marginalisation
-    void *marg = nullptr;                 // tcv_marg_host.cpp MargState
-    void (*marg_free)(tcv_batch *) = nullptr;
-    // evaluation (tcv_batch_evaluate)
-    void *eval = nullptr;                 // tcv_eval_host.cpp EvalState: owner lists, staging and output buffers, made at the first evaluation
-    // marginal covariance (include/tcv_covariance.h)
-    void *cov = nullptr;                  // tcv_cov_host.cpp CovState: owner lists, work and result buffers, made at the first computation
-    void (*cov_free)(tcv_batch *) = nullptr;
-    // relocalisation (tcv_relo.hip): the windows whose problem carries tcv_problem_set_relocalization; n_relo = 0: nothing below is used
-    int n_relo = 0;
-    std::vector<int> relo_win;            // window of every table entry
-    double *d_relo = nullptr;             // one allocation: [records x n_relo | prev_relo_t / _r x n_relo | table], tcv_relo.h
-    std::vector<double> h_relo_up;        // the upload's host image (alive as long as the batch: the copy is asynchronous)
-    bool relo_done = false;               // the records belong to the last solve (tcv_batch_gauge_fix ran behind it)
-    bool relo_in_dl = false;              // the download in flight carries them
-    bool relo_have = false;               // h_relo / relo_valid hold them
-    std::vector<double> h_relo;           // host copy of the records, downloaded with the states
-    std::vector<char> relo_valid;         // per entry: the window's solve did not end in FAILURE
-};
-int tcv_relo_attach(tcv_batch *b, hipStream_t upload_stream);      // tcv_batch_create: table + prev_relo_* up, record buffer (no-op without relocalisation problems)
-int tcv_relo_launch(tcv_batch *b, hipStream_t st);                 // tcv_batch_gauge_fix: relo_fix_batch_kernel in front of the gauge kernel
-
-
-// every asynchronous entry point of a batch passes through here: a call on another stream than the previous one waits (on the device) for
-// the batch's pending work there -- the gauge fix and the marginalisation read what the solve wrote -- and the stream joins the set
-// tcv_batch_synchronize waits for
-int tcv_batch_enter_stream(tcv_batch *b, void *hip_stream);
 namespace tcv {
 // A side table beside the plans of a batch (the owner lists of the gradient and of S, the landmark slot tables): one device allocation
 // [offset of every distinct plan's entry, in ints (long long) | the entries], at least one int behind the offsets.
@@ -296,7 +219,6 @@ void tcv_marg_elapsed(tcv_batch *b);
 int tcv_marg_download(tcv_batch *b, int compact);
 int tcv_marg_get_priors_device(tcv_batch *b, tcv_prior **out, int n, bool nowait);
 int tcv_marg_status_prefetch(tcv_batch *b, void *stream);
-void tcv_eval_free(tcv_batch *b);      // tcv_eval_host.cpp: the evaluation buffers of a batch (no-op before the first tcv_batch_evaluate)
 bool tcv_marg_has_problem(const tcv_batch *b, int window);      // false: marg_problems[window] was NULL
 int tcv_marg_layout_n(const tcv_batch *b, int window);          // n of the prior this window's marginalisation makes (known from the attached problem, before the kernel runs); -1: none
 // host only (tcv_problem_marg_plan): one window through the marginalisation packer -- ints = [MargHdr as ints | int pool], doubles = the
@@ -318,7 +240,7 @@ int launch_prior_splice(const PriorSplice *d_jobs, int njobs, double *d_dpool, v
 }  // namespace tcv
 
 namespace tcv {
-int solver_variant();      // tcv_set_solver_variant (tcv_batch.cpp): 0 chain layout when the graph allows it, 1 always the dense 171-dim layout
+int solver_variant();      // tcv_set_solver_variant (tcv_batch_create.cpp): 0 chain layout when the graph allows it, 1 always the dense 171-dim layout
 // returns TCV_OK or a negative status; fills out.  imu_sqrt: optional host-provided sqrt_info (n_imu x 225).
 // mode: 0 = chain layout when the graph allows it (speed-bias blocks form chains), else dense; 1 = dense layout
 // chain_lds: LDS doubles of a chain-layout workgroup (0: chain_lds_doubles(), half a CU's LDS so that two workgroups share a CU)
@@ -365,3 +287,5 @@ bool pack_reference();
 void cam_cache_stats(long long *hits, long long *misses);      // the camera halves of the plans (tcv_pack.cpp)
 unsigned long long plan_content_hash(const PlanHdr &hdr, const PlanInts &ints);
 }  // namespace tcv
+
+#include "tcv_batch.h"      // struct tcv_batch: its parts and side states

@@ -1,5 +1,5 @@
 // Host side of the marginalisation (the kernel and its launchers: tcv_marg.hip; what the two share: tcv_marg.h): the packer that turns a
-// marginalisation problem into the kernel's plan (pack_marg, in phases), the per-batch state behind tcv_batch::marg (attach, run, download)
+// marginalisation problem into the kernel's plan (pack_marg, in phases), the per-batch state behind tcv_batch::marg (MargState: attach, run, download)
 // and the hand-out of the results as priors, host- or device-resident.
 //
 // Block order (the reference's is unordered_map / address dependent, marginalization_factor.cpp:176-194): dropped blocks in the order
@@ -26,7 +26,7 @@ struct MargWindow {
                                       // empty MarginalizationInfo (marginalization_factor.cpp:174-194 with n = pos - m = 0; carried into the next frame
                                       // by estimator.cpp:2040-2043, where its factor has no residuals and no blocks)
 };
-struct MargState {
+struct MargState : tcv::SideState {
     std::vector<MargWindow> win;
     void *d_input = nullptr;          // one allocation: [double pool | headers | int pool]
     MargHdr *d_hdr = nullptr;
@@ -43,21 +43,17 @@ struct MargState {
     size_t h_stride = 0;              // doubles per window in h_out: MARG_OUT_STRIDE, or MARG_OUT_COMPACT (no A', b')
     std::vector<int> h_status;
     bool h_valid = false;
+    ~MargState() override {
+        (void)tcv::dev_free(d_input);      // (d_hdr, d_ipool, d_dpool point into d_input; d_status lives behind d_out in the result blob)
+        out_blob.reset();                  // (d_out: freed when the last device-resident prior that reads it is gone)
+        (void)tcv::dev_free(d_scratch);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        tcv::host_staging_release(h_out);
+        tcv::host_staging_release(h_status_pre);
+    }
 };
-
-static void marg_free(tcv_batch *b) {
-    MargState *s = (MargState *)b->marg;
-    if (!s) return;
-    (void)tcv::dev_free(s->d_input);      // (d_hdr, d_ipool, d_dpool point into d_input; d_status lives behind d_out in the result blob)
-    s->out_blob.reset(); s->d_out = nullptr;      // (freed when the last device-resident prior that reads it is gone)
-    (void)tcv::dev_free(s->d_scratch);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    tcv::host_staging_release(s->h_out);
-    tcv::host_staging_release(s->h_status_pre);
-    delete s;
-    b->marg = nullptr;
-}
+static MargState *marg_of(const tcv_batch *b) { return static_cast<MargState *>(b->marg.get()); }
 
 // The developer switches of the marginalisation, read once per attach / plan dump (the packer's and the launch shape's) or per run (the
 // kernel's) and handed down -- per call, not once per process: the tests flip them between the batches of one process
@@ -505,7 +501,7 @@ static int marg_pack_windows(tcv_batch *b, tcv_problem *const *marg_problems, do
         std::vector<double> &D = P.D[t];
         for (int w = P.first(t); w < P.first(t + 1); w++) {
             const size_t i0 = I.size(), d0 = D.size();
-            const int rc = marg_problems[w] ? pack_marg(*marg_problems[w], marg_drop[w], marg_num_drop[w], b->problems[w], &b->packed[w], sw, s->win[w], I, D)
+            const int rc = marg_problems[w] ? pack_marg(*marg_problems[w], marg_drop[w], marg_num_drop[w], b->in.problems[w], &b->in.packed[w], sw, s->win[w], I, D)
                                             : (int)MARG_PACK_EMPTY_KEEP;      // (not marginalised: skipped alike, but MargWindow::empty_keep stays false)
             if (rc == MARG_PACK_EMPTY_KEEP) { I.resize(i0); D.resize(d0); marg_skip_header(s->win[w].hdr, i0, d0, w); continue; }
             if (rc != TCV_OK) { rcs[t] = rc; msgs[t] = tcv_last_error(); return; }
@@ -551,33 +547,33 @@ static void marg_fill_staging(char *h_in, const MargBlobLayout &lay, const MargP
 }
 // more windows than CUs and every window within half a CU's LDS: two 256-thread workgroups per CU; otherwise one of 512 threads
 static int marg_launch_shape(const tcv_batch *b, const MargSwitches &sw, size_t lds_bytes, MargState *s) {
-    const int n_cu = b->n_cu;      // (of the batch's device: tcv_batch_create sets it before anything attaches)
+    const int n_cu = b->shape.n_cu;      // (of the batch's device: tcv_batch_create sets it before anything attaches)
     const size_t half = (size_t)LDS_DOUBLES * 4;
-    const bool pair = sw.nt_forced ? sw.nt == MARG_NT_PAIR : (b->n > n_cu && lds_bytes <= half);
+    const bool pair = sw.nt_forced ? sw.nt == MARG_NT_PAIR : (b->in.n > n_cu && lds_bytes <= half);
     if (pair && lds_bytes > half) { set_error("TCV_MARG_NT=256: the batch does not fit 80 KB of LDS per window"); return TCV_ERR_TOO_LARGE; }
     s->nt = pair ? MARG_NT_PAIR : MARG_NT_WIDE;
     s->lds_bytes = pair ? half : lds_bytes;
-    s->grid = std::min(b->n, pair ? 2 * n_cu : n_cu);
+    s->grid = std::min(b->in.n, pair ? 2 * n_cu : n_cu);
     if (sw.grid_cap > 0) s->grid = std::min(s->grid, sw.grid_cap);      // tuning experiments (one workgroup per CU: TCV_MARG_GRID=256)
     return TCV_OK;
 }
 // device buffers and the one asynchronous copy of the staged input on the calling thread's stream
 static int marg_upload(tcv_batch *b, MargState *s, tcv::StagedTransfer &staged, const MargBlobLayout &lay) {
     hipStream_t ust = staged.st;
-    const size_t out_doubles = std::max<size_t>(1, (size_t)b->n * MARG_OUT_STRIDE);
+    const size_t out_doubles = std::max<size_t>(1, (size_t)b->in.n * MARG_OUT_STRIDE);
     hipError_t e_ = tcv::dev_malloc(&s->d_input, lay.bytes);
     if (e_ == hipSuccess) { staged.issued(); e_ = hipMemcpyAsync(s->d_input, staged.host, lay.bytes, hipMemcpyHostToDevice, ust); }
     // result blocks and, behind them, [status | k0] of every window: one buffer, kept alive by the device-resident priors that read it
-    if (e_ == hipSuccess) e_ = tcv::dev_malloc((void **)&s->d_out, sizeof(double) * out_doubles + sizeof(int) * 2 * (size_t)b->n);
+    if (e_ == hipSuccess) e_ = tcv::dev_malloc((void **)&s->d_out, sizeof(double) * out_doubles + sizeof(int) * 2 * (size_t)b->in.n);
     if (e_ == hipSuccess) { s->out_blob = std::make_shared<DevBlob>(); s->out_blob->p = s->d_out; (void)hipGetDevice(&s->out_blob->dev); s->d_status = (int *)(s->d_out + out_doubles); }
     if (e_ == hipSuccess) e_ = tcv::dev_malloc((void **)&s->d_scratch, sizeof(double) * (size_t)s->grid * MARG_SCR_STRIDE);
-    if (e_ == hipSuccess) e_ = hipMemsetAsync(s->d_status, 0xff, sizeof(int) * 2 * b->n, ust);
+    if (e_ == hipSuccess) e_ = hipMemsetAsync(s->d_status, 0xff, sizeof(int) * 2 * b->in.n, ust);
     // No wait for the upload: the native estimator attaches the problems while the batch's SOLVE runs on this very stream, and a wait here
     // is a wait for that kernel (a caller that overlaps another group's host work with it -- tcv_estimators_optimize_begin -- lost the whole
     // overlap to it).  The batch notes the stream (a later launch on another stream is ordered behind the upload by an event,
-    // tcv_batch_enter_stream); the pinned staging buffer is parked until this thread's next wait on the stream.
+    // BatchFlight::enter); the pinned staging buffer is parked until this thread's next wait on the stream.
     if (e_ == hipSuccess && ust != nullptr) {
-        if (int rce = tcv_batch_enter_stream(b, (void *)ust)) return rce;
+        if (int rce = b->flight.enter(ust)) return rce;
         staged.park();
     } else if (e_ == hipSuccess) e_ = staged.wait();
     if (e_ != hipSuccess) return hip_fail(e_, "upload of the marginalisation problems");
@@ -587,15 +583,14 @@ static int marg_upload(tcv_batch *b, MargState *s, tcv::StagedTransfer &staged, 
 
 int tcv_marg_attach(tcv_batch *b, tcv_problem *const *marg_problems, double *const *const *marg_drop, const int *marg_num_drop) {
     MargState *s = new MargState();
-    b->marg = s;
-    b->marg_free = marg_free;
-    s->win.resize(b->n);
-    for (int w = 0; w < b->n; w++)
+    b->marg.reset(s);
+    s->win.resize(b->in.n);
+    for (int w = 0; w < b->in.n; w++)
         if (marg_problems[w] && (!marg_drop || !marg_drop[w])) { set_error("marginalisation problem without a drop list"); return TCV_ERR_INVALID; }
     const MargSwitches sw = MargSwitches::for_attach();
-    MargPools P(b->n, tcv::host_threads(std::max(1, std::min(b->n <= 16 ? b->n : b->n / 8, 16))));      // (inside tcv_batch_create's HostOp; a lock-step frame's handful of windows: one each)
+    MargPools P(b->in.n, tcv::host_threads(std::max(1, std::min(b->in.n <= 16 ? b->in.n : b->in.n / 8, 16))));      // (inside tcv_batch_create's HostOp; a lock-step frame's handful of windows: one each)
     if (int rc = marg_pack_windows(b, marg_problems, marg_drop, marg_num_drop, sw, s, P)) return rc;
-    std::vector<MargHdr> hdrs(b->n);
+    std::vector<MargHdr> hdrs(b->in.n);
     size_t lds_bytes = 0;
     if (int rc = marg_concat(s, P, hdrs, lds_bytes)) return rc;
     const MargBlobLayout lay(P.db[P.nth], P.ib[P.nth], hdrs.size());
@@ -611,16 +606,16 @@ int tcv_marg_attach(tcv_batch *b, tcv_problem *const *marg_problems, double *con
 }
 
 int tcv_marg_run(tcv_batch *b, void *stream) {
-    MargState *s = (MargState *)b->marg;
+    MargState *s = marg_of(b);
     if (!s) { set_error("batch was created without marginalisation problems"); return TCV_ERR_INVALID; }
     const MargSwitches sw = MargSwitches::for_run();
     MargArgs a;
     std::memset(&a, 0, sizeof a);
-    a.hdr = s->d_hdr; a.ipool = s->d_ipool; a.dpool = s->d_dpool; a.solve_state = b->d_state; a.out = s->d_out;
-    a.out_status = s->d_status; a.scratch = s->d_scratch; a.nwin = b->n; a.state_stride = b->state_stride;
-    a.use_solved_state = b->solved ? 1 : 0;
-    a.solve_dpool = b->d_dpool; a.solve_win = (const void *)b->d_win;
-    a.solve_sqrt = (b->solved && b->sqrt_out_valid && !sw.own_sqrt) ? b->d_sqrt_out : nullptr;
+    a.hdr = s->d_hdr; a.ipool = s->d_ipool; a.dpool = s->d_dpool; a.solve_state = b->mem.d_state; a.out = s->d_out;
+    a.out_status = s->d_status; a.scratch = s->d_scratch; a.nwin = b->in.n; a.state_stride = b->in.state_stride;
+    a.use_solved_state = b->last.solved ? 1 : 0;
+    a.solve_dpool = b->mem.d_dpool; a.solve_win = (const void *)b->mem.d_win;
+    a.solve_sqrt = (b->last.solved && b->last.sqrt_out_valid && !sw.own_sqrt) ? b->mem.d_sqrt_out : nullptr;
     a.eig_mm = sw.eig_mm ? 1 : 0;
     a.eig_flags = sw.eig_flags;
     hipStream_t st = (hipStream_t)stream;
@@ -643,71 +638,71 @@ int tcv_marg_run(tcv_batch *b, void *stream) {
 // the statuses on their way to the host behind the marginalisation kernel (tcv_batch_get_priors_device_async): whoever asks later, after
 // waiting for the batch, finds them in pinned memory instead of paying a blocking copy
 int tcv_marg_status_prefetch(tcv_batch *b, void *stream) {
-    MargState *s = (MargState *)b->marg;
+    MargState *s = marg_of(b);
     if (!s || !s->ran) return TCV_OK;
-    if (!s->h_status_pre) s->h_status_pre = (int *)tcv::host_staging_acquire(sizeof(int) * 2 * (size_t)b->n);
+    if (!s->h_status_pre) s->h_status_pre = (int *)tcv::host_staging_acquire(sizeof(int) * 2 * (size_t)b->in.n);
     if (!s->h_status_pre) return TCV_OK;      // (the blocking copy later)
-    const hipError_t e = hipMemcpyAsync(s->h_status_pre, s->d_status, sizeof(int) * 2 * (size_t)b->n, hipMemcpyDeviceToHost, (hipStream_t)stream);
+    const hipError_t e = hipMemcpyAsync(s->h_status_pre, s->d_status, sizeof(int) * 2 * (size_t)b->in.n, hipMemcpyDeviceToHost, (hipStream_t)stream);
     s->status_prefetched = e == hipSuccess;
     return TCV_OK;
 }
 
 int tcv_marg_layout_n(const tcv_batch *b, int window) {
-    const MargState *s = (const MargState *)b->marg;
+    const MargState *s = marg_of(b);
     if (!s || window < 0 || window >= (int)s->win.size() || s->win[window].hdr.nblk == 0) return -1;
     return s->win[window].hdr.n;
 }
 bool tcv_marg_has_problem(const tcv_batch *b, int window) {
-    const MargState *s = (const MargState *)b->marg;
-    return s && window >= 0 && window < b->n && (s->win[window].hdr.nblk != 0 || s->win[window].empty_keep);
+    const MargState *s = marg_of(b);
+    return s && window >= 0 && window < b->in.n && (s->win[window].hdr.nblk != 0 || s->win[window].empty_keep);
 }
 int tcv_marg_sqrt_source(const tcv_batch *b, int window) {
-    const MargState *s = (const MargState *)b->marg;
-    return (s && window >= 0 && window < b->n) ? s->win[window].hdr.sqrt_src : -1;
+    const MargState *s = marg_of(b);
+    return (s && window >= 0 && window < b->in.n) ? s->win[window].hdr.sqrt_src : -1;
 }
 
 // one D2H copy of every window's result block and status instead of one copy per tcv_batch_get_prior call, into a pinned buffer.
 // compact: J0, r0 and the linearisation point only (a strided copy of the first MARG_OUT_COMPACT doubles of every block); the priors
 // handed out afterwards carry no A', b'.
 int tcv_marg_download(tcv_batch *b, int compact) {
-    MargState *s = (MargState *)b->marg;
+    MargState *s = marg_of(b);
     if (!s || !s->ran) { set_error("no marginalisation result"); return TCV_ERR_INVALID; }
     const size_t stride = compact ? (size_t)MARG_OUT_COMPACT : (size_t)MARG_OUT_STRIDE;
     if (s->h_out && s->h_stride != stride) { tcv::host_staging_release(s->h_out); s->h_out = nullptr; }
-    const size_t out_bytes = sizeof(double) * stride * b->n;      // the status of every window rides behind the blocks in the same pinned buffer
-    if (!s->h_out) s->h_out = (double *)tcv::host_staging_acquire(out_bytes + sizeof(int) * b->n);
+    const size_t out_bytes = sizeof(double) * stride * b->in.n;      // the status of every window rides behind the blocks in the same pinned buffer
+    if (!s->h_out) s->h_out = (double *)tcv::host_staging_acquire(out_bytes + sizeof(int) * b->in.n);
     if (!s->h_out) { set_error("hipHostMalloc (download staging) failed"); return TCV_ERR_HIP; }
     s->h_stride = stride;
-    s->h_status.resize(b->n);
+    s->h_status.resize(b->in.n);
     hipStream_t ust = tcv::util_stream();      // (h_out is pinned: asynchronous copies on the calling thread's own stream, one wait)
-    hipError_t e = compact ? hipMemcpy2DAsync(s->h_out, sizeof(double) * stride, s->d_out, sizeof(double) * MARG_OUT_STRIDE, sizeof(double) * stride, b->n, hipMemcpyDeviceToHost, ust)
+    hipError_t e = compact ? hipMemcpy2DAsync(s->h_out, sizeof(double) * stride, s->d_out, sizeof(double) * MARG_OUT_STRIDE, sizeof(double) * stride, b->in.n, hipMemcpyDeviceToHost, ust)
                            : hipMemcpyAsync(s->h_out, s->d_out, out_bytes, hipMemcpyDeviceToHost, ust);
-    if (e == hipSuccess) e = hipMemcpyAsync((char *)s->h_out + out_bytes, s->d_status, sizeof(int) * b->n, hipMemcpyDeviceToHost, ust);
+    if (e == hipSuccess) e = hipMemcpyAsync((char *)s->h_out + out_bytes, s->d_status, sizeof(int) * b->in.n, hipMemcpyDeviceToHost, ust);
     const hipError_t ew = tcv::stream_wait(ust);      // (whatever was issued is drained before anybody touches h_out again)
     if (e == hipSuccess) e = ew;
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy D2H");
-    std::memcpy(s->h_status.data(), (char *)s->h_out + out_bytes, sizeof(int) * b->n);
+    std::memcpy(s->h_status.data(), (char *)s->h_out + out_bytes, sizeof(int) * b->in.n);
     s->h_valid = true;
     return TCV_OK;
 }
 
 // elapsed time of the last marginalisation launch (called from tcv_batch_synchronize)
 void tcv_marg_elapsed(tcv_batch *b) {
-    MargState *s = (MargState *)b->marg;
-    if (s && s->ran) (void)hipEventElapsedTime(&b->marg_ms, s->ev0, s->ev1);
+    MargState *s = marg_of(b);
+    if (s && s->ran) (void)hipEventElapsedTime(&b->last.marg_ms, s->ev0, s->ev1);
 }
 
 // per-window status of the last marginalisation: 0 ok, 1 an eigen-solver hit its sweep cap, 2 the tridiagonal eigen-solver's
 // self-check failed and the cyclic-Jacobi safety net produced the result, < 0 not run
 extern "C" int tcv_batch_marg_status(tcv_batch *b, int *out, int n) {
-    MargState *s = b ? (MargState *)b->marg : nullptr;
-    if (!s || !s->ran || !out || n > b->n) { set_error("no marginalisation result"); return TCV_ERR_INVALID; }
-    if (b->pending) if (int rc = tcv_batch_synchronize(b)) return rc;      // (a copy on the calling thread's stream is not ordered behind the batch's streams)
-    std::vector<int> st(2 * (size_t)b->n);
+    MargState *s = b ? marg_of(b) : nullptr;
+    if (!s || !s->ran || !out || n > b->in.n) { set_error("no marginalisation result"); return TCV_ERR_INVALID; }
+    if (int rc = b->settle()) return rc;
+    std::vector<int> st(2 * (size_t)b->in.n);
     if (s->status_prefetched) std::memcpy(st.data(), s->h_status_pre, sizeof(int) * st.size());      // (came down behind the kernel; the wait above covers it)
     else if (int rc = tcv::staged_download(st.data(), s->d_status, sizeof(int) * st.size(), "download of the marginalisation status")) return rc;
     for (int w = 0; w < n; w++)      // -2: a NaN in the result; a marginalisation that keeps nothing has nothing to run: 0
-        out[w] = s->win[w].empty_keep ? 0 : ((st[w] == 0 && st[b->n + w] < 0 && s->win[w].hdr.nblk != 0) ? -2 : st[w]);
+        out[w] = s->win[w].empty_keep ? 0 : ((st[w] == 0 && st[b->in.n + w] < 0 && s->win[w].hdr.nblk != 0) ? -2 : st[w]);
     return TCV_OK;
 }
 
@@ -750,8 +745,8 @@ static void marg_debug_dump(const double *o, int window, int m, int n, int statu
 }
 
 int tcv_marg_get_prior(tcv_batch *b, int window, tcv_prior **out) {
-    MargState *s = (MargState *)b->marg;
-    if (!s || !s->ran || window < 0 || window >= b->n) { set_error("no marginalisation result for this window"); return TCV_ERR_INVALID; }
+    MargState *s = marg_of(b);
+    if (!s || !s->ran || window < 0 || window >= b->in.n) { set_error("no marginalisation result for this window"); return TCV_ERR_INVALID; }
     const MargWindow &mw = s->win[window];
     if (mw.empty_keep) { tcv_prior *pr = new tcv_prior(); pr->m = mw.m_total; pr->n = 0; *out = pr; return TCV_OK; }      // the reference's empty MarginalizationInfo
     if (mw.hdr.nblk == 0) { set_error("this window of the batch has no marginalisation problem"); return TCV_ERR_INVALID; }
@@ -793,11 +788,11 @@ int tcv_marg_get_prior(tcv_batch *b, int window, tcv_prior **out) {
 
 // tcv_batch_get_priors_device: layout on the host, numbers left in the batch's result buffer (shared with the handles)
 int tcv_marg_get_priors_device(tcv_batch *b, tcv_prior **out, int n, bool nowait) {
-    MargState *s = (MargState *)b->marg;
-    if (!s || !s->ran || n != b->n) { set_error("no marginalisation result (or n is not the batch size)"); return TCV_ERR_INVALID; }
+    MargState *s = marg_of(b);
+    if (!s || !s->ran || n != b->in.n) { set_error("no marginalisation result (or n is not the batch size)"); return TCV_ERR_INVALID; }
     if (nowait && !(s->out_blob && s->out_blob->ready)) {      // (no event to order consumers by: wait as usual)
         nowait = false;
-        if (b->pending) if (int rcs = tcv_batch_synchronize(b)) return rcs;
+        if (int rcs = b->settle()) return rcs;
     }
     std::vector<int> st(2 * (size_t)n, 0);
     if (nowait) { for (int w = 0; w < n; w++) st[n + w] = -1; }      // status unknown here (tcv_batch_marg_status later), k0 read on the device

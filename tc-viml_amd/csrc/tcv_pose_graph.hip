@@ -659,8 +659,7 @@ extern "C" int tcv_pose_graphs_optimize(int n, const tcv_pose_graph_desc *descs,
     // one upload: [headers | input doubles | ints], one device allocation: [upload | output | scratch]
     const size_t b_hdr = sizeof(PgHdr) * (size_t)n, b_dbl = 8 * (size_t)n_dbl, b_int = ((4 * (size_t)n_int + 7) / 8) * 8;
     const size_t b_in = b_hdr + b_dbl + b_int, b_out = 8 * (size_t)n_out, b_scr = 8 * (size_t)n_scr;
-    if (hip_stream == TCV_STREAM_THREAD) hip_stream = (void *)tcv::util_stream();
-    hipStream_t st = (hipStream_t)hip_stream;
+    hipStream_t st = tcv::resolve_stream(hip_stream);
     tcv::StagedTransfer tr(st, b_in + b_out);
     if (!tr.host) { set_error("hipHostMalloc (pose graph staging) failed"); return TCV_ERR_HIP; }
     char *h = (char *)tr.host;

@@ -86,16 +86,17 @@ extern "C" int tcv_relocalization_fix(int n, const double *R0, const double *P0,
 // tcv_batch_create: the relocalisation table of the batch, its prev_relo_* and the record buffer in one device allocation
 // [records RELO_REC x n | prev RELO_PREV x n | table n entries]; the upload goes on `st` (the batch's own upload stream: tcv_batch_create
 // waits for it before it returns).  A batch without such a problem allocates, copies and launches nothing.
+tcv::ReloState::~ReloState() { tcv::dev_free(d); }
 int tcv_relo_attach(tcv_batch *b, hipStream_t st) {
     std::vector<ReloEntry> tab;
     std::vector<double> prev;
-    for (int w = 0; w < b->n; w++) {
-        const tcv_problem &p = *b->problems[w];
+    for (int w = 0; w < b->in.n; w++) {
+        const tcv_problem &p = *b->in.problems[w];
         if (p.relo_block < 0) continue;
-        const Packed &pk = b->packed[w];
+        const Packed &pk = b->in.packed[w];
         const int l = p.relo_local;
         if (l < 0 || l >= (int)p.frame_pose.size() || p.frame_pose.size() > 64) { set_error("batch_create: relocalisation without a frame table (tcv_problem_set_frames)"); return TCV_ERR_INVALID; }
-        // where the blocks sit in the state vector: camera blocks in plan order (scatter_states, tcv_batch.cpp)
+        // where the blocks sit in the state vector: camera blocks in plan order (scatter_states, tcv_batch_results.cpp)
         int off = 0, relo_off = -1;
         bool have0 = false, havel = false;
         for (int blk : pk.cam_block) {
@@ -103,45 +104,49 @@ int tcv_relo_attach(tcv_batch *b, hipStream_t st) {
             have0 = have0 || blk == p.frame_pose[0]; havel = havel || blk == p.frame_pose[l];
             off += p.blocks[blk].size;
         }
-        if (relo_off < 0 || !have0 || !havel || relo_off + 7 > b->state_stride) { set_error("batch_create: the relocalisation pose, para_Pose[0] or the matched frame's pose takes part in no factor"); return TCV_ERR_INVALID; }
+        if (relo_off < 0 || !have0 || !havel || relo_off + 7 > b->in.state_stride) { set_error("batch_create: the relocalisation pose, para_Pose[0] or the matched frame's pose takes part in no factor"); return TCV_ERR_INVALID; }
         tab.push_back(ReloEntry{w, relo_off, l, 0});
         prev.insert(prev.end(), p.relo_prev, p.relo_prev + RELO_PREV);
     }
-    b->n_relo = (int)tab.size();
     if (tab.empty()) return TCV_OK;
+    ReloState *r = new ReloState();
+    b->relo.reset(r);
     const size_t nr = tab.size();
+    r->n = (int)nr;
     static_assert(sizeof(ReloEntry) == 16, "two doubles per table entry");
-    b->relo_win.resize(nr);
-    for (size_t k = 0; k < nr; k++) b->relo_win[k] = tab[k].window;
-    b->h_relo_up.assign(((size_t)RELO_PREV + 2) * nr, 0.0);
-    std::memcpy(b->h_relo_up.data(), prev.data(), sizeof(double) * RELO_PREV * nr);
-    std::memcpy(b->h_relo_up.data() + RELO_PREV * nr, tab.data(), sizeof(ReloEntry) * nr);
-    hipError_t e = tcv::dev_malloc((void **)&b->d_relo, sizeof(double) * ((size_t)RELO_REC + RELO_PREV + 2) * nr);
+    r->win.resize(nr);
+    for (size_t k = 0; k < nr; k++) r->win[k] = tab[k].window;
+    r->h_up.assign(((size_t)RELO_PREV + 2) * nr, 0.0);
+    std::memcpy(r->h_up.data(), prev.data(), sizeof(double) * RELO_PREV * nr);
+    std::memcpy(r->h_up.data() + RELO_PREV * nr, tab.data(), sizeof(ReloEntry) * nr);
+    hipError_t e = tcv::dev_malloc((void **)&r->d, sizeof(double) * ((size_t)RELO_REC + RELO_PREV + 2) * nr);
     if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    e = hipMemcpyAsync(b->d_relo + RELO_REC * nr, b->h_relo_up.data(), sizeof(double) * b->h_relo_up.size(), hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(r->d + RELO_REC * nr, r->h_up.data(), sizeof(double) * r->h_up.size(), hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return hip_fail(e, "upload of the relocalisation table");
     return TCV_OK;
 }
 
 // tcv_batch_gauge_fix of a batch with relocalisation windows: the records, from the un-fixed states, in front of the gauge kernel
 int tcv_relo_launch(tcv_batch *b, hipStream_t st) {
-    const size_t nr = (size_t)b->n_relo;
-    const double *prev = b->d_relo + RELO_REC * nr;
+    ReloState *r = tcv_relo_of(b);
+    const size_t nr = (size_t)r->n;
+    const double *prev = r->d + RELO_REC * nr;
     const ReloEntry *tab = (const ReloEntry *)(prev + RELO_PREV * nr);
-    hipLaunchKernelGGL(relo_fix_batch_kernel, dim3((b->n_relo + 63) / 64), dim3(64), 0, st, b->n_relo, tab, prev, b->d_win, b->d_plans, b->d_plan_base, b->d_ipool,
-                       b->d_dpool, b->d_state, b->state_stride, b->d_relo);
+    hipLaunchKernelGGL(relo_fix_batch_kernel, dim3((r->n + 63) / 64), dim3(64), 0, st, r->n, tab, prev, b->mem.d_win, b->mem.d_plans, b->mem.d_plan_base, b->mem.d_ipool,
+                       b->mem.d_dpool, b->mem.d_state, b->in.state_stride, r->d);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "relocalisation kernel launch");
-    b->relo_done = true;
+    r->done = true;
     return TCV_OK;
 }
 
 extern "C" int tcv_batch_get_relocalization(tcv_batch *b, int window, tcv_relo_result *out) {
-    if (!b || !out || window < 0 || window >= b->n) { set_error("batch_get_relocalization: bad argument"); return TCV_ERR_INVALID; }
-    if (b->n_relo > 0 && !b->relo_have) { set_error("batch_get_relocalization: the states have not been downloaded behind tcv_batch_gauge_fix"); return TCV_ERR_INVALID; }
-    if (b->n_relo == 0 && b->h_state.empty()) { set_error("batch_get_relocalization: the states have not been downloaded"); return TCV_ERR_INVALID; }
-    for (int k = 0; k < b->n_relo; k++)
-        if (b->relo_win[k] == window) { record_to_public(b->h_relo.data() + (size_t)RELO_REC * k, b->relo_valid[k], out); return TCV_OK; }
+    if (!b || !out || window < 0 || window >= b->in.n) { set_error("batch_get_relocalization: bad argument"); return TCV_ERR_INVALID; }
+    const ReloState *r = tcv_relo_of(b);
+    if (r && !r->have) { set_error("batch_get_relocalization: the states have not been downloaded behind tcv_batch_gauge_fix"); return TCV_ERR_INVALID; }
+    if (!r && b->dl.h_state.empty()) { set_error("batch_get_relocalization: the states have not been downloaded"); return TCV_ERR_INVALID; }
+    for (int k = 0; r && k < r->n; k++)
+        if (r->win[k] == window) { record_to_public(r->h_rec.data() + (size_t)RELO_REC * k, r->valid[k], out); return TCV_OK; }
     record_to_public(nullptr, 0, out);      // a window without relocalisation
     return TCV_OK;
 }

@@ -133,7 +133,7 @@ void flush_deferred(hipStream_t st) {
 }
 namespace {
 // Streams of host threads that have ended, per device.  A thread's stream is drained and parked here instead of being destroyed: a batch
-// that ran on it (TCV_STREAM_THREAD, the native estimator) may still hold the handle in tcv_batch::streams / last_stream, and a
+// that ran on it (TCV_STREAM_THREAD, the native estimator) may still hold the handle in BatchFlight::streams / last_stream, and a
 // hipStreamSynchronize / hipEventRecord on a destroyed stream is an error (round-4 advisor finding).  The next new thread takes a parked
 // stream over, so the process never holds more streams than it had live threads at once -- which is what keeps two LIVE threads off one
 // hardware queue (see above).  Leaked on purpose, like the device pool.

@@ -54,6 +54,8 @@ int staged_upload(void *d_dst, const void *src, size_t bytes, const char *what);
 // (pre-integration, line association, gauge fix, the factor evaluators) launch there and wait for THAT stream, never for the device --
 // another host thread's batches keep running (several estimator groups per GPU, bench.py --mode replay)
 hipStream_t util_stream();
+// the stream argument of an asynchronous entry point (include/tcv.h): TCV_STREAM_THREAD is the calling thread's stream, anything else a hipStream_t
+inline hipStream_t resolve_stream(void *hip_stream) { return hip_stream == TCV_STREAM_THREAD ? util_stream() : (hipStream_t)hip_stream; }
 // the calling thread's second stream (created at first use): the native estimator runs a frame's marginalisation there, beside the next
 // frame's association and upload on the thread's main stream
 hipStream_t aux_stream();

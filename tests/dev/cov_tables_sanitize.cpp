@@ -96,7 +96,7 @@ int main() {
             }
         // request tables of a one-window batch (nothing but the host maps of the batch is read)
         tcv_batch b;
-        b.n = 1; b.problems.push_back(p); b.packed.push_back(pk); b.plans.push_back(H); b.wins.push_back(pk.win);
+        b.in.n = 1; b.in.problems.push_back(p); b.in.packed.push_back(pk); b.in.plans.push_back(H); b.in.wins.push_back(pk.win);
         const tcv_covariance_block rq[4] = {{TCV_COV_POSE, -1, TCV_COV_POSE, -1}, {TCV_COV_POSE, -1, TCV_COV_SPEED_BIAS, -1}, {TCV_COV_EXTRINSIC, 0, TCV_COV_POSE, 0},
                                             {TCV_COV_SPEED_BIAS, 1, TCV_COV_SPEED_BIAS, 1}};
         std::vector<int> tab, rows, cols;
