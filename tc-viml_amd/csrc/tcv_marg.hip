@@ -1117,6 +1117,928 @@ __device__ __noinline__ void fwd_small_regs(const lds_d *Mm_, const lds_d *Apk_,
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// marg_kernel, one window: the carve and the phases, in the order the kernel calls them.  Every phase is inlined into the kernel (the
+// functions above are the ones that were separated on purpose); each header names what the phase reads, what it leaves where, which LDS
+// regions it may overwrite and where the workgroup stands relative to its barriers on entry and on exit ("behind a barrier": every
+// thread has passed one since the last LDS access of the phase before).
+// ------------------------------------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) MargHdr cst_mh;
+typedef __attribute__((address_space(3))) unsigned char lds_b;
+
+// One window's view of its plan, its LDS and its outputs; built once per window by marg_carve, read-only afterwards.
+struct MargWin {
+    cst_mh &H;
+    cst_i *ip, *blk;                // the plan's ints; its block table (MargHdr::o_blk)
+    cst_d *dp, *misc;               // the window's doubles; gravity, sqrt_info, loss, td constants (MargHdr::d_misc)
+    int tid, pos, m, n, npk;        // npk: entries of the packed lower triangle of A
+    int me, ne, r1, ldm, ldn;       // m, n rounded up to even; doubles of region P; row strides of Mm / Vm and of A'
+    lds_d *lds, *Apk, *R2, *Mm, *Vm, *bv, *x, *rot, *lam, *cvec, *lmacc, *sm, *stage;
+    lds_i *cnt;
+    gbl_d *out, *scr;               // the window's result block; the workgroup's scratch in HBM
+};
+
+// LDS carve (marg_lds_layout() in tcv_marg_host.cpp is the host's copy of this arithmetic: change the two together).  P: the prior's J0 while J0'J0 is formed, then the packed lower
+// triangle of A, then A' and finally its eigenvectors V2.  R2: the factor staging records, then Amm + V, then the reflectors of
+// the tridiagonalisation of A'.
+// Reads the header only; touches no LDS and no barrier.
+__device__ __forceinline__ MargWin marg_carve(cst_mh &H, const MargArgs &Aarg, lds_d *lds, gbl_d *scr, int win, int tid) {
+    MargWin W = {H};
+    W.ip = (cst_i *)Aarg.ipool + H.ibase; W.blk = W.ip + H.o_blk;
+    W.dp = (cst_d *)Aarg.dpool + H.dbase; W.misc = W.dp + H.d_misc;
+    W.tid = tid; W.pos = H.pos; W.m = H.m; W.n = H.n;
+    const int pos = W.pos, m = W.m, n = W.n;
+    W.npk = pos * (pos + 1) / 2;
+    W.lds = lds;
+    W.Apk = lds;
+    const int me = W.me = m + (m & 1), ne = W.ne = n + (n & 1);
+    const int r1 = W.r1 = max(W.npk, ne * (ne + 1));
+    W.R2 = lds + ((r1 + 1) & ~1);
+    const int cb_in_r2 = (H.cb_off >= 0 && H.cb_off >= ((r1 + 1) & ~1)) ? MARG_CB_LM * H.cb_stride + 2 * MARG_CB_LM : 0;      // C behind the staging records
+    const int r2 = max(max((int)MARG_STAGE + cb_in_r2, me * (me + 1) + max(me * (me + 1), m * (n + 1))), (n - 2) * (n - 1) / 2 + 1);
+    W.bv = W.R2 + ((r2 + 1) & ~1);                      // pos
+    W.x = W.bv + MARG_MAX_POS;                          // nx
+    W.rot = W.x + ((H.nx + 7) & ~7);                    // 160
+    W.lam = W.rot + 160;                                // MARG_MAX_N
+    W.cvec = W.lam + MARG_MAX_N;                        // block mode: the current landmark's coupling to the camera columns
+    W.lmacc = W.cvec + MARG_MAX_POS;                    // its diagonal and gradient
+    W.sm = W.lmacc + 8;                                 // MARG_SM: vectors of the eigen-solver; the prior's dx and residual before
+    W.stage = W.R2;                                     // 64 proj records or 1 imu record
+    W.cnt = (lds_i *)(W.rot + 158);
+    W.ldm = me + 1; W.Mm = W.R2; W.Vm = W.R2 + me * W.ldm;      // Amm and its eigenvectors V; on the Cholesky route Z (m x (n + 1)) takes V's place
+    W.ldn = ne + 1;                                     // A' and later its eigenvectors V2, both at Apk
+    W.out = (gbl_d *)Aarg.out + (size_t)win * MARG_OUT_STRIDE;
+    W.scr = scr;
+    return W;
+}
+
+// State load: gathers the linearisation point x (the solve's result where the plan names one, else the plan's own copy), zeroes b, the
+// landmark vector cvec and lmacc, loads gravity.
+// Clobbers x, bv, cvec, lmacc.  Entry: behind the last barrier of the window before (whose carve may differ).  Exit: behind a barrier.
+template <int MARG_NT>
+__device__ __forceinline__ void marg_load_state(const MargWin &W, const MargArgs &Aarg, double (&G3)[3]) {
+    cst_mh &H = W.H;
+    cst_i *blk = W.blk;
+    cst_d *dp = W.dp;
+    lds_d *x = W.x, *bv = W.bv, *cvec = W.cvec, *lmacc = W.lmacc;
+    const int tid = W.tid, pos = W.pos;
+    for (int b = tid; b < H.nblk; b += MARG_NT) {
+        const int gs = blk[b * 5], go = blk[b * 5 + 1], xs = blk[b * 5 + 4];
+        for (int i = 0; i < gs; i++)
+            x[go + i] = (Aarg.use_solved_state && xs >= 0 && Aarg.solve_state)
+                            ? ((const gbl_d *)Aarg.solve_state)[(size_t)H.solve_window * Aarg.state_stride + xs + i]
+                            : dp[H.d_x + go + i];
+    }
+    for (int i = tid; i < pos; i += MARG_NT) { bv[i] = 0.0; cvec[i] = 0.0; }
+    if (tid < 8) lmacc[tid] = 0.0;
+    G3[0] = W.misc[0]; G3[1] = W.misc[1]; G3[2] = W.misc[2];
+    __syncthreads();
+}
+
+// Prior factor (MarginalizationFactor::Evaluate, :335-384): the first contribution to A and b.
+// Reads x, the prior's J0 | r0 | x0 (the solve batch's pool or the plan's own copy), o_prior, o_pcol.  Leaves the packed A (region P, Apk)
+// zeroed and then holding J0'J0, and b (bv) += J0' r.  in_lds: J0 fits region P and is staged there while the products are formed; they
+// wait in registers across the barrier after which P is zeroed and becomes A.  Otherwise A is zeroed first and the products read J0 from
+// HBM.  a_zeroed is the contract with the tail: whichever way was taken (or none: no prior) A is zeroed exactly once.
+// Clobbers P, bv, sm[0 .. 128 + nr) (the prior's dx and residual).  Entry: behind a barrier.  Exit: behind a barrier.
+template <int MARG_NT>
+__device__ __forceinline__ void marg_prior(const MargWin &W, const MargArgs &Aarg) {
+    cst_mh &H = W.H;
+    cst_i *ip = W.ip, *blk = W.blk;
+    cst_d *dp = W.dp;
+    lds_d *Apk = W.Apk, *bv = W.bv, *x = W.x, *sm = W.sm;
+    const int tid = W.tid, npk = W.npk, r1 = W.r1;
+    bool a_zeroed = false;
+    if (H.prior_n > 0) {
+        const int np = H.prior_n, k0 = H.prior_k0 >= 0 ? H.prior_k0 : ((cst_win *)Aarg.solve_win)[H.solve_window].prior_k0, nr = np - k0;      // J0 | r0 without their leading zero rows: nr x np, column-major
+        cst_d *J0 = H.prior_abs >= 0 ? (cst_d *)Aarg.solve_dpool + H.prior_abs : dp + H.d_prior, *r0 = J0 + nr * np, *x0 = r0 + nr;
+        lds_d *pdx = sm, *pr = sm + 128;
+        if (tid < H.prior_nblk) {
+            cst_i *pb = ip + H.o_prior + tid * 4;
+            const int gs = pb[2], ls = gs == 7 ? 6 : gs;
+            double x0v[16], xv[16], dxv[16];
+            for (int i = 0; i < 16; i++) { x0v[i] = (i < gs) ? x0[pb[3] + i] : 0.0; xv[i] = (i < gs) ? x[blk[pb[0] * 5 + 1] + i] : 0.0; }
+            prior_block_dx(xv, x0v, gs, dxv);
+            for (int i = 0; i < 16; i++) if (i < ls) pdx[pb[1] + i] = dxv[i];
+        }
+        cst_i *pcol = ip + H.o_pcol;
+        // J0 (np x np, column-major) staged in P (A is not started yet): r = r0 + J0 dx, J0' J0 and J0' r run out of LDS, the
+        // products wait in registers until the barrier after which P becomes the packed A
+        const bool in_lds = np <= MARG_MAX_N && nr * np <= r1;
+        lds_d *Js = Apk;
+        if (in_lds) {
+            for (int e = tid; e < nr * np; e += 4 * MARG_NT) {
+                double v4[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) if (e + k * MARG_NT < nr * np) v4[k] = J0[e + k * MARG_NT];
+#pragma unroll
+                for (int k = 0; k < 4; k++) if (e + k * MARG_NT < nr * np) Js[e + k * MARG_NT] = v4[k];
+            }
+        } else {
+            for (int i = tid; i < npk; i += MARG_NT) Apk[i] = 0.0;
+            a_zeroed = true;
+        }
+        __syncthreads();
+        if (tid < nr) {      // (row k0 + tid of the full matrix; the dropped rows have r = 0)
+            double r = r0[tid];
+            if (in_lds) {
+                int j = 0;
+                for (; j + 3 < np; j += 4) {
+                    double a4[4], d4[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { a4[u] = Js[tid + nr * (j + u)]; d4[u] = pdx[j + u]; }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) r += a4[u] * d4[u];
+                }
+                for (; j < np; j++) r += Js[tid + nr * j] * pdx[j];
+            }
+            else for (int j = 0; j < np; j++) r += J0[tid + nr * j] * pdx[j];
+            pr[tid] = r;
+        }
+        __syncthreads();
+        if (in_lds) {
+            // J0' J0 on the matrix cores: 16 x 16 output tiles of the lower triangle (at most 15 for np <= 80: four per wavefront
+            // with 256 threads), v_mfma_f64_16x16x4 over the rows of J0 (column-major in LDS: J0[i + np a]); rows beyond np contribute zeros
+            typedef double v4f64 __attribute__((ext_vector_type(4)));
+            constexpr int NWV = MARG_NT / 64;
+            const int nt16 = (np + 15) >> 4, lane = tid & 63, wave = tid >> 6;
+            const int m16 = lane & 15, k4 = lane >> 4;
+            v4f64 accs[4];
+#pragma unroll
+            for (int slot = 0; slot < 4; slot++) {
+                const int t = wave + slot * NWV;
+                v4f64 acc = {0.0, 0.0, 0.0, 0.0};
+                if (t < nt16 * (nt16 + 1) / 2) {
+                    int ta = 0;
+                    while ((ta + 1) * (ta + 2) / 2 <= t) ta++;
+                    const int tb = t - ta * (ta + 1) / 2;
+                    const int a = 16 * ta + m16, b = 16 * tb + m16;
+                    // (the K steps keep the row quads of the FULL matrix -- i is the original row index, the dropped rows feed zeros and the
+                    // trips that hold nothing else are skipped --, so every sum is accumulated exactly as with the zero rows in place)
+                    const lds_d *ca = Js + nr * min(a, np - 1), *cb = Js + nr * min(b, np - 1);
+                    for (int i0 = k0 & ~15; i0 < np; i0 += 16) {
+                        double av[4], bv4[4];
+#pragma unroll
+                        for (int u = 0; u < 4; u++) {
+                            const int i = i0 + 4 * u + k4, ic = max(0, min(i, np - 1) - k0);
+                            const double xa = ca[ic], y = cb[ic];
+                            av[u] = (i >= k0 && i < np && a < np) ? xa : 0.0; bv4[u] = (i >= k0 && i < np && b < np) ? y : 0.0;
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; u++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv4[u], acc, 0, 0, 0);
+                    }
+                }
+                accs[slot] = acc;
+            }
+            double s2 = 0;
+            const bool mine = tid < np && pcol[min(tid, np - 1)] >= 0;
+            if (mine) {
+                int i = 0;
+                for (; i + 3 < nr; i += 4) {
+                    double a4[4], r4[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { a4[u] = Js[i + u + nr * tid]; r4[u] = pr[i + u]; }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) s2 += a4[u] * r4[u];
+                }
+                for (; i < nr; i++) s2 += Js[i + nr * tid] * pr[i];
+            }
+            __syncthreads();      // every read of the staged J0 is done: P becomes A
+            for (int i = tid; i < npk; i += MARG_NT) Apk[i] = 0.0;
+            a_zeroed = true;
+            __syncthreads();
+#pragma unroll
+            for (int slot = 0; slot < 4; slot++) {
+                const int t = wave + slot * NWV;
+                if (t < nt16 * (nt16 + 1) / 2) {
+                    int ta = 0;
+                    while ((ta + 1) * (ta + 2) / 2 <= t) ta++;
+                    const int tb = t - ta * (ta + 1) / 2;
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {      // acc[i] = G[16 ta + 4 i + k4][16 tb + m16]
+                        const int ga = 16 * ta + 4 * i + k4, gb = 16 * tb + m16;
+                        if (ga < np && gb <= ga) { const int ia = pcol[ga], ib = pcol[gb]; if (ia >= 0 && ib >= 0) Apk[pidx(ia, ib)] += accs[slot][i]; }
+                    }
+                }
+            }
+            if (mine) bv[pcol[tid]] += s2;
+        } else {
+            for (int e = tid; e < np * np; e += MARG_NT) {
+                const int a = e / np, b = e - a * np;
+                if (b > a) continue;
+                const int ia = pcol[a], ib = pcol[b];
+                if (ia < 0 || ib < 0) continue;
+                double s0 = 0;
+                for (int i = 0; i < nr; i++) s0 += J0[i + nr * a] * J0[i + nr * b];
+                Apk[pidx(ia, ib)] += s0;
+            }
+            if (tid < np && pcol[tid] >= 0) {
+                double s2 = 0;
+                for (int i = 0; i < nr; i++) s2 += J0[i + nr * tid] * pr[i];
+                bv[pcol[tid]] += s2;
+            }
+        }
+        __syncthreads();
+    }
+    if (!a_zeroed) {
+        for (int i = tid; i < npk; i += MARG_NT) Apk[i] = 0.0;
+        __syncthreads();
+    }
+}
+
+// ---- projection factors in chunks of at most 64: evaluated in parallel into staging records, then accumulated on one of three paths
+// point records: [18 pose columns | inverse depth | r | td (ProjectionTdFactor only)] per residual row
+struct ProjRec {
+    bool with_td;
+    int prs, prr;      // doubles per residual row and per record
+    int njc;           // Jacobian columns; logical column k lives at record column (k == 19 ? 20 : k)
+};
+__device__ __forceinline__ ProjRec proj_rec(cst_mh &H) {
+    const bool with_td = H.td_blk >= 0;
+    return {with_td, with_td ? 21 : (int)PROJ_STRIDE, with_td ? 43 : (int)PROJ_REC, with_td ? 20 : 19};
+}
+// entry t of a factor record -> (ca, cb): the lower triangle of the Jacobian columns (ca >= cb) row by row, then one entry per column
+// against the residual, which is given the column index rescol
+__device__ __forceinline__ void rec_entry(int t, int ntri, int rescol, int &ca, int &cb) {
+    if (t < ntri) { ca = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5); while ((ca + 1) * (ca + 2) / 2 <= t) ca++; while (ca * (ca + 1) / 2 > t) ca--; cb = t - ca * (ca + 1) / 2; }
+    else { ca = t - ntri; cb = rescol; }
+}
+// Evaluates point factor f (ProjectionFactor, or ProjectionTdFactor with_td) at x, applies the loss and writes its staging record rec.
+// One thread per factor; reads x and the plan, writes only rec; no barrier.
+__device__ __forceinline__ void proj_stage_factor(const MargWin &W, bool with_td, int f, lds_d *rec) {
+    cst_mh &H = W.H;
+    cst_i *blk = W.blk, *pf = W.ip + H.o_proj + f * 4;
+    cst_d *dp = W.dp, *misc = W.misc;
+    lds_d *x = W.x;
+    double r[2], pts[6];
+    if (with_td) {
+        double aux[8], Jl[40];
+#pragma unroll
+        for (int i = 0; i < 6; i++) pts[i] = dp[H.d_proj + f * 14 + i];
+#pragma unroll
+        for (int i = 0; i < 8; i++) aux[i] = dp[H.d_proj + f * 14 + 6 + i];
+        proj_td_eval(CGEN(x + blk[pf[0] * 5 + 1]), CGEN(x + blk[pf[1] * 5 + 1]), CGEN(x + blk[pf[2] * 5 + 1]), x[blk[pf[3] * 5 + 1]],
+                     x[blk[H.td_blk * 5 + 1]], pts, aux, misc[3], misc[6], misc[7], r, Jl, 20);
+        (void)loss_correct2(r, Jl, 20, 20, misc[4]);
+        for (int row = 0; row < 2; row++) {
+            for (int c2 = 0; c2 < 19; c2++) rec[row * 21 + c2] = Jl[row * 20 + c2];
+            rec[row * 21 + 19] = r[row]; rec[row * 21 + 20] = Jl[row * 20 + 19];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 6; i++) pts[i] = dp[H.d_proj + f * 6 + i];
+        proj_eval(CGEN(x + blk[pf[0] * 5 + 1]), CGEN(x + blk[pf[1] * 5 + 1]), CGEN(x + blk[pf[2] * 5 + 1]), x[blk[pf[3] * 5 + 1]],
+                  pts, misc[3], r, GEN(rec), PROJ_STRIDE);
+        (void)loss_correct2(r, GEN(rec), 19, PROJ_STRIDE, misc[4]);
+        rec[19] = r[0]; rec[PROJ_STRIDE + 19] = r[1];
+    }
+}
+
+// Chunked block path, elimination of one chunk's landmarks: A -= C' diag(1 / hll) C over the lower triangle (pseudo-inverse: a landmark
+// without information, hll <= eps, contributes nothing), 16 x 16 tiles on the matrix cores, K = the chunk's landmarks; b -= C' diag(1 / hll) gl.
+// Reads C (MARG_CB_LM rows of stride cbs at Cb), hll and gl behind it.  Writes A and b only.  Entry: behind the barrier that ends the
+// chunk's accumulation.  Exit: no barrier; the caller places it.
+template <int MARG_NT>
+__device__ __forceinline__ void proj_chunk_eliminate(const MargWin &W, const lds_d *Cb, int cbs) {
+    const lds_d *hl = Cb + MARG_CB_LM * cbs, *glv = hl + MARG_CB_LM;
+    lds_d *Apk = W.Apk, *bv = W.bv;
+    const int tid = W.tid, pos = W.pos;
+    typedef double v4f64 __attribute__((ext_vector_type(4)));
+    constexpr int NWV = MARG_NT / 64;
+    const int lane = tid & 63, wave = tid >> 6, col = lane & 15, row0 = lane >> 4;
+    const int nt16 = (pos + 15) >> 4;
+    double ih[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; kk++) { const double h = hl[4 * kk + row0]; ih[kk] = h > 1e-8 ? 1.0 / h : 0.0; }
+    for (int t = wave; t < nt16 * (nt16 + 1) / 2; t += NWV) {
+        int I = 0;
+        while ((I + 1) * (I + 2) / 2 <= t) I++;
+        const int J = t - I * (I + 1) / 2;
+        double av[4], bw[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) { const lds_d *row = Cb + (4 * kk + row0) * cbs; av[kk] = row[16 * I + col] * ih[kk]; bw[kk] = row[16 * J + col]; }
+        v4f64 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kk], bw[kk], acc, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int ra2 = 16 * I + row0 + 4 * i, cc = 16 * J + col;
+            if (ra2 < pos && cc <= ra2) Apk[pidx(ra2, cc)] -= acc[i];
+        }
+    }
+    if (tid < pos) {
+        double sb = 0.0;
+        for (int l = 0; l < MARG_CB_LM; l++) { const double h = hl[l]; sb += Cb[l * cbs + tid] * (glv[l] * (h > 1e-8 ? 1.0 / h : 0.0)); }
+        bv[tid] -= sb;
+    }
+}
+
+// Projection, chunked block path (block mode with room for C: MargHdr::cb_off >= 0): all point factors of the window, in the plan's chunks
+// of whole landmarks.  Per chunk: evaluation, accumulation of J'J / J'r as independent tasks, one rank-16 update that eliminates the
+// chunk's landmarks.
+// Reads x and the plan's chunk, group and landmark tables.  Leaves A and b with every point factor added and the eliminated landmarks'
+// Schur complements subtracted.
+// Clobbers the staging records, C | hll | gl at lds + cb_off (in region P behind A, or in R2 behind the records), cvec (as the per-factor
+// destination words ftab) and sm[0 .. 400) (tables: the eigen-solver's vector area, idle until the eigen-decomposition).
+// Entry: behind a barrier.  Exit: behind a barrier.
+template <int MARG_NT>
+__device__ __forceinline__ void marg_proj_chunked(const MargWin &W, const ProjRec &PR) {
+    cst_mh &H = W.H;
+    cst_i *ip = W.ip, *blk = W.blk;
+    lds_d *lds = W.lds, *Apk = W.Apk, *bv = W.bv, *stage = W.stage;
+    gbl_d *out = W.out;
+    const int tid = W.tid, pos = W.pos, prs = PR.prs, prr = PR.prr;
+#ifdef TCV_PROFILE
+    long long t_sub = clock64();
+#endif
+    MARG_SUB(0);
+    // the current chunk's group table, the entries of the factor record by class (see the accumulation below)
+    lds_i *gtab = (lds_i *)W.sm, *ncls = gtab + 336;
+    lds_b *listS = (lds_b *)(gtab + 340), *listJ = listS + 96, *listL = listJ + 104;
+    if (tid < 3) ncls[tid] = 0;
+    __syncthreads();
+    const int ntri = 19 * 20 / 2;
+    if (tid < ntri + 19) {
+        int ca, cb;
+        rec_entry(tid, ntri, 19, ca, cb);
+        const int ga = ca < 18 ? ca / 6 : 3, gb = cb < 18 ? cb / 6 : 3;
+        const int cls = ca == 18 ? 2 : ((ga == 1 || (cb < 18 && gb == 1)) ? 1 : 0);
+        const int at = atomicAdd((int *)(ncls + cls), 1);      // (which thread later takes which entry does not matter: entries are independent)
+        (cls == 0 ? listS : (cls == 1 ? listJ : listL))[at] = (unsigned char)tid;
+    }
+    __syncthreads();
+    for (int pc = 0; pc < H.n_pchunk; pc++) {
+        cst_i *pch = ip + H.o_pchunk + pc * 4;
+        const int f0 = pch[0], fn = pch[1];
+        lds_d *Cb = lds + H.cb_off, *hl = Cb + MARG_CB_LM * H.cb_stride, *glv = hl + MARG_CB_LM;
+        lds_i *ftab = (lds_i *)W.cvec;      // (the per-landmark vector of the factor-by-factor path below: unused on this path, 144 doubles >= 128 ints)
+        const int cbs = H.cb_stride;
+        for (int i = tid; i < MARG_CB_LM * cbs + 2 * MARG_CB_LM; i += MARG_NT) Cb[i] = 0.0;
+        {      // the chunk's group table (MargHdr::o_pgrp) into LDS
+            cst_i *gsrc = ip + H.o_pgrp + pch[3];
+            const int glen = gsrc[3];
+            for (int i = tid; i < glen; i += MARG_NT) gtab[i] = gsrc[i];
+        }
+        if (tid < fn) {
+            cst_i *pf = ip + H.o_proj + (f0 + tid) * 4;
+            proj_stage_factor(W, false, f0 + tid, stage + tid * prr);      // (no ProjectionTdFactor on this path: tcv_marg_host.cpp)
+            // where the factor's four blocks and its landmark go, for the accumulation below: one LDS word pair per factor (tangent offset + 1
+            // of the blocks, a byte each -- MARG_MAX_POS < 255 --, 0 = constant / dropped from this matrix; eliminated landmark's row of C + 1)
+            // instead of nine dependent loads from the plan per factor and thread (a 512-factor replay window: accumulation 497 K -> 352 K cycles,
+            // 0.59 -> 0.52 ms per marginalisation; what is left is the per-factor bookkeeping of 209 threads, not the loads: pre-evaluating all
+            // factors in one pass and walking the factors frame by frame were both measured and changed nothing)
+            unsigned wq = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) wq |= (unsigned)((blk[pf[k] * 5 + 2] + 1) & 255) << (8 * k);
+            ftab[2 * tid] = (int)wq;
+            ftab[2 * tid + 1] = ip[H.o_plm + f0 + tid] + 1;
+        }
+        __syncthreads();
+        MARG_SUB(1);
+        {
+            // Accumulation of the chunk's J'J / J'r: every element of A, b, C, hll, gl receives its terms in factor order (the sums of the
+            // factor-by-factor path, bit for bit), but the elements are independent, and which factors reach an element is known from the
+            // plan: entries of the 19 x 20 factor record (ca >= cb, or cb = the residual column) come in three classes --
+            //   S  both columns in the first pose / the extrinsic: one element for every factor of the chunk when they all share those blocks
+            //      (MARGIN_OLD: the host frame is frame 0) -- a plain sum over the chunk;
+            //   J  a column in the second pose: the element depends on that pose only -- one task per (frame, entry) over the frame's factors;
+            //   L  the inverse-depth row: one task per (landmark, entry) over the landmark's factors.
+            // ~1 300 short tasks on all eight wavefronts instead of 209 threads walking every factor (a 512-factor replay window: 352 K ->
+            // ~90 K cycles of the marginalisation's 1.2 M).
+            const int nfr = gtab[0], nlg = gtab[1], uniform = gtab[2];
+            const lds_i *fr = gtab + 4, *lg = fr + 2 * nfr, *fl = lg + 2 * nlg;
+            const int nS = ncls[0], nJ = ncls[1], nL = ncls[2];
+            const int secS = (nS + 63) & ~63, secJ = (nfr * nJ + 63) & ~63, secL = nlg * nL;
+            const int o_bv = (int)(bv - lds), o_cb = (int)(Cb - lds), o_hl = (int)(hl - lds), o_gl = (int)(glv - lds);
+            for (int task = tid; task < secS + secJ + secL; task += MARG_NT) {
+                int t, kind, g0 = 0, cnt = fn;
+                if (task < secS) { if (task >= nS) continue; kind = 0; t = listS[task]; }
+                else if (task < secS + secJ) {
+                    const int q = task - secS;
+                    if (q >= nfr * nJ) continue;
+                    const int sfr = q / nJ;
+                    kind = 1; t = listJ[q - sfr * nJ]; g0 = fr[2 * sfr]; cnt = fr[2 * sfr + 1];
+                } else {
+                    const int q = task - secS - secJ, sl = q / nL;
+                    kind = 2; t = listL[q - sl * nL]; g0 = lg[2 * sl]; cnt = lg[2 * sl + 1];
+                }
+                int ca, cb;
+                rec_entry(t, ntri, 19, ca, cb);
+                const int ga = ca < 18 ? ca / 6 : 3, oa = ca < 18 ? ca % 6 : 0;
+                const int gb = cb < 18 ? cb / 6 : 3, ob = cb < 18 ? cb % 6 : 0;
+                const int rb = cb == 19 ? 19 : cb;      // record column of cb (19 = the residual)
+                // destination of factor f's term as an offset from the workgroup's LDS base (>= 0; -1: a constant / dropped block).  Row 18
+                // (the inverse depth) of a factor whose landmark is eliminated goes to the landmark's row of C / hll / gl instead of A.
+                auto dest = [&](int f) -> int {
+                    const unsigned w = (unsigned)ftab[2 * f];
+                    const int lml = ftab[2 * f + 1] - 1;
+                    const int la = (int)((w >> (8 * ga)) & 255u) - 1, lb = (int)((w >> (8 * gb)) & 255u) - 1;
+                    if (ca == 18 && lml >= 0) {      // (18, column of a camera block) -> C, (18, 18) -> hll, (18, residual) -> gl
+                        if (cb < 18) return lb >= 0 ? o_cb + lml * cbs + lb + ob : -1;
+                        return (cb == 18 ? o_hl : o_gl) + lml;
+                    }
+                    if (la >= 0 && (cb == 19 || lb >= 0)) return cb == 19 ? o_bv + la + oa : pidx(la + oa, lb + ob);
+                    return -1;
+                };
+                // With the first pose and the extrinsic shared by the chunk's factors a task has ONE element -- the frame's (J), the landmark's
+                // (L, except its couplings to the second pose: one element per factor) or the chunk's (S): a plain sum, four record
+                // entries in flight
+                if (uniform && !(kind == 2 && cb < 18 && gb == 1)) {
+                    const int d = dest(kind == 1 ? fl[g0] : g0);
+                    if (d < 0) continue;
+                    double accv = lds[d];
+                    int k = 0;
+                    for (; k + 3 < cnt; k += 4) {
+                        double s4[4];
+#pragma unroll
+                        for (int u = 0; u < 4; u++) {
+                            const int f = kind == 1 ? fl[g0 + k + u] : g0 + k + u;
+                            const lds_d *rec = stage + f * prr;
+                            s4[u] = rec[ca] * rec[rb] + rec[prs + ca] * rec[prs + rb];
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; u++) accv += s4[u];
+                    }
+                    for (; k < cnt; k++) {
+                        const int f = kind == 1 ? fl[g0 + k] : g0 + k;
+                        const lds_d *rec = stage + f * prr;
+                        accv += rec[ca] * rec[rb] + rec[prs + ca] * rec[prs + rb];
+                    }
+                    lds[d] = accv;
+                    continue;
+                }
+                int prev = -1;
+                double accv = 0.0;
+                for (int k = 0; k < cnt; k++) {
+                    const int f = kind == 1 ? fl[g0 + k] : g0 + k;
+                    const lds_d *rec = stage + f * prr;
+                    const double sv = rec[ca] * rec[rb] + rec[prs + ca] * rec[prs + rb];
+                    const int d = dest(f);
+                    if (d < 0) continue;
+                    if (d != prev) {
+                        if (prev >= 0) lds[prev] = accv;
+                        accv = lds[d];
+                        prev = d;
+                    }
+                    accv += sv;
+                }
+                if (prev >= 0) lds[prev] = accv;
+            }
+        }
+        __syncthreads();
+        MARG_SUB(2);
+        proj_chunk_eliminate<MARG_NT>(W, Cb, cbs);
+        __syncthreads();
+        MARG_SUB(3);
+    }
+}
+
+// Projection, disjoint path (MargHdr::proj_disjoint, not block mode), one staged chunk of fn factors from factor f0: thread t owns entry
+// (ca >= cb, or cb = residual) of the factor record for every factor of the chunk, in factor order: the same sums as the factor-by-factor
+// path, bit for bit, without its barrier per factor.  The running destination stays in a register while consecutive factors hit the
+// same element (the anchor pose, the extrinsics, one landmark's factors).
+// Reads the staging records and the plan.  Writes A and b only.  Entry: behind the barrier after the staging.  Exit: behind a barrier.
+template <int MARG_NT>
+__device__ __forceinline__ void marg_proj_entries(const MargWin &W, const ProjRec &PR, int f0, int fn) {
+    cst_mh &H = W.H;
+    cst_i *ip = W.ip, *blk = W.blk;
+    lds_d *Apk = W.Apk, *bv = W.bv, *stage = W.stage;
+    const int tid = W.tid, prs = PR.prs, prr = PR.prr, njc = PR.njc;
+    constexpr int D_BV = MARG_MAX_POS * MARG_MAX_POS;      // destination d: entry d of the packed A, or b[d - D_BV]
+    auto flush = [&](int d, double v) { if (d >= D_BV) bv[d - D_BV] = v; else Apk[d] = v; };
+    const int ntri = njc * (njc + 1) / 2;
+    for (int t = tid; t < ntri + njc; t += MARG_NT) {
+        int ca, cb;
+        rec_entry(t, ntri, njc, ca, cb);
+        const int ga = ca < 18 ? ca / 6 : (ca == 18 ? 3 : 4), oa = ca < 18 ? ca % 6 : 0;
+        const int gb = cb < 18 ? cb / 6 : (cb == 18 ? 3 : 4), ob = cb < 18 ? cb % 6 : 0;
+        const int ra = ca == 19 ? 20 : ca, rb = cb == njc ? 19 : (cb == 19 ? 20 : cb);
+        const int ltd = PR.with_td ? blk[H.td_blk * 5 + 2] : -1;
+        int prev = -1;
+        double accv = 0.0;
+        for (int f = 0; f < fn; f++) {
+            cst_i *pf = ip + H.o_proj + (f0 + f) * 4;
+            const int l0 = blk[pf[0] * 5 + 2], l1 = blk[pf[1] * 5 + 2], l2 = blk[pf[2] * 5 + 2], l3 = blk[pf[3] * 5 + 2];
+            const int la = ga == 0 ? l0 : (ga == 1 ? l1 : (ga == 2 ? l2 : (ga == 3 ? l3 : ltd)));
+            const int lb = gb == 0 ? l0 : (gb == 1 ? l1 : (gb == 2 ? l2 : (gb == 3 ? l3 : ltd)));
+            const lds_d *rec = stage + f * prr;
+            const double sv = rec[ra] * rec[rb] + rec[prs + ra] * rec[prs + rb];
+            const int d = (la < 0 || (cb != njc && lb < 0)) ? -1 : (cb == njc ? D_BV + la + oa : pidx(la + oa, lb + ob));
+            if (d < 0) continue;
+            if (d != prev) {
+                if (prev >= 0) flush(prev, accv);
+                accv = d >= D_BV ? bv[d - D_BV] : Apk[d];
+                prev = d;
+            }
+            accv += sv;
+        }
+        if (prev >= 0) flush(prev, accv);
+    }
+    __syncthreads();
+}
+
+// Projection, factor-by-factor path (every other window: factors that are not disjoint, TCV_MARG_PROJ_SERIAL, block mode with
+// ProjectionTdFactors or under TCV_MARG_BLOCK_SERIAL), one staged chunk of fn factors from factor f0: all threads add one factor's J'J / J'r at a time.
+// Block mode: the inverse-depth row goes to cvec / lmacc, and behind the last factor of a landmark (MargHdr::o_plast) its 1 x 1 block
+// is eliminated by a scalar pivot.
+// Reads the staging records and the plan.  Writes A and b; cvec and lmacc are zero on entry and zero again on exit.
+// Entry: behind the barrier after the staging.  Exit: behind a barrier.
+template <int MARG_NT>
+__device__ __forceinline__ void marg_proj_factors(const MargWin &W, const ProjRec &PR, int f0, int fn) {
+    cst_mh &H = W.H;
+    cst_i *ip = W.ip, *blk = W.blk;
+    lds_d *Apk = W.Apk, *bv = W.bv, *cvec = W.cvec, *lmacc = W.lmacc, *stage = W.stage;
+    const int tid = W.tid, pos = W.pos, prs = PR.prs, prr = PR.prr, njc = PR.njc;
+    for (int f = 0; f < fn; f++) {
+        cst_i *pf = ip + H.o_proj + (f0 + f) * 4;
+        const lds_d *rec = stage + f * prr;
+        for (int e = tid; e < njc * (njc + 1); e += MARG_NT) {
+            const int ca = e / (njc + 1), cb = e - ca * (njc + 1);   // cb == njc: residual column
+            if (cb < njc && cb > ca) continue;
+            // block and offset of a logical Jacobian column: 0..17 the three poses, 18 the inverse depth, 19 Td
+            const int ba = ca < 18 ? pf[ca / 6] : (ca == 18 ? pf[3] : H.td_blk), oa = ca < 18 ? ca % 6 : 0;
+            const int ra = ca == 19 ? 20 : ca, rb = cb == njc ? 19 : (cb == 19 ? 20 : cb);
+            const int la = blk[ba * 5 + 2];
+            const double s = rec[ra] * rec[rb] + rec[prs + ra] * rec[prs + rb];
+            if (H.block_mode && ca == 18) {
+                // the landmark's row: coupling to the camera columns, its diagonal and its gradient
+                if (cb == 18) lmacc[0] += s;
+                else if (cb == njc) lmacc[1] += s;
+                else { const int bb = cb < 18 ? pf[cb / 6] : H.td_blk, lb = blk[bb * 5 + 2]; if (lb >= 0) cvec[lb + (cb < 18 ? cb % 6 : 0)] += s; }
+                continue;
+            }
+            if (H.block_mode && ca == 19 && cb == 18) {      // Td row meets the landmark column: same coupling, transposed
+                if (la >= 0) cvec[la] += s;
+                continue;
+            }
+            if (la < 0) continue;
+            const int ia = la + oa;
+            if (cb == njc) { bv[ia] += s; continue; }
+            const int bb = cb < 18 ? pf[cb / 6] : (cb == 18 ? pf[3] : H.td_blk);
+            const int lb = blk[bb * 5 + 2];
+            if (lb < 0) continue;
+            Apk[pidx(ia, lb + (cb < 18 ? cb % 6 : 0))] += s;
+        }
+        __syncthreads();
+        if (H.block_mode && ip[H.o_plast + f0 + f]) {
+            // Schur complement of the 1 x 1 landmark block (pseudo-inverse: a landmark without information contributes nothing)
+            const double d = lmacc[0], g = lmacc[1], invd = d > 1e-8 ? 1.0 / d : 0.0;
+            for (int e = tid; e < pos * pos; e += MARG_NT) {
+                const int i = e / pos, j = e - i * pos;
+                if (j > i) continue;
+                const double ci = cvec[i], cj = cvec[j];
+                if (ci != 0.0 && cj != 0.0) Apk[pidx(i, j)] -= ci * cj * invd;
+            }
+            if (tid < pos) bv[tid] -= cvec[tid] * g * invd;
+            __syncthreads();
+            for (int i = tid; i < pos; i += MARG_NT) cvec[i] = 0.0;
+            if (tid == 0) { lmacc[0] = 0.0; lmacc[1] = 0.0; }
+            __syncthreads();
+        }
+    }
+}
+
+// Projection phase: picks the path.  The chunked block path takes the whole window; the other two share the staging of 64 factors at a
+// time (one thread per factor, then a barrier) and differ in how a staged chunk is accumulated.
+// Leaves A and b complete (block mode: with the marginalised landmarks eliminated).  Clobbers what its paths clobber.
+// Entry: behind a barrier.  Exit: behind a barrier.
+template <int MARG_NT>
+__device__ __forceinline__ void marg_projection(const MargWin &W) {
+    cst_mh &H = W.H;
+    const int tid = W.tid;
+    const ProjRec PR = proj_rec(H);
+#ifdef TCV_PROFILE
+    if (tid == 0) for (int i = 0; i < 4; i++) W.out[MARG_DIAG_PROJ_SUB + i] = 0.0;
+#endif
+    if (H.block_mode && H.cb_off >= 0) { marg_proj_chunked<MARG_NT>(W, PR); return; }
+    const bool by_entry = H.proj_disjoint && !H.block_mode;
+    for (int f0 = 0; f0 < H.n_proj; f0 += 64) {
+        const int fn = min(64, H.n_proj - f0);
+        if (tid < fn) proj_stage_factor(W, PR.with_td, f0 + tid, W.stage + tid * PR.prr);
+        __syncthreads();
+        if (by_entry) marg_proj_entries<MARG_NT>(W, PR, f0, fn);
+        else marg_proj_factors<MARG_NT>(W, PR, f0, fn);
+    }
+}
+
+// Mm <- Amm, the dropped block of the packed A unpacked to m x m with row stride ldm.  No barrier.
+template <int MARG_NT>
+__device__ __forceinline__ void amm_unpack(const MargWin &W) {
+    const int m = W.m, ldm = W.ldm;
+    for (int i = W.tid; i < m * m; i += MARG_NT) { const int r = i / m, c = i - r * m; W.Mm[r * ldm + c] = W.Apk[pidx(r, c)]; }
+}
+// The proof of rank behind the forward substitutions: rot[j] = |L^-1 e_j|^2, so tr = trace(Amm^-1) and lambda_min >= 1 / tr > 1e-8
+// (false for NaN).  Every thread computes the same sum; the diagnostics keep tr and its unit-diagonal scaling.
+__device__ __forceinline__ bool amm_trace_proof(const MargWin &W) {
+    double tr = 0, trs = 0;
+    for (int j = 0; j < W.m; j++) { tr += W.rot[j]; trs += W.rot[j] * W.Apk[pidx(j, j)]; }
+    if (W.tid == 0) { W.out[MARG_DIAG_AMM_TRACE] = tr; W.out[MARG_DIAG_AMM_TRACE + 1] = trs; }
+    return tr < 1e8;
+}
+
+// Route of Amm^+ (marginalization_factor.cpp:267-272: eigen-decomposition, eigenvalues <= eps dropped).  When every eigenvalue is
+// provably above eps the pseudo-inverse IS the inverse, and Arm Amm^-1 Amr = Z'Z with Z = L^-1 Amr from the Cholesky factor
+// Amm = L L' -- 23 dependent column steps on one wavefront instead of ~100 Jacobi rounds of three barriers each.  Proof of rank
+// per window: lambda_min >= 1 / trace(Amm^-1) = 1 / |L^-1|_F^2 > eps.  Otherwise (a landmark without parallax, a prior
+// that does not constrain the dropped pose) the eigen form of marg_schur runs.
+// Reads the packed A and b.  Returns the one decision chol.  chol: Z = L^-1 [Amr | bmm] (m x (n + 1), row stride n + 1) stands at Vm.
+// Not chol: Mm holds Amm again unless the Cholesky attempt overwrote it (eig_mm == 0: marg_schur copies it once more).
+// Clobbers R2 (Mm, Vm), rot[0 .. m), lmacc[2].  Entry: behind a barrier.  Exit: behind a barrier.
+template <int MARG_NT>
+__device__ __forceinline__ bool marg_amm_route(const MargWin &W, int eig_mm, long long &t_last) {
+    lds_d *Apk = W.Apk, *bv = W.bv, *Mm = W.Mm, *rot = W.rot, *lmacc = W.lmacc;
+    lds_d *Zl = W.Vm;                                   // Cholesky path: Z (m x (n + 1), last column L^-1 bmm) in LDS
+    gbl_d *out = W.out;
+    const int tid = W.tid, m = W.m, n = W.n, ldm = W.ldm, zs = n + 1;
+    amm_unpack<MARG_NT>(W);
+    __syncthreads();
+    bool chol = eig_mm == 0;
+    constexpr int MREG = 24;      // dropped sets of at most 24 dims (a pose, a speed-bias and up to nine landmarks; block mode: 15): in registers
+    if (chol && m <= MREG) {
+        // right-looking in registers, lane = row: entry (i, c) takes its subtractions L_ip L_cp in the order p = 0, 1, ... of the left-looking
+        // loop below (same products, same fused operations: the same bits), pivot column broadcast with v_readlane -- no LDS round trip
+        // on the 23 dependent column steps.  One basic block (steps k >= m work on zero rows behind selects, only their stores are
+        // guarded), so that the trailing update of a step is scheduled into the 1 / sqrt chain of the next one.
+        chol_small_regs<MREG>(Mm, lmacc + 2, m, ldm, tid);
+        MARG_MARK(9);
+        __syncthreads();
+        MARG_MARK(10);
+        chol = lmacc[2] != 0.0;
+    } else
+    if (chol) {
+        if (tid < 64) {      // left-looking Cholesky, lane = row; the diagonal keeps 1 / L_kk
+            const int i = min(tid, m - 1);
+            bool ok = true;
+            for (int k = 0; k < m; k++) {
+                double sv = Mm[i * ldm + k], sd = Mm[k * ldm + k];
+                int p2 = 0;
+                for (; p2 + 3 < k; p2 += 4) {      // four steps' loads in flight, the updates in the original order
+                    double lk[4], li[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { lk[u] = Mm[k * ldm + p2 + u]; li[u] = Mm[i * ldm + p2 + u]; }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { sv -= li[u] * lk[u]; sd -= lk[u] * lk[u]; }
+                }
+                for (; p2 < k; p2++) { const double lk = Mm[k * ldm + p2]; sv -= Mm[i * ldm + p2] * lk; sd -= lk * lk; }
+                ok = ok && (sd > 0.0) && (sd < 1e300);
+                const double rs = 1.0 / sqrt(ok ? sd : 1.0);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                if (tid < m && tid > k) Mm[tid * ldm + k] = sv * rs;
+                if (tid == k) Mm[k * ldm + k] = rs;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            }
+            if (tid == 0) lmacc[2] = ok ? 1.0 : 0.0;
+        }
+        __syncthreads();
+        chol = lmacc[2] != 0.0;
+    }
+    if (chol && m <= MREG) {
+        // forward substitutions, one thread per right-hand side (the n columns of Amr, bmm, the m unit vectors for |L^-1|_F^2), the
+        // solution in registers: z_k' -= L_k'k z_k as soon as z_k is final -- per entry the subtractions of the loop below in its order --
+        // with L read as broadcasts; nothing waits for its own stores.  Branch-free but for the stores: a guard per entry makes every load
+        // of L wait out its own LDS round trip (45 K cycles instead of 8 K); rows k >= m compute on clamped loads and are never stored.
+        fwd_small_regs<MREG>(Mm, Apk, bv, Zl, rot, m, n, ldm, zs, tid);
+        MARG_MARK(11);
+        __syncthreads();
+        chol = amm_trace_proof(W);
+    } else
+    if (chol) {
+        // forward substitutions L z = rhs, one thread per right-hand side: the n columns of Amr, bmm, and the m unit vectors whose
+        // solutions give |L^-1|_F^2 (kept in the unused upper triangle of Mm)
+        if (tid < n + 1) {
+            const int j = tid;
+            for (int k = 0; k < m; k++) {
+                double sv = j < n ? Apk[pidx(m + j, k)] : bv[k];
+                int p2 = 0;
+                for (; p2 + 3 < k; p2 += 4) {
+                    double lk[4], zz[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { lk[u] = Mm[k * ldm + p2 + u]; zz[u] = Zl[(p2 + u) * zs + j]; }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) sv -= lk[u] * zz[u];
+                }
+                for (; p2 < k; p2++) sv -= Mm[k * ldm + p2] * Zl[p2 * zs + j];
+                Zl[k * zs + j] = sv * Mm[k * ldm + k];
+            }
+        } else if (tid < n + 1 + m) {
+            const int j = tid - n - 1;
+            double y = Mm[j * ldm + j], nn = y * y;       // y_j = 1 / L_jj
+            lds_d *yr = Mm + j * ldm;                       // y_k for k > j at Mm[j][k]
+            for (int k = j + 1; k < m; k++) {
+                double sv = -Mm[k * ldm + j] * y;
+                for (int p2 = j + 1; p2 < k; p2++) sv -= Mm[k * ldm + p2] * yr[p2];
+                sv *= Mm[k * ldm + k];
+                yr[k] = sv;
+                nn += sv * sv;
+            }
+            rot[j] = nn;
+        }
+        __syncthreads();
+        chol = amm_trace_proof(W);
+    }
+    return chol;
+}
+
+// A' in registers between marg_schur and marg_write_back: entries per thread, for all n x n entries over the workgroup
+template <int MARG_NT> constexpr int MARG_KEEP = (MARG_MAX_N * MARG_MAX_N + MARG_NT - 1) / MARG_NT;
+// The lower triangle of an n x n matrix folded into ((n + 1) >> 1) lines of n + 1 entries: rows R and n - 1 - R share a line.  Entry e of
+// the rectangle -> (i, j), j <= i (the second half of the middle line of an odd n repeats entries of its first half: harmless duplicates)
+__device__ __forceinline__ void folded_tri(int e, int n, int &i, int &j) {
+    const int R = e / (n + 1), Cc = e - R * (n + 1);
+    i = (Cc <= R) ? R : n - 1 - R; j = (Cc <= R) ? Cc : Cc - R - 1;
+}
+
+// Schur complement A' = Arr - Arm Amm^+ Amr, b' = brr - Arm Amm^+ bmm into registers, in one of two forms.
+// chol: from Z at Vm (marg_amm_route); keepA holds the folded lower triangle (folded_tri).  Not chol: Amm = V diag(lam) V' by jacobi_eig
+// (Mm, Vm), Z = diag(sqrt(lam^+)) V' Amr and its right-hand side in the workgroup's HBM scratch (MARG_SCR_Z, MARG_SCR_PR); keepA holds all
+// n x n entries, entry e = tid + q MARG_NT at keepA[q].  bprime is b'[tid] for tid < n.  Returns the Jacobi sweeps of Amm (0: chol).
+// Reads the packed A and b, which stay intact.  Clobbers (not chol) Mm, Vm, rot, cnt, lam[0 .. m) and the scratch.
+// Entry: behind a barrier.  Exit: NOT behind a barrier, reads of A, b, Z in flight: marg_write_back opens with the barrier.
+template <int MARG_NT>
+__device__ __forceinline__ int marg_schur(const MargWin &W, bool chol, int eig_mm, double (&keepA)[MARG_KEEP<MARG_NT>], double &bprime, long long &t_last) {
+    lds_d *Apk = W.Apk, *bv = W.bv, *Mm = W.Mm, *Vm = W.Vm, *rot = W.rot, *lam = W.lam;
+    lds_d *Zl = W.Vm;
+    gbl_d *out = W.out, *Z = W.scr + MARG_SCR_Z, *zb = W.scr + MARG_SCR_PR;
+    const int tid = W.tid, m = W.m, n = W.n, ldm = W.ldm, zs = n + 1;
+    int sweeps1 = 0;
+    bprime = 0;
+    if (chol) {
+        MARG_MARK(4);
+        MARG_MARK(5);
+        // A' = Arr - Z'Z, b' = brr - Z' zb: held in registers until every read of the packed A is done, then written over it
+        // (only the lower triangle, folded: entry (j, i) is the same difference of the same products as (i, j), bit for bit, and is
+        // mirrored when the registers are written back)
+        int q = 0;
+        for (int e = tid; e < ((n + 1) >> 1) * (n + 1); e += MARG_NT, q++) {
+            int i, j;
+            folded_tri(e, n, i, j);
+            double sv = Apk[pidx(m + i, m + j)];
+            int k = 0;
+            for (; k + 3 < m; k += 4) {      // four steps' loads in flight, the updates in the original order
+                double za[4], zb4[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) { za[u] = Zl[(k + u) * zs + i]; zb4[u] = Zl[(k + u) * zs + j]; }
+#pragma unroll
+                for (int u = 0; u < 4; u++) sv -= za[u] * zb4[u];
+            }
+            for (; k < m; k++) sv -= Zl[k * zs + i] * Zl[k * zs + j];
+            keepA[q] = sv;
+        }
+        if (tid < n) {
+            bprime = bv[m + tid];
+            for (int k = 0; k < m; k++) bprime -= Zl[k * zs + tid] * Zl[k * zs + n];
+        }
+    } else {
+        // ---- Amm = V diag(lam) V'
+        if (eig_mm == 0) {      // the Cholesky attempt overwrote Mm
+            __syncthreads();
+            amm_unpack<MARG_NT>(W);
+            __syncthreads();
+        }
+        sweeps1 = jacobi_eig<MARG_NT, lds_d>(Mm, Vm, m, ldm, rot, W.cnt, tid, 0.0);
+        MARG_MARK(4);
+        if (tid < m) { const double l = Mm[tid * ldm + tid]; lam[tid] = l > 1e-8 ? sqrt(1.0 / l) : 0.0; }
+        __syncthreads();
+        // Z = diag(sqrt(lam^+)) V' Amr  (m x n) and zb = diag(sqrt(lam^+)) V' bmm, kept in global scratch
+        for (int e = tid; e < m * n; e += MARG_NT) {
+            const int k = e / n, j = e - k * n;
+            double sv = 0;
+            for (int p2 = 0; p2 < m; p2++) sv += Vm[p2 * ldm + k] * Apk[pidx(m + j, p2)];
+            Z[k * n + j] = lam[k] * sv;
+        }
+        if (tid < m) {
+            double sv = 0;
+            for (int p2 = 0; p2 < m; p2++) sv += Vm[p2 * ldm + tid] * bv[p2];
+            zb[tid] = lam[tid] * sv;
+        }
+        __syncthreads();
+        MARG_MARK(5);
+        int q = 0;
+        for (int e = tid; e < n * n; e += MARG_NT, q++) {
+            const int i = e / n, j = e - i * n;
+            double sv = Apk[pidx(m + i, m + j)];
+            for (int k = 0; k < m; k++) sv -= Z[k * n + i] * Z[k * n + j];
+            keepA[q] = sv;
+        }
+        if (tid < n) {
+            bprime = bv[m + tid];
+            for (int k = 0; k < m; k++) bprime -= Z[k * n + tid] * zb[k];
+        }
+    }
+    return sweeps1;
+}
+
+// Write-back of A' (n x n, row stride ldn, at the start of region P) and b' (bv[0 .. n)), and their copies in the result block.
+// folded: keepA holds the folded lower triangle (the Cholesky form of marg_schur) instead of all n x n entries.
+// Opens with the barrier that licenses the overwrite: behind it every read marg_schur made of the packed A, of b and of Vm is done, so P
+// and R2 can be overwritten.  Clobbers P and bv.  Exit: behind a barrier.
+template <int MARG_NT>
+__device__ __forceinline__ void marg_write_back(const MargWin &W, bool folded, const double (&keepA)[MARG_KEEP<MARG_NT>], double bprime) {
+    lds_d *As = W.Apk, *bv = W.bv;
+    gbl_d *out = W.out;
+    const int tid = W.tid, n = W.n, ldn = W.ldn;
+    __syncthreads();   // every read of Vm / Apk is done: P and R2 can be overwritten
+    {
+        int q = 0;
+        if (folded) {
+            for (int e = tid; e < ((n + 1) >> 1) * (n + 1); e += MARG_NT, q++) {
+                int i, j;
+                folded_tri(e, n, i, j);
+                As[i * ldn + j] = keepA[q]; As[j * ldn + i] = keepA[q];
+                out[MARG_OUT_AS + i * n + j] = keepA[q]; out[MARG_OUT_AS + j * n + i] = keepA[q];
+            }
+        } else
+        for (int e = tid; e < n * n; e += MARG_NT, q++) {
+            const int i = e / n, j = e - i * n;
+            As[i * ldn + j] = keepA[q];
+            out[MARG_OUT_AS + i * n + j] = keepA[q];
+        }
+    }
+    if (tid < n) { bv[tid] = bprime; out[MARG_OUT_BS + tid] = bprime; }
+    __syncthreads();
+}
+
+// A' = V2 diag(lam) V2': tridiagonal path first, Jacobi sweep as the safety net (its eigenvector matrix in HBM scratch, MARG_SCR_V,
+// copied over the diagonalised A' at the end: the LDS holds one n x n matrix).
+// Reads A' in P (the safety net reads it once more from the result block).  Leaves the eigenvectors V2 in its place (column k at
+// V2[j * ldn + k]) and the eigenvalues in lam[0 .. n).  Returns 0, or 100 + the Jacobi sweeps of the safety net.
+// Clobbers P, R2 (reflectors), sm, rot, cnt.  Entry: behind a barrier.  Exit: NOT behind a barrier (lam and, on the safety net, V2 just
+// written): marg_output opens with it.
+template <int MARG_NT>
+__device__ __forceinline__ int marg_eig_kept(const MargWin &W, int eig_flags) {
+    lds_d *As = W.Apk, *V2 = W.Apk, *R2 = W.R2, *sm = W.sm, *rot = W.rot, *lam = W.lam;
+    lds_i *cnt = W.cnt;
+    gbl_d *out = W.out, *scr = W.scr;
+    const int tid = W.tid, n = W.n, ldn = W.ldn;
+    int sweeps2 = 0;
+    {
+        const bool ok = sym_eig_tridiag<MARG_NT>(As, R2, sm, rot, n, ldn, tid, out + MARG_DIAG_EIG_CHECK, eig_flags, scr + MARG_SCR_V);    // rot: 160 doubles >= n eigenvalues
+        if (ok) {
+            if (tid < n) lam[tid] = rot[tid];
+        } else {
+            gbl_d *Vg = scr + MARG_SCR_V;
+            for (int e = tid; e < n * n; e += MARG_NT) { const int i2 = e / n, j2 = e - i2 * n; As[i2 * ldn + j2] = out[MARG_OUT_AS + i2 * n + j2]; }
+            __syncthreads();
+            sweeps2 = 100 + jacobi_eig<MARG_NT, gbl_d>(As, Vg, n, ldn, rot, cnt, tid, 2.3e-16, out + MARG_DIAG_PHASE + 9);
+            if (tid < n) lam[tid] = As[tid * ldn + tid];
+            __syncthreads();
+            for (int e = tid; e < n * n; e += MARG_NT) { const int i2 = e / n, j2 = e - i2 * n; V2[i2 * ldn + j2] = Vg[i2 * ldn + j2]; }
+        }
+    }
+    return sweeps2;
+}
+
+// Output and status: J0 | r0 = sqrt(S) V2' | sqrt(S^+) V2' b' with the rows in the order of the eigenvalues, the linearisation point x,
+// the count of leading zero rows (status word nwin + win; -1: a NaN in the result), the status word win and the sweep diagnostics.
+// Reads V2 (P), b' (bv), lam, x.  Writes the result block and the two status words only.
+// Entry: NOT behind a barrier (opens with it).  Exit: behind the window's last barrier, with no LDS access after it (see below).
+template <int MARG_NT>
+__device__ __forceinline__ void marg_output(const MargWin &W, const MargArgs &Aarg, int win, int sweeps1, int sweeps2, long long &t_last) {
+    cst_mh &H = W.H;
+    lds_d *V2 = W.Apk, *bv = W.bv, *lam = W.lam, *x = W.x;
+    gbl_d *out = W.out;
+    const int tid = W.tid, n = W.n, ldn = W.ldn;
+    __syncthreads();
+    bool bad = false;     // a NaN in J0 | r0 (the host path scans the downloaded J0 for it)
+    if (tid < n) {
+        const double l = lam[tid];
+        int rank = 0;
+        for (int j = 0; j < n; j++) rank += (lam[j] < l || (lam[j] == l && j < tid)) ? 1 : 0;
+        const double S = l > 1e-8 ? l : 0.0, Sinv = l > 1e-8 ? 1.0 / l : 0.0;
+        const double ss = sqrt(S), si = sqrt(Sinv);
+        double rb = 0;
+        for (int j = 0; j < n; j++) {
+            const double v = V2[j * ldn + tid];
+            out[MARG_OUT_J0 + rank + n * j] = ss * v;
+            rb += v * bv[j];
+        }
+        out[MARG_OUT_R0 + rank] = si * rb;
+        // (a NaN or Inf anywhere in the eigenvector reaches rb -- NaN * 0 is NaN -- and from there si * rb, thresholded row or not)
+        if (!(si * rb == si * rb) || !(l == l)) bad = true;
+    }
+    // what a device-resident consumer of this prior needs on the host (tcv_batch_get_priors_device): the number of leading rows of
+    // J0 | r0 that are exact zeros -- the thresholded eigenvalues rank first and their rows are 0 * v --, capped like
+    // tcv_packed.h prior_zero_rows() (one row is kept); -1: the result holds a NaN.
+    // Nothing of the window's LDS is read behind its last barrier: the other wavefronts are in the next window of the loop by then,
+    // whose carve-up of the LDS (r1 / r2 / nx differ between MARGIN_OLD and SECOND_NEW windows) puts x[] / bv[] / cvec[] over this
+    // window's lam[] (round-4 advisor finding).  The count is taken here -- lam[] is final since the barrier above --, stored by lane 0
+    // BEFORE the barrier, and a thread that saw a NaN overwrites it with -1 BEHIND the barrier from its register (no LDS flag, and NOT
+    // __syncthreads_or, whose work-group reduction brings a static LDS variable -- 80 KiB + 4 bytes per workgroup is one workgroup per
+    // CU instead of two: 0.85 -> 1.40 ms per 1024 windows, measured).
+    if (tid < 64) {      // (the first wavefront counts, two eigenvalues per lane: n <= 80)
+        const bool z0 = tid < n && !(lam[tid] > 1e-8), z1 = tid + 64 < n && !(lam[tid + 64] > 1e-8);
+        int k0 = __popcll(__ballot(z0)) + __popcll(__ballot(z1));
+        if (k0 >= n) k0 = n > 0 ? n - 1 : 0;
+        if (tid == 0) ((gbl_i *)Aarg.out_status)[Aarg.nwin + win] = k0;
+    }
+    for (int i = tid; i < H.nx; i += MARG_NT) out[MARG_OUT_X + i] = x[i];
+    MARG_MARK(8);
+    if (tid == 0) ((gbl_i *)Aarg.out_status)[win] = (sweeps1 >= 24 || sweeps2 == 124) ? 1 : (sweeps2 >= 100 ? 2 : 0);   // 1: a Jacobi sweep hit its cap, 2: A' went through the Jacobi safety net
+    if (tid == 0) { out[MARG_DIAG_SWEEPS_MM] = sweeps1; out[MARG_DIAG_SWEEPS_RR] = sweeps2; }
+    __syncthreads();
+    if (bad) ((gbl_i *)Aarg.out_status)[Aarg.nwin + win] = -1;      // (ordered behind lane 0's store by the barrier)
+}
+
 #ifndef TCV_MARG_WAVES      // wavefronts per SIMD (developer A/B build `build.py --suffix=margocc1 -DTCV_MARG_WAVES=1`: one, 512 registers, no VGPR spill)
 #define TCV_MARG_WAVES 2
 #endif
@@ -1127,800 +2049,90 @@ __global__ void __launch_bounds__(MARG_NT) __attribute__((disable_tail_calls)) _
     const int tid = threadIdx.x;
     gbl_d *scr = (gbl_d *)Aarg.scratch + (size_t)blockIdx.x * MARG_SCR_STRIDE;
     for (int win = blockIdx.x; win < Aarg.nwin; win += gridDim.x) {
-        typedef const __attribute__((address_space(4))) MargHdr cst_mh;
         cst_mh &H = ((cst_mh *)Aarg.hdr)[win];
-        cst_i *ip = (cst_i *)Aarg.ipool + H.ibase;
-        cst_d *dp = (cst_d *)Aarg.dpool + H.dbase;
-        const int pos = H.pos, m = H.m, n = H.n;
         if (H.nblk == 0) {      // a window of the batch that is not marginalised (tcv_batch_create: marg_problems[w] == NULL): nothing to do
             if (tid == 0) { ((gbl_i *)Aarg.out_status)[win] = 0; ((gbl_i *)Aarg.out_status)[Aarg.nwin + win] = 0; }
             continue;
         }
-        const int npk = pos * (pos + 1) / 2;
-        // LDS carve (marg_lds_layout() in tcv_marg_host.cpp is the host's copy of this arithmetic: change the two together).  P: the prior's J0 while J0'J0 is formed, then the packed lower
-        // triangle of A, then A' and finally its eigenvectors V2.  R2: the factor staging records, then Amm + V, then the reflectors of
-        // the tridiagonalisation of A'.
-        lds_d *Apk = lds;
-        const int me = m + (m & 1), ne = n + (n & 1);
-        const int r1 = max(npk, ne * (ne + 1));
-        lds_d *R2 = lds + ((r1 + 1) & ~1);
-        const int cb_in_r2 = (H.cb_off >= 0 && H.cb_off >= ((r1 + 1) & ~1)) ? MARG_CB_LM * H.cb_stride + 2 * MARG_CB_LM : 0;      // C behind the staging records
-        const int r2 = max(max((int)MARG_STAGE + cb_in_r2, me * (me + 1) + max(me * (me + 1), m * (n + 1))), (n - 2) * (n - 1) / 2 + 1);
-        lds_d *bv = R2 + ((r2 + 1) & ~1);                   // pos
-        lds_d *x = bv + MARG_MAX_POS;                       // nx
-        lds_d *rot = x + ((H.nx + 7) & ~7);                 // 160
-        lds_d *lam = rot + 160;                             // MARG_MAX_N
-        lds_d *cvec = lam + MARG_MAX_N;                     // block mode: the current landmark's coupling to the camera columns
-        lds_d *lmacc = cvec + MARG_MAX_POS;                 // its diagonal and gradient
-        lds_d *sm = lmacc + 8;                              // MARG_SM: vectors of the eigen-solver; the prior's dx and residual before
-        lds_d *stage = R2;                                  // 64 proj records or 1 imu record
-        lds_i *cnt = (lds_i *)(rot + 158);
-        gbl_d *out = (gbl_d *)Aarg.out + (size_t)win * MARG_OUT_STRIDE;
+        const MargWin W = marg_carve(H, Aarg, lds, scr, win, tid);
+        gbl_d *out = W.out;
         long long t_last = clock64();
         if (tid == 0) for (int i = 0; i < 12; i++) out[MARG_DIAG_PHASE + i] = 0.0;
-
-        cst_i *blk = ip + H.o_blk;
-        for (int b = tid; b < H.nblk; b += MARG_NT) {
-            const int gs = blk[b * 5], go = blk[b * 5 + 1], xs = blk[b * 5 + 4];
-            for (int i = 0; i < gs; i++)
-                x[go + i] = (Aarg.use_solved_state && xs >= 0 && Aarg.solve_state)
-                                ? ((const gbl_d *)Aarg.solve_state)[(size_t)H.solve_window * Aarg.state_stride + xs + i]
-                                : dp[H.d_x + go + i];
-        }
-        for (int i = tid; i < pos; i += MARG_NT) { bv[i] = 0.0; cvec[i] = 0.0; }
-        if (tid < 8) lmacc[tid] = 0.0;
-        cst_d *misc = dp + H.d_misc;
-        const double G3[3] = {misc[0], misc[1], misc[2]};
-        __syncthreads();
-
+        double G3[3];
+        marg_load_state<MARG_NT>(W, Aarg, G3);
         MARG_MARK(0);
-        // ---- prior factor (MarginalizationFactor::Evaluate, :335-384): the first contribution to A and b
-        bool a_zeroed = false;
-        if (H.prior_n > 0) {
-            const int np = H.prior_n, k0 = H.prior_k0 >= 0 ? H.prior_k0 : ((cst_win *)Aarg.solve_win)[H.solve_window].prior_k0, nr = np - k0;      // J0 | r0 without their leading zero rows: nr x np, column-major
-            cst_d *J0 = H.prior_abs >= 0 ? (cst_d *)Aarg.solve_dpool + H.prior_abs : dp + H.d_prior, *r0 = J0 + nr * np, *x0 = r0 + nr;
-            lds_d *pdx = sm, *pr = sm + 128;
-            if (tid < H.prior_nblk) {
-                cst_i *pb = ip + H.o_prior + tid * 4;
-                const int gs = pb[2], ls = gs == 7 ? 6 : gs;
-                double x0v[16], xv[16], dxv[16];
-                for (int i = 0; i < 16; i++) { x0v[i] = (i < gs) ? x0[pb[3] + i] : 0.0; xv[i] = (i < gs) ? x[blk[pb[0] * 5 + 1] + i] : 0.0; }
-                prior_block_dx(xv, x0v, gs, dxv);
-                for (int i = 0; i < 16; i++) if (i < ls) pdx[pb[1] + i] = dxv[i];
-            }
-            cst_i *pcol = ip + H.o_pcol;
-            // J0 (np x np, column-major) staged in P (A is not started yet): r = r0 + J0 dx, J0' J0 and J0' r run out of LDS, the
-            // products wait in registers until the barrier after which P becomes the packed A
-            const bool in_lds = np <= MARG_MAX_N && nr * np <= r1;
-            lds_d *Js = Apk;
-            if (in_lds) {
-                for (int e = tid; e < nr * np; e += 4 * MARG_NT) {
-                    double v4[4];
-#pragma unroll
-                    for (int k = 0; k < 4; k++) if (e + k * MARG_NT < nr * np) v4[k] = J0[e + k * MARG_NT];
-#pragma unroll
-                    for (int k = 0; k < 4; k++) if (e + k * MARG_NT < nr * np) Js[e + k * MARG_NT] = v4[k];
-                }
-            } else {
-                for (int i = tid; i < npk; i += MARG_NT) Apk[i] = 0.0;
-                a_zeroed = true;
-            }
-            __syncthreads();
-            if (tid < nr) {      // (row k0 + tid of the full matrix; the dropped rows have r = 0)
-                double r = r0[tid];
-                if (in_lds) {
-                    int j = 0;
-                    for (; j + 3 < np; j += 4) {
-                        double a4[4], d4[4];
-#pragma unroll
-                        for (int u = 0; u < 4; u++) { a4[u] = Js[tid + nr * (j + u)]; d4[u] = pdx[j + u]; }
-#pragma unroll
-                        for (int u = 0; u < 4; u++) r += a4[u] * d4[u];
-                    }
-                    for (; j < np; j++) r += Js[tid + nr * j] * pdx[j];
-                }
-                else for (int j = 0; j < np; j++) r += J0[tid + nr * j] * pdx[j];
-                pr[tid] = r;
-            }
-            __syncthreads();
-            if (in_lds) {
-                // J0' J0 on the matrix cores: 16 x 16 output tiles of the lower triangle (at most 15 for np <= 80: four per wavefront
-                // with 256 threads), v_mfma_f64_16x16x4 over the rows of J0 (column-major in LDS: J0[i + np a]); rows beyond np contribute zeros
-                typedef double v4f64 __attribute__((ext_vector_type(4)));
-                constexpr int NWV = MARG_NT / 64;
-                const int nt16 = (np + 15) >> 4, lane = tid & 63, wave = tid >> 6;
-                const int m16 = lane & 15, k4 = lane >> 4;
-                v4f64 accs[4];
-#pragma unroll
-                for (int slot = 0; slot < 4; slot++) {
-                    const int t = wave + slot * NWV;
-                    v4f64 acc = {0.0, 0.0, 0.0, 0.0};
-                    if (t < nt16 * (nt16 + 1) / 2) {
-                        int ta = 0;
-                        while ((ta + 1) * (ta + 2) / 2 <= t) ta++;
-                        const int tb = t - ta * (ta + 1) / 2;
-                        const int a = 16 * ta + m16, b = 16 * tb + m16;
-                        // (the K steps keep the row quads of the FULL matrix -- i is the original row index, the dropped rows feed zeros and the
-                        // trips that hold nothing else are skipped --, so every sum is accumulated exactly as with the zero rows in place)
-                        const lds_d *ca = Js + nr * min(a, np - 1), *cb = Js + nr * min(b, np - 1);
-                        for (int i0 = k0 & ~15; i0 < np; i0 += 16) {
-                            double av[4], bv4[4];
-#pragma unroll
-                            for (int u = 0; u < 4; u++) {
-                                const int i = i0 + 4 * u + k4, ic = max(0, min(i, np - 1) - k0);
-                                const double xa = ca[ic], y = cb[ic];
-                                av[u] = (i >= k0 && i < np && a < np) ? xa : 0.0; bv4[u] = (i >= k0 && i < np && b < np) ? y : 0.0;
-                            }
-#pragma unroll
-                            for (int u = 0; u < 4; u++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv4[u], acc, 0, 0, 0);
-                        }
-                    }
-                    accs[slot] = acc;
-                }
-                double s2 = 0;
-                const bool mine = tid < np && pcol[min(tid, np - 1)] >= 0;
-                if (mine) {
-                    int i = 0;
-                    for (; i + 3 < nr; i += 4) {
-                        double a4[4], r4[4];
-#pragma unroll
-                        for (int u = 0; u < 4; u++) { a4[u] = Js[i + u + nr * tid]; r4[u] = pr[i + u]; }
-#pragma unroll
-                        for (int u = 0; u < 4; u++) s2 += a4[u] * r4[u];
-                    }
-                    for (; i < nr; i++) s2 += Js[i + nr * tid] * pr[i];
-                }
-                __syncthreads();      // every read of the staged J0 is done: P becomes A
-                for (int i = tid; i < npk; i += MARG_NT) Apk[i] = 0.0;
-                a_zeroed = true;
-                __syncthreads();
-#pragma unroll
-                for (int slot = 0; slot < 4; slot++) {
-                    const int t = wave + slot * NWV;
-                    if (t < nt16 * (nt16 + 1) / 2) {
-                        int ta = 0;
-                        while ((ta + 1) * (ta + 2) / 2 <= t) ta++;
-                        const int tb = t - ta * (ta + 1) / 2;
-#pragma unroll
-                        for (int i = 0; i < 4; i++) {      // acc[i] = G[16 ta + 4 i + k4][16 tb + m16]
-                            const int ga = 16 * ta + 4 * i + k4, gb = 16 * tb + m16;
-                            if (ga < np && gb <= ga) { const int ia = pcol[ga], ib = pcol[gb]; if (ia >= 0 && ib >= 0) Apk[pidx(ia, ib)] += accs[slot][i]; }
-                        }
-                    }
-                }
-                if (mine) bv[pcol[tid]] += s2;
-            } else {
-                for (int e = tid; e < np * np; e += MARG_NT) {
-                    const int a = e / np, b = e - a * np;
-                    if (b > a) continue;
-                    const int ia = pcol[a], ib = pcol[b];
-                    if (ia < 0 || ib < 0) continue;
-                    double s0 = 0;
-                    for (int i = 0; i < nr; i++) s0 += J0[i + nr * a] * J0[i + nr * b];
-                    Apk[pidx(ia, ib)] += s0;
-                }
-                if (tid < np && pcol[tid] >= 0) {
-                    double s2 = 0;
-                    for (int i = 0; i < nr; i++) s2 += J0[i + nr * tid] * pr[i];
-                    bv[pcol[tid]] += s2;
-                }
-            }
-            __syncthreads();
-        }
-        if (!a_zeroed) {
-            for (int i = tid; i < npk; i += MARG_NT) Apk[i] = 0.0;
-            __syncthreads();
-        }
+        marg_prior<MARG_NT>(W, Aarg);
         MARG_MARK(1);
-        // ---- IMU factors, one at a time (only the factor touching the marginalised frame is passed in)
-        cst_d *imu0 = H.imu_abs >= 0 ? (cst_d *)Aarg.solve_dpool + H.imu_abs : dp + H.d_imu;      // (the factor's constants: this problem's own copy, or the solve batch's)
-        for (int f = 0; f < H.n_imu; f++) {
-            cst_i *b = ip + H.o_imu + f * 4;
-            lds_d *S = stage + 1500;
-            // sqrt_info: the one the solve of this batch computed from the same covariance with the same code (bit-identical), else here
-            const bool s_given = Aarg.solve_sqrt != nullptr && H.sqrt_src >= 0 && H.n_imu == 1;
-            if (s_given) { for (int i = tid; i < 225; i += MARG_NT) S[i] = ((const gbl_d *)Aarg.solve_sqrt)[(size_t)H.solve_window * 225 + i]; }
-            else if (tid < 16) (void)imu_sqrt_info_group(imu0 + f * IMU_CONST + IMU_COV, S, stage + 512, stage + 512 + 225, tid);
-            // the four parts of the raw residual / Jacobian on four wavefronts: lane 0 of waves 1..4, or (256 threads) lane 32 of waves 0..3
-            constexpr int RW0 = MARG_NT >= 320 ? 1 : 0, RLANE = MARG_NT >= 320 ? 0 : 32;
-            if ((tid & 63) == RLANE && (tid >> 6) >= RW0 && (tid >> 6) < RW0 + 4) {
-                double cst[62];
+        // ---- IMU factors, one at a time (only the factor touching the marginalised frame is passed in).  Inline on purpose: as a function
+        // next to marg_projection this phase takes the kernel from 320 / 281 spilled VGPRs to about 1 000 and the scratch size above the budget
+        // (profiles/marg_kernel_phases.txt).
+        // Reads x, gravity G3, the factor's constants and, where the solve computed it, its sqrt_info.  Leaves A += J'J, b += J'r of each factor.
+        // Clobbers the staging records (R2: the raw 15 x 31 record at stage, scratch of the sqrt_info at stage + 512, sqrt_info at stage + 1500).
+        // Entry: behind a barrier, A zeroed or holding the prior's part.  Exit: behind a barrier (or nothing done: no IMU factor).
+        {
+            cst_i *ip = W.ip, *blk = W.blk;
+            cst_d *dp = W.dp;
+            lds_d *Apk = W.Apk, *bv = W.bv, *x = W.x, *stage = W.stage;
+            cst_d *imu0 = H.imu_abs >= 0 ? (cst_d *)Aarg.solve_dpool + H.imu_abs : dp + H.d_imu;      // (the factor's constants: this problem's own copy, or the solve batch's)
+            for (int f = 0; f < H.n_imu; f++) {
+                cst_i *b = ip + H.o_imu + f * 4;
+                lds_d *S = stage + 1500;
+                // sqrt_info: the one the solve of this batch computed from the same covariance with the same code (bit-identical), else here
+                const bool s_given = Aarg.solve_sqrt != nullptr && H.sqrt_src >= 0 && H.n_imu == 1;
+                if (s_given) { for (int i = tid; i < 225; i += MARG_NT) S[i] = ((const gbl_d *)Aarg.solve_sqrt)[(size_t)H.solve_window * 225 + i]; }
+                else if (tid < 16) (void)imu_sqrt_info_group(imu0 + f * IMU_CONST + IMU_COV, S, stage + 512, stage + 512 + 225, tid);
+                // the four parts of the raw residual / Jacobian on four wavefronts: lane 0 of waves 1..4, or (256 threads) lane 32 of waves 0..3
+                constexpr int RW0 = MARG_NT >= 320 ? 1 : 0, RLANE = MARG_NT >= 320 ? 0 : 32;
+                if ((tid & 63) == RLANE && (tid >> 6) >= RW0 && (tid >> 6) < RW0 + 4) {
+                    double cst[62];
 #pragma unroll
-                for (int i = 0; i < 62; i++) cst[i] = imu0[f * IMU_CONST + i];
-                imu_raw_part((tid >> 6) - RW0, CGEN(x + blk[b[0] * 5 + 1]), CGEN(x + blk[b[1] * 5 + 1]), CGEN(x + blk[b[2] * 5 + 1]),
-                             CGEN(x + blk[b[3] * 5 + 1]), cst, G3, GEN(stage), IMU_STRIDE_J, true);
-            }
-            __syncthreads();
-            if (tid < 31) {
-                lds_d *rec = stage + tid;
-                double v[15];
-                for (int r = 0; r < 15; r++) v[r] = rec[r * IMU_STRIDE_J];
-                for (int r = 0; r < 15; r++) {
-                    double a = 0;
-                    for (int s2 = r; s2 < 15; s2++) a += S[r * 15 + s2] * v[s2];
-                    rec[r * IMU_STRIDE_J] = a;
+                    for (int i = 0; i < 62; i++) cst[i] = imu0[f * IMU_CONST + i];
+                    imu_raw_part((tid >> 6) - RW0, CGEN(x + blk[b[0] * 5 + 1]), CGEN(x + blk[b[1] * 5 + 1]), CGEN(x + blk[b[2] * 5 + 1]),
+                                 CGEN(x + blk[b[3] * 5 + 1]), cst, G3, GEN(stage), IMU_STRIDE_J, true);
                 }
+                __syncthreads();
+                if (tid < 31) {
+                    lds_d *rec = stage + tid;
+                    double v[15];
+                    for (int r = 0; r < 15; r++) v[r] = rec[r * IMU_STRIDE_J];
+                    for (int r = 0; r < 15; r++) {
+                        double a = 0;
+                        for (int s2 = r; s2 < 15; s2++) a += S[r * 15 + s2] * v[s2];
+                        rec[r * IMU_STRIDE_J] = a;
+                    }
+                }
+                __syncthreads();
+                const int colc[4] = {0, 6, 15, 21};
+                for (int e = tid; e < 30 * 31; e += MARG_NT) {
+                    const int ca = e / 31, cb = e - ca * 31;   // cb == 30: residual column
+                    if (cb < 30 && cb > ca) continue;
+                    int sa = 0, sb = 0;
+                    while (sa < 3 && ca >= colc[sa + 1]) sa++;
+                    const int la = blk[b[sa] * 5 + 2];
+                    if (la < 0) continue;
+                    const int ia = la + ca - colc[sa];
+                    double s = 0;
+                    for (int r = 0; r < 15; r++) s += stage[r * IMU_STRIDE_J + ca] * stage[r * IMU_STRIDE_J + cb];
+                    if (cb == 30) { bv[ia] += s; continue; }
+                    while (sb < 3 && cb >= colc[sb + 1]) sb++;
+                    const int lb = blk[b[sb] * 5 + 2];
+                    if (lb < 0) continue;
+                    Apk[pidx(ia, lb + cb - colc[sb])] += s;
+                }
+                __syncthreads();
             }
-            __syncthreads();
-            const int colc[4] = {0, 6, 15, 21};
-            for (int e = tid; e < 30 * 31; e += MARG_NT) {
-                const int ca = e / 31, cb = e - ca * 31;   // cb == 30: residual column
-                if (cb < 30 && cb > ca) continue;
-                int sa = 0, sb = 0;
-                while (sa < 3 && ca >= colc[sa + 1]) sa++;
-                const int la = blk[b[sa] * 5 + 2];
-                if (la < 0) continue;
-                const int ia = la + ca - colc[sa];
-                double s = 0;
-                for (int r = 0; r < 15; r++) s += stage[r * IMU_STRIDE_J + ca] * stage[r * IMU_STRIDE_J + cb];
-                if (cb == 30) { bv[ia] += s; continue; }
-                while (sb < 3 && cb >= colc[sb + 1]) sb++;
-                const int lb = blk[b[sb] * 5 + 2];
-                if (lb < 0) continue;
-                Apk[pidx(ia, lb + cb - colc[sb])] += s;
-            }
-            __syncthreads();
         }
         MARG_MARK(2);
-        // ---- projection factors in chunks of 64: evaluate in parallel, accumulate one factor at a time
-        // point records: [18 pose columns | inverse depth | r | td (ProjectionTdFactor only)] per residual row
-        const bool with_td = H.td_blk >= 0;
-        const int prs = with_td ? 21 : (int)PROJ_STRIDE, prr = with_td ? 43 : (int)PROJ_REC;
-        const int njc = with_td ? 20 : 19;                    // Jacobian columns; logical column k lives at record column (k == 19 ? 20 : k)
-        const bool cb_path = H.block_mode && H.cb_off >= 0;
-#ifdef TCV_PROFILE
-        long long t_sub = clock64();
-        if (tid == 0) for (int i = 0; i < 4; i++) out[MARG_DIAG_PROJ_SUB + i] = 0.0;
-#endif
-        MARG_SUB(0);
-        // chunked block path: tables in the eigen-solver's vector area (idle until the eigen-decomposition): the current chunk's group table,
-        // the entries of the factor record by class (see the accumulation below)
-        typedef __attribute__((address_space(3))) unsigned char lds_b;
-        lds_i *gtab = (lds_i *)sm, *ncls = gtab + 336;
-        lds_b *listS = (lds_b *)(gtab + 340), *listJ = listS + 96, *listL = listJ + 104;
-        if (cb_path) {
-            if (tid < 3) ncls[tid] = 0;
-            __syncthreads();
-            const int ntri = 19 * 20 / 2;
-            if (tid < ntri + 19) {
-                int ca, cb;
-                if (tid < ntri) { ca = (int)((sqrt(8.0 * (double)tid + 1.0) - 1.0) * 0.5); while ((ca + 1) * (ca + 2) / 2 <= tid) ca++; while (ca * (ca + 1) / 2 > tid) ca--; cb = tid - ca * (ca + 1) / 2; }
-                else { ca = tid - ntri; cb = 19; }
-                const int ga = ca < 18 ? ca / 6 : 3, gb = cb < 18 ? cb / 6 : 3;
-                const int cls = ca == 18 ? 2 : ((ga == 1 || (cb < 18 && gb == 1)) ? 1 : 0);
-                const int at = atomicAdd((int *)(ncls + cls), 1);      // (which thread later takes which entry does not matter: entries are independent)
-                (cls == 0 ? listS : (cls == 1 ? listJ : listL))[at] = (unsigned char)tid;
-            }
-            __syncthreads();
-        }
-        for (int pc = 0; cb_path && pc < H.n_pchunk; pc++) {
-            cst_i *pch = ip + H.o_pchunk + pc * 4;
-            const int f0 = pch[0], fn = pch[1];
-            lds_d *Cb = lds + H.cb_off, *hl = Cb + MARG_CB_LM * H.cb_stride, *glv = hl + MARG_CB_LM;
-            lds_i *ftab = (lds_i *)cvec;      // (the per-landmark vector of the factor-by-factor path below: unused on this path, 144 doubles >= 128 ints)
-            const int cbs = H.cb_stride;
-            for (int i = tid; i < MARG_CB_LM * cbs + 2 * MARG_CB_LM; i += MARG_NT) Cb[i] = 0.0;
-            {      // the chunk's group table (MargHdr::o_pgrp) into LDS
-                cst_i *gsrc = ip + H.o_pgrp + pch[3];
-                const int glen = gsrc[3];
-                for (int i = tid; i < glen; i += MARG_NT) gtab[i] = gsrc[i];
-            }
-            if (tid < fn) {
-                cst_i *pf = ip + H.o_proj + (f0 + tid) * 4;
-                lds_d *rec = stage + tid * prr;
-                double r[2], pts[6];
-#pragma unroll
-                for (int i = 0; i < 6; i++) pts[i] = dp[H.d_proj + (f0 + tid) * 6 + i];
-                proj_eval(CGEN(x + blk[pf[0] * 5 + 1]), CGEN(x + blk[pf[1] * 5 + 1]), CGEN(x + blk[pf[2] * 5 + 1]), x[blk[pf[3] * 5 + 1]],
-                          pts, misc[3], r, GEN(rec), PROJ_STRIDE);
-                (void)loss_correct2(r, GEN(rec), 19, PROJ_STRIDE, misc[4]);
-                rec[19] = r[0]; rec[PROJ_STRIDE + 19] = r[1];
-                // where the factor's four blocks and its landmark go, for the accumulation below: one LDS word pair per factor (tangent offset + 1
-                // of the blocks, a byte each -- MARG_MAX_POS < 255 --, 0 = constant / dropped from this matrix; eliminated landmark's row of C + 1)
-                // instead of nine dependent loads from the plan per factor and thread (a 512-factor replay window: accumulation 497 K -> 352 K cycles,
-                // 0.59 -> 0.52 ms per marginalisation; what is left is the per-factor bookkeeping of 209 threads, not the loads: pre-evaluating all
-                // factors in one pass and walking the factors frame by frame were both measured and changed nothing)
-                unsigned wq = 0;
-#pragma unroll
-                for (int k = 0; k < 4; k++) wq |= (unsigned)((blk[pf[k] * 5 + 2] + 1) & 255) << (8 * k);
-                ftab[2 * tid] = (int)wq;
-                ftab[2 * tid + 1] = ip[H.o_plm + f0 + tid] + 1;
-            }
-            __syncthreads();
-            MARG_SUB(1);
-            {
-                // Accumulation of the chunk's J'J / J'r: every element of A, b, C, hll, gl receives its terms in factor order (the sums of the
-                // factor-by-factor path, bit for bit), but the elements are independent, and which factors reach an element is known from the
-                // plan: entries of the 19 x 20 factor record (ca >= cb, or cb = the residual column) come in three classes --
-                //   S  both columns in the first pose / the extrinsic: one element for every factor of the chunk when they all share those blocks
-                //      (MARGIN_OLD: the host frame is frame 0) -- a plain sum over the chunk;
-                //   J  a column in the second pose: the element depends on that pose only -- one task per (frame, entry) over the frame's factors;
-                //   L  the inverse-depth row: one task per (landmark, entry) over the landmark's factors.
-                // ~1 300 short tasks on all eight wavefronts instead of 209 threads walking every factor (a 512-factor replay window: 352 K ->
-                // ~90 K cycles of the marginalisation's 1.2 M).
-                const int nfr = gtab[0], nlg = gtab[1], uniform = gtab[2];
-                cst_i *dummy_plm = ip + H.o_plm + f0; (void)dummy_plm;
-                const lds_i *fr = gtab + 4, *lg = fr + 2 * nfr, *fl = lg + 2 * nlg;
-                const int nS = ncls[0], nJ = ncls[1], nL = ncls[2];
-                const int secS = (nS + 63) & ~63, secJ = (nfr * nJ + 63) & ~63, secL = nlg * nL;
-                const int o_bv = (int)(bv - lds), o_cb = (int)(Cb - lds), o_hl = (int)(hl - lds), o_gl = (int)(glv - lds);
-                for (int task = tid; task < secS + secJ + secL; task += MARG_NT) {
-                    int t, kind, g0 = 0, cnt = fn;
-                    if (task < secS) { if (task >= nS) continue; kind = 0; t = listS[task]; }
-                    else if (task < secS + secJ) {
-                        const int q = task - secS;
-                        if (q >= nfr * nJ) continue;
-                        const int sfr = q / nJ;
-                        kind = 1; t = listJ[q - sfr * nJ]; g0 = fr[2 * sfr]; cnt = fr[2 * sfr + 1];
-                    } else {
-                        const int q = task - secS - secJ, sl = q / nL;
-                        kind = 2; t = listL[q - sl * nL]; g0 = lg[2 * sl]; cnt = lg[2 * sl + 1];
-                    }
-                    const int ntri = 19 * 20 / 2;
-                    int ca, cb;
-                    if (t < ntri) { ca = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5); while ((ca + 1) * (ca + 2) / 2 <= t) ca++; while (ca * (ca + 1) / 2 > t) ca--; cb = t - ca * (ca + 1) / 2; }
-                    else { ca = t - ntri; cb = 19; }
-                    const int ga = ca < 18 ? ca / 6 : 3, oa = ca < 18 ? ca % 6 : 0;
-                    const int gb = cb < 18 ? cb / 6 : 3, ob = cb < 18 ? cb % 6 : 0;
-                    const int rb = cb == 19 ? 19 : cb;      // record column of cb (19 = the residual)
-                    // destination of factor f's term as an offset from the workgroup's LDS base (>= 0; -1: a constant / dropped block).  Row 18
-                    // (the inverse depth) of a factor whose landmark is eliminated goes to the landmark's row of C / hll / gl instead of A.
-                    auto dest = [&](int f) -> int {
-                        const unsigned w = (unsigned)ftab[2 * f];
-                        const int lml = ftab[2 * f + 1] - 1;
-                        const int la = (int)((w >> (8 * ga)) & 255u) - 1, lb = (int)((w >> (8 * gb)) & 255u) - 1;
-                        if (ca == 18 && lml >= 0) {      // (18, column of a camera block) -> C, (18, 18) -> hll, (18, residual) -> gl
-                            if (cb < 18) return lb >= 0 ? o_cb + lml * cbs + lb + ob : -1;
-                            return (cb == 18 ? o_hl : o_gl) + lml;
-                        }
-                        if (la >= 0 && (cb == 19 || lb >= 0)) return cb == 19 ? o_bv + la + oa : pidx(la + oa, lb + ob);
-                        return -1;
-                    };
-                    // With the first pose and the extrinsic shared by the chunk's factors a task has ONE element -- the frame's (J), the landmark's
-                    // (L, except its couplings to the second pose: one element per factor) or the chunk's (S): a plain sum, four record
-                    // entries in flight
-                    if (uniform && !(kind == 2 && cb < 18 && gb == 1)) {
-                        const int d = dest(kind == 1 ? fl[g0] : g0);
-                        if (d < 0) continue;
-                        double accv = lds[d];
-                        int k = 0;
-                        for (; k + 3 < cnt; k += 4) {
-                            double s4[4];
-#pragma unroll
-                            for (int u = 0; u < 4; u++) {
-                                const int f = kind == 1 ? fl[g0 + k + u] : g0 + k + u;
-                                const lds_d *rec = stage + f * prr;
-                                s4[u] = rec[ca] * rec[rb] + rec[prs + ca] * rec[prs + rb];
-                            }
-#pragma unroll
-                            for (int u = 0; u < 4; u++) accv += s4[u];
-                        }
-                        for (; k < cnt; k++) {
-                            const int f = kind == 1 ? fl[g0 + k] : g0 + k;
-                            const lds_d *rec = stage + f * prr;
-                            accv += rec[ca] * rec[rb] + rec[prs + ca] * rec[prs + rb];
-                        }
-                        lds[d] = accv;
-                        continue;
-                    }
-                    int prev = -1;
-                    double accv = 0.0;
-                    for (int k = 0; k < cnt; k++) {
-                        const int f = kind == 1 ? fl[g0 + k] : g0 + k;
-                        const lds_d *rec = stage + f * prr;
-                        const double sv = rec[ca] * rec[rb] + rec[prs + ca] * rec[prs + rb];
-                        const int d = dest(f);
-                        if (d < 0) continue;
-                        if (d != prev) {
-                            if (prev >= 0) lds[prev] = accv;
-                            accv = lds[d];
-                            prev = d;
-                        }
-                        accv += sv;
-                    }
-                    if (prev >= 0) lds[prev] = accv;
-                }
-            }
-            __syncthreads();
-            MARG_SUB(2);
-            {
-                // A -= C' diag(1 / hll) C over the lower triangle (pseudo-inverse: a landmark without information, hll <= eps, contributes
-                // nothing), 16 x 16 tiles on the matrix cores, K = the chunk's landmarks; b -= C' diag(1 / hll) gl
-                typedef double v4f64 __attribute__((ext_vector_type(4)));
-                constexpr int NWV = MARG_NT / 64;
-                const int lane = tid & 63, wave = tid >> 6, col = lane & 15, row0 = lane >> 4;
-                const int nt16 = (pos + 15) >> 4;
-                double ih[4];
-#pragma unroll
-                for (int kk = 0; kk < 4; kk++) { const double h = hl[4 * kk + row0]; ih[kk] = h > 1e-8 ? 1.0 / h : 0.0; }
-                for (int t = wave; t < nt16 * (nt16 + 1) / 2; t += NWV) {
-                    int I = 0;
-                    while ((I + 1) * (I + 2) / 2 <= t) I++;
-                    const int J = t - I * (I + 1) / 2;
-                    double av[4], bw[4];
-#pragma unroll
-                    for (int kk = 0; kk < 4; kk++) { const lds_d *row = Cb + (4 * kk + row0) * cbs; av[kk] = row[16 * I + col] * ih[kk]; bw[kk] = row[16 * J + col]; }
-                    v4f64 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int kk = 0; kk < 4; kk++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kk], bw[kk], acc, 0, 0, 0);
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        const int ra2 = 16 * I + row0 + 4 * i, cc = 16 * J + col;
-                        if (ra2 < pos && cc <= ra2) Apk[pidx(ra2, cc)] -= acc[i];
-                    }
-                }
-                if (tid < pos) {
-                    double sb = 0.0;
-                    for (int l = 0; l < MARG_CB_LM; l++) { const double h = hl[l]; sb += Cb[l * cbs + tid] * (glv[l] * (h > 1e-8 ? 1.0 / h : 0.0)); }
-                    bv[tid] -= sb;
-                }
-            }
-            __syncthreads();
-            MARG_SUB(3);
-        }
-        for (int f0 = 0; !cb_path && f0 < H.n_proj; f0 += 64) {
-            const int fn = min(64, H.n_proj - f0);
-            if (tid < fn) {
-                cst_i *pf = ip + H.o_proj + (f0 + tid) * 4;
-                lds_d *rec = stage + tid * prr;
-                double r[2], pts[6];
-                if (with_td) {
-                    double aux[8], Jl[40];
-#pragma unroll
-                    for (int i = 0; i < 6; i++) pts[i] = dp[H.d_proj + (f0 + tid) * 14 + i];
-#pragma unroll
-                    for (int i = 0; i < 8; i++) aux[i] = dp[H.d_proj + (f0 + tid) * 14 + 6 + i];
-                    proj_td_eval(CGEN(x + blk[pf[0] * 5 + 1]), CGEN(x + blk[pf[1] * 5 + 1]), CGEN(x + blk[pf[2] * 5 + 1]), x[blk[pf[3] * 5 + 1]],
-                                 x[blk[H.td_blk * 5 + 1]], pts, aux, misc[3], misc[6], misc[7], r, Jl, 20);
-                    (void)loss_correct2(r, Jl, 20, 20, misc[4]);
-                    for (int row = 0; row < 2; row++) {
-                        for (int c2 = 0; c2 < 19; c2++) rec[row * 21 + c2] = Jl[row * 20 + c2];
-                        rec[row * 21 + 19] = r[row]; rec[row * 21 + 20] = Jl[row * 20 + 19];
-                    }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 6; i++) pts[i] = dp[H.d_proj + (f0 + tid) * 6 + i];
-                    proj_eval(CGEN(x + blk[pf[0] * 5 + 1]), CGEN(x + blk[pf[1] * 5 + 1]), CGEN(x + blk[pf[2] * 5 + 1]), x[blk[pf[3] * 5 + 1]],
-                              pts, misc[3], r, GEN(rec), PROJ_STRIDE);
-                    (void)loss_correct2(r, GEN(rec), 19, PROJ_STRIDE, misc[4]);
-                    rec[19] = r[0]; rec[PROJ_STRIDE + 19] = r[1];
-                }
-            }
-            __syncthreads();
-            if (H.proj_disjoint && !H.block_mode) {
-                // thread t owns entry (ca >= cb, or cb = residual) of the factor record for every factor of the chunk, in factor order: the
-                // same sums as the factor-by-factor loop below, bit for bit, without its barrier per factor.  The running destination stays
-                // in a register while consecutive factors hit the same element (the anchor pose, the extrinsics, one landmark's factors).
-                const int ntri = njc * (njc + 1) / 2;
-                for (int t = tid; t < ntri + njc; t += MARG_NT) {
-                    int ca, cb;
-                    if (t < ntri) { ca = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5); while ((ca + 1) * (ca + 2) / 2 <= t) ca++; while (ca * (ca + 1) / 2 > t) ca--; cb = t - ca * (ca + 1) / 2; }
-                    else { ca = t - ntri; cb = njc; }
-                    const int ga = ca < 18 ? ca / 6 : (ca == 18 ? 3 : 4), oa = ca < 18 ? ca % 6 : 0;
-                    const int gb = cb < 18 ? cb / 6 : (cb == 18 ? 3 : 4), ob = cb < 18 ? cb % 6 : 0;
-                    const int ra = ca == 19 ? 20 : ca, rb = cb == njc ? 19 : (cb == 19 ? 20 : cb);
-                    const int ltd = with_td ? blk[H.td_blk * 5 + 2] : -1;
-                    int prev = -1;
-                    double accv = 0.0;
-                    for (int f = 0; f < fn; f++) {
-                        cst_i *pf = ip + H.o_proj + (f0 + f) * 4;
-                        const int l0 = blk[pf[0] * 5 + 2], l1 = blk[pf[1] * 5 + 2], l2 = blk[pf[2] * 5 + 2], l3 = blk[pf[3] * 5 + 2];
-                        const int la = ga == 0 ? l0 : (ga == 1 ? l1 : (ga == 2 ? l2 : (ga == 3 ? l3 : ltd)));
-                        const int lb = gb == 0 ? l0 : (gb == 1 ? l1 : (gb == 2 ? l2 : (gb == 3 ? l3 : ltd)));
-                        const lds_d *rec = stage + f * prr;
-                        const double sv = rec[ra] * rec[rb] + rec[prs + ra] * rec[prs + rb];
-                        const int d = (la < 0 || (cb != njc && lb < 0)) ? -1 : (cb == njc ? MARG_MAX_POS * MARG_MAX_POS + la + oa : pidx(la + oa, lb + ob));
-                        if (d < 0) continue;
-                        if (d != prev) {
-                            if (prev >= 0) { if (prev >= MARG_MAX_POS * MARG_MAX_POS) bv[prev - MARG_MAX_POS * MARG_MAX_POS] = accv; else Apk[prev] = accv; }
-                            accv = d >= MARG_MAX_POS * MARG_MAX_POS ? bv[d - MARG_MAX_POS * MARG_MAX_POS] : Apk[d];
-                            prev = d;
-                        }
-                        accv += sv;
-                    }
-                    if (prev >= 0) { if (prev >= MARG_MAX_POS * MARG_MAX_POS) bv[prev - MARG_MAX_POS * MARG_MAX_POS] = accv; else Apk[prev] = accv; }
-                }
-                __syncthreads();
-                continue;
-            }
-            for (int f = 0; f < fn; f++) {
-                cst_i *pf = ip + H.o_proj + (f0 + f) * 4;
-                const lds_d *rec = stage + f * prr;
-                for (int e = tid; e < njc * (njc + 1); e += MARG_NT) {
-                    const int ca = e / (njc + 1), cb = e - ca * (njc + 1);   // cb == njc: residual column
-                    if (cb < njc && cb > ca) continue;
-                    // block and offset of a logical Jacobian column: 0..17 the three poses, 18 the inverse depth, 19 Td
-                    const int ba = ca < 18 ? pf[ca / 6] : (ca == 18 ? pf[3] : H.td_blk), oa = ca < 18 ? ca % 6 : 0;
-                    const int ra = ca == 19 ? 20 : ca, rb = cb == njc ? 19 : (cb == 19 ? 20 : cb);
-                    const int la = blk[ba * 5 + 2];
-                    const double s = rec[ra] * rec[rb] + rec[prs + ra] * rec[prs + rb];
-                    if (H.block_mode && ca == 18) {
-                        // the landmark's row: coupling to the camera columns, its diagonal and its gradient
-                        if (cb == 18) lmacc[0] += s;
-                        else if (cb == njc) lmacc[1] += s;
-                        else { const int bb = cb < 18 ? pf[cb / 6] : H.td_blk, lb = blk[bb * 5 + 2]; if (lb >= 0) cvec[lb + (cb < 18 ? cb % 6 : 0)] += s; }
-                        continue;
-                    }
-                    if (H.block_mode && ca == 19 && cb == 18) {      // Td row meets the landmark column: same coupling, transposed
-                        if (la >= 0) cvec[la] += s;
-                        continue;
-                    }
-                    if (la < 0) continue;
-                    const int ia = la + oa;
-                    if (cb == njc) { bv[ia] += s; continue; }
-                    const int bb = cb < 18 ? pf[cb / 6] : (cb == 18 ? pf[3] : H.td_blk);
-                    const int lb = blk[bb * 5 + 2];
-                    if (lb < 0) continue;
-                    Apk[pidx(ia, lb + (cb < 18 ? cb % 6 : 0))] += s;
-                }
-                __syncthreads();
-                if (H.block_mode && ip[H.o_plast + f0 + f]) {
-                    // Schur complement of the 1 x 1 landmark block (pseudo-inverse: a landmark without information contributes nothing)
-                    const double d = lmacc[0], g = lmacc[1], invd = d > 1e-8 ? 1.0 / d : 0.0;
-                    for (int e = tid; e < pos * pos; e += MARG_NT) {
-                        const int i = e / pos, j = e - i * pos;
-                        if (j > i) continue;
-                        const double ci = cvec[i], cj = cvec[j];
-                        if (ci != 0.0 && cj != 0.0) Apk[pidx(i, j)] -= ci * cj * invd;
-                    }
-                    if (tid < pos) bv[tid] -= cvec[tid] * g * invd;
-                    __syncthreads();
-                    for (int i = tid; i < pos; i += MARG_NT) cvec[i] = 0.0;
-                    if (tid == 0) { lmacc[0] = 0.0; lmacc[1] = 0.0; }
-                    __syncthreads();
-                }
-            }
-        }
+        marg_projection<MARG_NT>(W);
         MARG_MARK(3);
-        // ---- Amm^+ (marginalization_factor.cpp:267-272: eigen-decomposition, eigenvalues <= eps dropped).  When every eigenvalue is
-        // provably above eps the pseudo-inverse IS the inverse, and Arm Amm^-1 Amr = Z'Z with Z = L^-1 Amr from the Cholesky factor
-        // Amm = L L' -- 23 dependent column steps on one wavefront instead of ~100 Jacobi rounds of three barriers each.  Proof of rank
-        // per window: lambda_min >= 1 / trace(Amm^-1) = 1 / |L^-1|_F^2 > eps.  Otherwise (a landmark without parallax, a prior
-        // that does not constrain the dropped pose) the eigen path below runs as before.
-        const int ldm = me + 1;
-        lds_d *Mm = R2, *Vm = R2 + me * ldm;
-        lds_d *Zl = Vm;                                     // Cholesky path: Z (m x (n + 1), last column L^-1 bmm) in LDS
-        const int zs = n + 1;
-        for (int i = tid; i < m * m; i += MARG_NT) { const int r = i / m, c = i - r * m; Mm[r * ldm + c] = Apk[pidx(r, c)]; }
-        __syncthreads();
-        bool chol = Aarg.eig_mm == 0;
-        constexpr int MREG = 24;      // dropped sets of at most 24 dims (a pose, a speed-bias and up to nine landmarks; block mode: 15): in registers
-        if (chol && m <= MREG) {
-            // right-looking in registers, lane = row: entry (i, c) takes its subtractions L_ip L_cp in the order p = 0, 1, ... of the left-looking
-            // loop below (same products, same fused operations: the same bits), pivot column broadcast with v_readlane -- no LDS round trip
-            // on the 23 dependent column steps.  One basic block (steps k >= m work on zero rows behind selects, only their stores are
-            // guarded), so that the trailing update of a step is scheduled into the 1 / sqrt chain of the next one.
-            chol_small_regs<MREG>(Mm, lmacc + 2, m, ldm, tid);
-            MARG_MARK(9);
-            __syncthreads();
-            MARG_MARK(10);
-            chol = lmacc[2] != 0.0;
-        } else
-        if (chol) {
-            if (tid < 64) {      // left-looking Cholesky, lane = row; the diagonal keeps 1 / L_kk
-                const int i = min(tid, m - 1);
-                bool ok = true;
-                for (int k = 0; k < m; k++) {
-                    double sv = Mm[i * ldm + k], sd = Mm[k * ldm + k];
-                    int p2 = 0;
-                    for (; p2 + 3 < k; p2 += 4) {      // four steps' loads in flight, the updates in the original order
-                        double lk[4], li[4];
-#pragma unroll
-                        for (int u = 0; u < 4; u++) { lk[u] = Mm[k * ldm + p2 + u]; li[u] = Mm[i * ldm + p2 + u]; }
-#pragma unroll
-                        for (int u = 0; u < 4; u++) { sv -= li[u] * lk[u]; sd -= lk[u] * lk[u]; }
-                    }
-                    for (; p2 < k; p2++) { const double lk = Mm[k * ldm + p2]; sv -= Mm[i * ldm + p2] * lk; sd -= lk * lk; }
-                    ok = ok && (sd > 0.0) && (sd < 1e300);
-                    const double rs = 1.0 / sqrt(ok ? sd : 1.0);
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    if (tid < m && tid > k) Mm[tid * ldm + k] = sv * rs;
-                    if (tid == k) Mm[k * ldm + k] = rs;
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                }
-                if (tid == 0) lmacc[2] = ok ? 1.0 : 0.0;
-            }
-            __syncthreads();
-            chol = lmacc[2] != 0.0;
-        }
-        if (chol && m <= MREG) {
-            // forward substitutions, one thread per right-hand side (the n columns of Amr, bmm, the m unit vectors for |L^-1|_F^2), the
-            // solution in registers: z_k' -= L_k'k z_k as soon as z_k is final -- per entry the subtractions of the loop below in its order --
-            // with L read as broadcasts; nothing waits for its own stores.  Branch-free but for the stores: a guard per entry makes every load
-            // of L wait out its own LDS round trip (45 K cycles instead of 8 K); rows k >= m compute on clamped loads and are never stored.
-            fwd_small_regs<MREG>(Mm, Apk, bv, Zl, rot, m, n, ldm, zs, tid);
-            MARG_MARK(11);
-            __syncthreads();
-            double tr = 0, trs = 0;
-            for (int j = 0; j < m; j++) { tr += rot[j]; trs += rot[j] * Apk[pidx(j, j)]; }
-            chol = tr < 1e8;                                    // lambda_min >= 1 / tr > 1e-8 (false for NaN)
-            if (tid == 0) { out[MARG_DIAG_AMM_TRACE] = tr; out[MARG_DIAG_AMM_TRACE + 1] = trs; }
-        } else
-        if (chol) {
-            // forward substitutions L z = rhs, one thread per right-hand side: the n columns of Amr, bmm, and the m unit vectors whose
-            // solutions give |L^-1|_F^2 (kept in the unused upper triangle of Mm)
-            if (tid < n + 1) {
-                const int j = tid;
-                for (int k = 0; k < m; k++) {
-                    double sv = j < n ? Apk[pidx(m + j, k)] : bv[k];
-                    int p2 = 0;
-                    for (; p2 + 3 < k; p2 += 4) {
-                        double lk[4], zz[4];
-#pragma unroll
-                        for (int u = 0; u < 4; u++) { lk[u] = Mm[k * ldm + p2 + u]; zz[u] = Zl[(p2 + u) * zs + j]; }
-#pragma unroll
-                        for (int u = 0; u < 4; u++) sv -= lk[u] * zz[u];
-                    }
-                    for (; p2 < k; p2++) sv -= Mm[k * ldm + p2] * Zl[p2 * zs + j];
-                    Zl[k * zs + j] = sv * Mm[k * ldm + k];
-                }
-            } else if (tid < n + 1 + m) {
-                const int j = tid - n - 1;
-                double y = Mm[j * ldm + j], nn = y * y;       // y_j = 1 / L_jj
-                lds_d *yr = Mm + j * ldm;                       // y_k for k > j at Mm[j][k]
-                for (int k = j + 1; k < m; k++) {
-                    double sv = -Mm[k * ldm + j] * y;
-                    for (int p2 = j + 1; p2 < k; p2++) sv -= Mm[k * ldm + p2] * yr[p2];
-                    sv *= Mm[k * ldm + k];
-                    yr[k] = sv;
-                    nn += sv * sv;
-                }
-                rot[j] = nn;
-            }
-            __syncthreads();
-            double tr = 0, trs = 0;
-            for (int j = 0; j < m; j++) { tr += rot[j]; trs += rot[j] * Apk[pidx(j, j)]; }
-            chol = tr < 1e8;                                    // lambda_min >= 1 / tr > 1e-8 (false for NaN)
-            if (tid == 0) { out[MARG_DIAG_AMM_TRACE] = tr; out[MARG_DIAG_AMM_TRACE + 1] = trs; }
-        }
-        int sweeps1 = 0;
-        const int ldn = ne + 1;
-        lds_d *As = Apk, *V2 = Apk;
-        double keepA[ (MARG_MAX_N * MARG_MAX_N + MARG_NT - 1) / MARG_NT ];
-        bool keep_sym = false;      // keepA holds the folded lower triangle (Cholesky route) instead of all n x n entries
-        double bprime = 0;
-        gbl_d *Z = scr + MARG_SCR_Z, *zb = scr + MARG_SCR_PR;
-        if (chol) {
-            MARG_MARK(4);
-            MARG_MARK(5);
-            // A' = Arr - Z'Z, b' = brr - Z' zb: held in registers until every read of the packed A is done, then written over it
-            // (only the lower triangle, folded into an (n + 1)-wide rectangle: rows R and n - 1 - R share a line; entry (j, i) is the same
-            // difference of the same products as (i, j), bit for bit, and is mirrored when the registers are written back)
-            int q = 0;
-            keep_sym = true;
-            for (int e = tid; e < ((n + 1) >> 1) * (n + 1); e += MARG_NT, q++) {
-                const int R = e / (n + 1), Cc = e - R * (n + 1);
-                const int i = (Cc <= R) ? R : n - 1 - R, j = (Cc <= R) ? Cc : Cc - R - 1;
-                double sv = Apk[pidx(m + i, m + j)];
-                int k = 0;
-                for (; k + 3 < m; k += 4) {      // four steps' loads in flight, the updates in the original order
-                    double za[4], zb4[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) { za[u] = Zl[(k + u) * zs + i]; zb4[u] = Zl[(k + u) * zs + j]; }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) sv -= za[u] * zb4[u];
-                }
-                for (; k < m; k++) sv -= Zl[k * zs + i] * Zl[k * zs + j];
-                keepA[q] = sv;      // (the second half of the middle line of an odd n repeats entries of its first half: harmless duplicates)
-            }
-            if (tid < n) {
-                bprime = bv[m + tid];
-                for (int k = 0; k < m; k++) bprime -= Zl[k * zs + tid] * Zl[k * zs + n];
-            }
-        } else {
-            // ---- Amm = V diag(lam) V'
-            if (Aarg.eig_mm == 0) {      // the Cholesky attempt overwrote Mm
-                __syncthreads();
-                for (int i = tid; i < m * m; i += MARG_NT) { const int r = i / m, c2 = i - r * m; Mm[r * ldm + c2] = Apk[pidx(r, c2)]; }
-                __syncthreads();
-            }
-            sweeps1 = jacobi_eig<MARG_NT, lds_d>(Mm, Vm, m, ldm, rot, cnt, tid, 0.0);
-            MARG_MARK(4);
-            if (tid < m) { const double l = Mm[tid * ldm + tid]; lam[tid] = l > 1e-8 ? sqrt(1.0 / l) : 0.0; }
-            __syncthreads();
-            // Z = diag(sqrt(lam^+)) V' Amr  (m x n) and zb = diag(sqrt(lam^+)) V' bmm, kept in global scratch
-            for (int e = tid; e < m * n; e += MARG_NT) {
-                const int k = e / n, j = e - k * n;
-                double sv = 0;
-                for (int p2 = 0; p2 < m; p2++) sv += Vm[p2 * ldm + k] * Apk[pidx(m + j, p2)];
-                Z[k * n + j] = lam[k] * sv;
-            }
-            if (tid < m) {
-                double sv = 0;
-                for (int p2 = 0; p2 < m; p2++) sv += Vm[p2 * ldm + tid] * bv[p2];
-                zb[tid] = lam[tid] * sv;
-            }
-            __syncthreads();
-            MARG_MARK(5);
-            int q = 0;
-            for (int e = tid; e < n * n; e += MARG_NT, q++) {
-                const int i = e / n, j = e - i * n;
-                double sv = Apk[pidx(m + i, m + j)];
-                for (int k = 0; k < m; k++) sv -= Z[k * n + i] * Z[k * n + j];
-                keepA[q] = sv;
-            }
-            if (tid < n) {
-                bprime = bv[m + tid];
-                for (int k = 0; k < m; k++) bprime -= Z[k * n + tid] * zb[k];
-            }
-        }
-        __syncthreads();   // every read of Vm / Apk is done: P and R2 can be overwritten
-        {
-            int q = 0;
-            if (keep_sym) {
-                for (int e = tid; e < ((n + 1) >> 1) * (n + 1); e += MARG_NT, q++) {
-                    const int R = e / (n + 1), Cc = e - R * (n + 1);
-                    const int i = (Cc <= R) ? R : n - 1 - R, j = (Cc <= R) ? Cc : Cc - R - 1;
-                    As[i * ldn + j] = keepA[q]; As[j * ldn + i] = keepA[q];
-                    out[MARG_OUT_AS + i * n + j] = keepA[q]; out[MARG_OUT_AS + j * n + i] = keepA[q];
-                }
-            } else
-            for (int e = tid; e < n * n; e += MARG_NT, q++) {
-                const int i = e / n, j = e - i * n;
-                As[i * ldn + j] = keepA[q];
-                out[MARG_OUT_AS + i * n + j] = keepA[q];
-            }
-        }
-        if (tid < n) { bv[tid] = bprime; out[MARG_OUT_BS + tid] = bprime; }
-        __syncthreads();
+        const bool chol = marg_amm_route<MARG_NT>(W, Aarg.eig_mm, t_last);      // (marks 9 .. 11 inside)
+        double keepA[MARG_KEEP<MARG_NT>], bprime;      // A' and b' in registers while the packed A is still being read
+        const int sweeps1 = marg_schur<MARG_NT>(W, chol, Aarg.eig_mm, keepA, bprime, t_last);      // (marks 4 and 5 inside)
+        marg_write_back<MARG_NT>(W, chol, keepA, bprime);
         MARG_MARK(6);
-        // A' = V2 diag(lam) V2': tridiagonal path first, Jacobi sweep as the safety net (its eigenvector matrix in HBM scratch, copied
-        // over the diagonalised A' at the end: the LDS holds one n x n matrix)
-        int sweeps2 = 0;
-        {
-            const bool ok = sym_eig_tridiag<MARG_NT>(As, R2, sm, rot, n, ldn, tid, out + MARG_DIAG_EIG_CHECK, Aarg.eig_flags, scr + MARG_SCR_V);    // rot: 160 doubles >= n eigenvalues
-            if (ok) {
-                if (tid < n) lam[tid] = rot[tid];
-            } else {
-                gbl_d *Vg = scr + MARG_SCR_V;
-                for (int e = tid; e < n * n; e += MARG_NT) { const int i2 = e / n, j2 = e - i2 * n; As[i2 * ldn + j2] = out[MARG_OUT_AS + i2 * n + j2]; }
-                __syncthreads();
-                sweeps2 = 100 + jacobi_eig<MARG_NT, gbl_d>(As, Vg, n, ldn, rot, cnt, tid, 2.3e-16, out + MARG_DIAG_PHASE + 9);
-                if (tid < n) lam[tid] = As[tid * ldn + tid];
-                __syncthreads();
-                for (int e = tid; e < n * n; e += MARG_NT) { const int i2 = e / n, j2 = e - i2 * n; V2[i2 * ldn + j2] = Vg[i2 * ldn + j2]; }
-            }
-        }
+        const int sweeps2 = marg_eig_kept<MARG_NT>(W, Aarg.eig_flags);
         MARG_MARK(7);
-        __syncthreads();
-        bool bad = false;      // a NaN in J0 | r0 (the host path scans the downloaded J0 for it)
-        if (tid < n) {
-            const double l = lam[tid];
-            int rank = 0;
-            for (int j = 0; j < n; j++) rank += (lam[j] < l || (lam[j] == l && j < tid)) ? 1 : 0;
-            const double S = l > 1e-8 ? l : 0.0, Sinv = l > 1e-8 ? 1.0 / l : 0.0;
-            const double ss = sqrt(S), si = sqrt(Sinv);
-            double rb = 0;
-            for (int j = 0; j < n; j++) {
-                const double v = V2[j * ldn + tid];
-                out[MARG_OUT_J0 + rank + n * j] = ss * v;
-                rb += v * bv[j];
-            }
-            out[MARG_OUT_R0 + rank] = si * rb;
-            // (a NaN or Inf anywhere in the eigenvector reaches rb -- NaN * 0 is NaN -- and from there si * rb, thresholded row or not)
-            if (!(si * rb == si * rb) || !(l == l)) bad = true;
-        }
-        // what a device-resident consumer of this prior needs on the host (tcv_batch_get_priors_device): the number of leading rows of
-        // J0 | r0 that are exact zeros -- the thresholded eigenvalues rank first and their rows are 0 * v --, capped like
-        // tcv_packed.h prior_zero_rows() (one row is kept); -1: the result holds a NaN.
-        // Nothing of the window's LDS is read behind its last barrier: the other wavefronts are in the next window of the loop by then,
-        // whose carve-up of the LDS (r1 / r2 / nx differ between MARGIN_OLD and SECOND_NEW windows) puts x[] / bv[] / cvec[] over this
-        // window's lam[] (round-4 advisor finding).  The count is taken here -- lam[] is final since the barrier above --, stored by lane 0
-        // BEFORE the barrier, and a thread that saw a NaN overwrites it with -1 BEHIND the barrier from its register (no LDS flag, and NOT
-        // __syncthreads_or, whose work-group reduction brings a static LDS variable -- 80 KiB + 4 bytes per workgroup is one workgroup per
-        // CU instead of two: 0.85 -> 1.40 ms per 1024 windows, measured).
-        if (tid < 64) {      // (the first wavefront counts, two eigenvalues per lane: n <= 80)
-            const bool z0 = tid < n && !(lam[tid] > 1e-8), z1 = tid + 64 < n && !(lam[tid + 64] > 1e-8);
-            int k0 = __popcll(__ballot(z0)) + __popcll(__ballot(z1));
-            if (k0 >= n) k0 = n > 0 ? n - 1 : 0;
-            if (tid == 0) ((gbl_i *)Aarg.out_status)[Aarg.nwin + win] = k0;
-        }
-        for (int i = tid; i < H.nx; i += MARG_NT) out[MARG_OUT_X + i] = x[i];
-        MARG_MARK(8);
-        if (tid == 0) ((gbl_i *)Aarg.out_status)[win] = (sweeps1 >= 24 || sweeps2 == 124) ? 1 : (sweeps2 >= 100 ? 2 : 0);   // 1: a Jacobi sweep hit its cap, 2: A' went through the Jacobi safety net
-        if (tid == 0) { out[MARG_DIAG_SWEEPS_MM] = sweeps1; out[MARG_DIAG_SWEEPS_RR] = sweeps2; }
-        __syncthreads();
-        if (bad) ((gbl_i *)Aarg.out_status)[Aarg.nwin + win] = -1;      // (ordered behind lane 0's store by the barrier)
+        marg_output<MARG_NT>(W, Aarg, win, sweeps1, sweeps2, t_last);      // (mark 8 inside)
     }
 }
 

@@ -183,7 +183,7 @@ struct SolveArgs {
     double *coop_x;               // per group COOP_X_DOUBLES: the state the master hands to its helpers (+ mu)
     double *coop_exp;             // per group coop_exp_chunks x coop_exp_stride doubles
     long long coop_timeout;       // ticks of the constant-rate device clock a workgroup waits for its partners before it gives up (status -9)
-    int chain_td;                     // chain kernel: 1 = the ProjectionTdFactor instance (a window estimates Td or has wider camera-space vectors, tcv_batch.cpp)
+    int chain_td;                     // chain kernel: 1 = the ProjectionTdFactor instance (a window estimates Td or has wider camera-space vectors, tcv_batch_create.cpp set_launch_shape)
     int coop_rot, gauge_fix;          // cooperative mode: group g runs on the workgroups b with b % 8 == (g + coop_rot) % 8, i.e. on XCD (g + coop_rot) % 8;
                                       // gauge_fix: double2vector() in the kernel's epilogue (tcv_batch_set_fused_gauge_fix)
 };

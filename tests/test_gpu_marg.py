@@ -172,6 +172,37 @@ def test_margin_second_new_prior_only(gpu):
     assert got == [tuple(b) for b in po["blocks"]]
 
 
+def test_margin_second_new_with_a_prior_that_does_not_fit_the_lds(gpu):
+    """The prior phase stages J0 in the region of the packed A when its stored rows fit there and forms J0'J0 on the matrix cores; otherwise
+    it reads J0 from HBM, entry by entry.  MARGIN_SECOND_NEW has the small region (pos = 75), and a prior without zero rows (the golden
+    prior's 34 zero rows given a unit entry each: 75 x 75 > 70 x 71 stored entries) does not fit: the same gates as
+    test_margin_second_new_prior_only, at the window's own state."""
+    import np_oracle as NO
+    pre, main, z = golden_windows()
+    J0 = np.array(main["prior"]["J0"], copy=True)
+    zero = np.flatnonzero(~J0.any(axis=1))
+    J0[zero, zero] = 1.0
+    main = dict(main, prior=dict(main["prior"], J0=J0))
+    prob = NO.Problem(main)
+    po, dbg = NO.marginalize_second_new(prob, prob.x0())
+    mw = gpu.margin_second_new_window(main)
+    Wm = gpu.Window(mw)
+    dr = gpu.margin_second_new_drops(Wm)
+    H = gpu.marg_plan(Wm, dr)[0]
+    ne = H.n + (H.n & 1)
+    assert H.prior_k0 == 0 and H.prior_n * H.prior_n > max(H.pos * (H.pos + 1) // 2, ne * (ne + 1))      # (csrc/tcv_marg.hip marg_prior: in_lds is false)
+    arr = (gpu._dp * len(dr))(*dr)
+    h = C.c_void_p()
+    gpu.check(gpu.lib().tcv_marginalize(Wm.h, arr, len(dr), C.byref(h)))
+    P = gpu.Prior(h); d = P.export(); As, bs = P.schur()
+    assert (d["m"], d["n"]) == (6, po["n"]) and d["sizes"] == po["sizes"] and d["idx"] == po["idx"]
+    print("MARGIN_SECOND_NEW, prior from HBM: A' %.2e b' %.2e J0'J0 %.2e J0'r0 %.2e" % (fro(As, dbg["A_schur"]), fro(bs, dbg["b_schur"]),
+          fro(d["J0"].T @ d["J0"], po["J0"].T @ po["J0"]), fro(d["J0"].T @ d["r0"], po["J0"].T @ po["r0"])))
+    assert fro(As, dbg["A_schur"]) < 2e-6 and fro(bs, dbg["b_schur"]) < 1e-8
+    assert fro(d["J0"].T @ d["J0"], po["J0"].T @ po["J0"]) < 2e-6
+    assert fro(d["J0"].T @ d["r0"], po["J0"].T @ po["r0"]) < 1e-10
+
+
 def test_large_drop_set_uses_landmark_pivots(gpu):
     """a 150-feature front end anchors far more landmarks in the oldest frame than the LDS-resident eigen-solver takes
     (m <= 64): the marginalised inverse depths are then eliminated by scalar pivots and only the frame part (15) goes through
@@ -194,6 +225,46 @@ def test_large_drop_set_uses_landmark_pivots(gpu):
     assert fro(As, dbg["A_schur"]) < 1e-5 and fro(bs, dbg["b_schur"]) < 1e-5
     assert fro(d["J0"].T @ d["J0"], dbg["A_schur"]) < 1e-5
     assert rel(np.concatenate(d["x0"]), np.concatenate([np.atleast_1d(v) for v in po["x0"]])) == 0.0
+
+
+BLOCK_PATHS = {      # name -> (frames kept, switch, what the packed plan must say: chunked?, C behind the staging records?)
+    "scalar_pivots": (11, "TCV_MARG_BLOCK_SERIAL", (False, False)),
+    "c_behind_the_records": (6, None, (True, True)),
+}
+
+
+@pytest.mark.parametrize("name", list(BLOCK_PATHS))
+def test_block_mode_paths_of_the_projection_phase_vs_oracle(gpu, monkeypatch, name):
+    """Block mode (more than 64 dropped dims: 344 landmarks anchor 50 in frame 0) on the paths of the projection phase that
+    test_large_drop_set_uses_landmark_pivots does not take: factor by factor with a scalar pivot per landmark (TCV_MARG_BLOCK_SERIAL), and the
+    chunked path with the couplings C behind the staging records (a window of 6 frames: n = 45 leaves no room in the region of the packed
+    A).  The plan says which path it is; A', b' against the C oracle at the same state, with the gates of
+    test_large_drop_set_uses_landmark_pivots.  Measured: scalar pivots 2.5e-7 / 1.2e-12, C behind the records 9.1e-8 / 2.9e-12.
+    (Block mode with ProjectionTdFactors takes the scalar pivots too, but has no reference good to these gates: the C oracle has no Td,
+    and the NumPy oracle's one-piece pseudo-inverse of this 65-dim A_mm is 7.9e-4 / 1.4e-3 from the C oracle's on the window without Td.)"""
+    from util import sub_window
+    frames, switch, (chunked, c_in_r2) = BLOCK_PATHS[name]
+    w = synth.window_at(synth.make_windows(902, 1, n_landmarks=344, frame_shift=-1), 0)
+    if frames < 11:
+        w = sub_window(w, frames)
+    po, dbg = orc.Window(w).marginalize_old()
+    assert po["m"] > 64
+    if switch:
+        monkeypatch.setenv(switch, "1")
+    mw = gpu.margin_old_window(w)
+    Wm = gpu.Window(mw)
+    dr = gpu.margin_old_drops(Wm, mw)
+    H = gpu.marg_plan(Wm, dr)[0]
+    r1 = max(H.pos * (H.pos + 1) // 2, (H.n + (H.n & 1)) * (H.n + (H.n & 1) + 1))      # doubles of the region of the packed A (csrc/tcv_marg.hip marg_carve)
+    assert H.block_mode == 1 and (H.cb_off >= 0, H.cb_off >= r1) == (chunked, c_in_r2)
+    arr = (gpu._dp * len(dr))(*dr)
+    h = C.c_void_p()
+    gpu.check(gpu.lib().tcv_marginalize(Wm.h, arr, len(dr), C.byref(h)))
+    P = gpu.Prior(h); d = P.export(); As, bs = P.schur()
+    assert (d["m"], d["n"]) == (po["m"], po["n"]) and d["sizes"] == po["sizes"] and d["idx"] == po["idx"]
+    print("block mode, %s (m = %d, n = %d): A' %.2e b' %.2e" % (name, po["m"], po["n"], fro(As, dbg["A_schur"]), fro(bs, dbg["b_schur"])))
+    assert fro(As, dbg["A_schur"]) < 1e-5 and fro(bs, dbg["b_schur"]) < 1e-5
+    assert fro(d["J0"].T @ d["J0"], dbg["A_schur"]) < 1e-5
 
 
 @pytest.mark.parametrize("nt", ["256", "512"])
