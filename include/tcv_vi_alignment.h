@@ -18,7 +18,8 @@
  *
  * Deviations from the reference, all documented in DESIGN.md section 8: the linear systems are solved by an unpivoted Cholesky in natural
  * order behind a rank gate (the reference: Eigen's pivoted LDLT, no gate); Quaterniond::FromTwoVectors of g2R takes the fixed axis
- * (1, 0, 0) in its antiparallel branch (Eigen: an axis from an SVD).
+ * (1, 0, 0) in its antiparallel branch (Eigen: an axis from an SVD); TangentBasis takes its special branch for gravity exactly along -z
+ * of the SfM frame as well as +z (the reference: +z only; at -z its basis is the zero vector).
  *
  * Limits (TCV_ERR_UNSUPPORTED before anything is launched): TCV_VI_ALIGN_MAX_FRAMES frames per sequence, TCV_VI_ALIGN_MAX_BATCH sequences
  * per call.  Valid C99 and C++14. */

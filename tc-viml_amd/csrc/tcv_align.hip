@@ -287,10 +287,11 @@ __global__ void __launch_bounds__(AL_THREADS) align_solve_kernel(int n_seq, cons
     if (status == 0) {      // RefineGravity
         V3 g0 = al_normalized(g) * G;                                            // :57
         for (int round = 0; round < 4 && status == 0; round++) {
-            // TangentBasis (:40-53)
+            // TangentBasis (:40-53).  The reference tests a == tmp only; at a == -tmp its b is the zero vector, which its LDLT survives (zero
+            // pivots give dg == 0) and a Cholesky behind a rank gate does not: both poles take the special branch here.
             const V3 a = al_normalized(g0);
             V3 tmp(0.0, 0.0, 1.0);
-            if (a.x == tmp.x && a.y == tmp.y && a.z == tmp.z) tmp = V3(1.0, 0.0, 0.0);
+            if (a.x == tmp.x && a.y == tmp.y && (a.z == tmp.z || a.z == -tmp.z)) tmp = V3(1.0, 0.0, 0.0);
             const V3 lx = al_normalized(tmp - a * dot(a, tmp)), ly = cross(a, lx);
             __syncthreads();
             if (tid == 0) {

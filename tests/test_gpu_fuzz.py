@@ -69,5 +69,11 @@ def test_pose_graphs_on_random_structures(gpu):
     assert run("fuzz_pose_graph", 200, 0) == 0
 
 
+def test_visual_inertial_alignment_on_random_sequences(gpu):
+    """60 seeded sequences, each alone and sixteen at a time in ragged batches, against the restatement on the device's own pre-integrations
+    (tests/test_vi_alignment_cpu.py holds the same seed range decided by the restatement alone)"""
+    assert run("fuzz_vi_alignment", 60, 0) == 0
+
+
 def test_native_estimator_on_stress_streams(gpu):
     assert run("fuzz_estimator", 6, 0, 40) == 0

@@ -279,3 +279,247 @@ def test_valid_input_without_a_device_is_no_device(va):
 
 def test_scope_comment_points_at_the_header():
     assert "tcv_vi_alignment.h" in open(os.path.join(ROOT, "include", "tcv_estimator.h")).read()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Inputs off the well-posed path (tests/vi_alignment_cases.py): the restatement alone must be decisive on each of them, in float64 and in
+# long double, before tests/test_gpu_vi_alignment_paths.py runs them on the device.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+from vi_alignment_cases import RANK_SITES, SINGULAR_FRAMES, STATUS2, TILTED, VERTICAL      # noqa: E402  (shared with the GPU tests)
+
+assert VC.DEFAULT_GATE == DEFAULT_GATE
+
+
+def _both(case, gate=DEFAULT_GATE):
+    return VC.run_oracle_imu(case, dtype=np.float64, gate=gate)[0], VC.run_oracle_imu(case, dtype=LD, gate=gate)[0]
+
+
+def _all_pivots(r):
+    return np.concatenate([np.asarray(r["bias_pivots"], dtype=np.float64)] + [np.asarray(p, dtype=np.float64) for _, p in r["stages"]])
+
+
+@pytest.mark.parametrize("F,S,sign", VERTICAL)
+def test_vertical_gravity_takes_the_exact_branches(F, S, sign):
+    """gravity exactly along +-z of the SfM frame: TangentBasis's special branch in all four rounds (at -z too -- there the reference's own basis
+    is the zero vector), g2R at c == +-1 exactly, the x / y gravity exactly zero"""
+    c = VC.vertical_case(F, S, sign)
+    for r in _both(c):
+        assert r["status"] == VO.OK, (c["name"], r["status"])
+        assert r["flags"].get("tangent_special") == 4 and r["flags"]["g2R_c"] == sign
+        assert bool(r["flags"].get("g2R_antiparallel")) == (sign < 0)
+        assert float(_all_pivots(r).min()) >= MARGIN * DEFAULT_GATE
+        assert abs(float(r["scale"]) / c["truth"]["scale"] - 1.0) < 1e-3      # (the mid-point integrator's error on a 3 Hz sine at 4 frames)
+    r64 = _both(c)[0]
+    print("%-24s smallest relative pivot %.3g, scale %.9f" % (c["name"], float(_all_pivots(r64).min()), float(r64["scale"])))
+    assert r64["gravity_c0"][0] == 0 and r64["gravity_c0"][1] == 0 and r64["gravity_c0"][2] == sign * 9.81007
+    assert not r64["delta_bg"].any()
+    if sign < 0:      # the rotation by pi about x (the yaw correction is exactly zero: Rs[0] = diag(1, -1, -1))
+        assert np.abs(r64["rot_diff"] - np.diag([1.0, -1.0, -1.0])).max() < 1e-15 and np.abs(r64["gravity"] - [0, 0, 9.81007]).max() < 1e-14
+
+
+@pytest.mark.parametrize("F,S,delta", TILTED)
+def test_tilted_gravity_is_on_the_intended_side_of_the_antiparallel_threshold(F, S, delta):
+    c = VC.tilted_case(F, S, delta)
+    for r in _both(c):
+        assert r["status"] == VO.OK and not r["flags"].get("tangent_special")
+        cc = r["flags"]["g2R_c"]
+        print("%-22s %s 1 + c = %.3e" % (c["name"], r["scale"].dtype, float(1 + cc)))
+        assert bool(r["flags"].get("g2R_antiparallel")) == (delta < 1e-6)
+        # and clear of the threshold 1e-12 by 100 x: 1 + c = delta^2 / 2 = 5e-15 | 5e-5
+        assert float(1 + cc) < 1e-14 if delta < 1e-6 else float(1 + cc) > 1e-10
+        assert _angle(r["gravity_c0"], c["truth"]["gravity_c0"]) < 1e-5
+
+
+def test_refined_scale_seeds_are_decided_by_more_than_rounding():
+    """status 2: LinearAlignment's s >= 0, the refined s < 0, in float64 and long double; |s| at both stages >= 100 x its float64-to-long-double
+    difference"""
+    assert len(STATUS2) >= 3
+    for seed, F in STATUS2:
+        c = VC.noise_T_case(seed, F)
+        r64, rld = _both(c)
+        assert r64["status"] == rld["status"] == VO.REFINED_SCALE, (c["name"], r64["status"], rld["status"])
+        for stage, a, b in (("linear", r64["linear"]["scale"], rld["linear"]["scale"]), ("refined", r64["scale"], rld["scale"])):
+            d = abs(float(LD(a) - b))
+            print("%-20s %-8s s %+.4e   |float64 - long double| %.2e   bar %.2e" % (c["name"], stage, float(a), d, 100 * d))
+            assert abs(float(a)) >= 100 * d, (c["name"], stage)
+        assert r64["linear"]["scale"] >= 0 > r64["scale"] and r64["velocity"].any() and not r64["Ps"].any()
+        assert float(_all_pivots(r64).min()) >= MARGIN * DEFAULT_GATE
+
+
+def _sites(case):
+    """every recorded relative pivot of a case at gate 0, in the order the device meets them, with its site"""
+    r = VC.run_oracle_imu(case, gate=0.0)[0]
+    F = len(case["R"])
+    seq = [("bias", float(p)) for p in r["bias_pivots"]]
+    for stage, piv in r["stages"]:
+        seq += [("band" if j < 3 * F else "linear border" if stage == "linear" else "refine border", float(p)) for j, p in enumerate(piv)]
+    return seq
+
+
+def _gates_by_site(seq):
+    vals = sorted({p for _, p in seq})
+    out = {}
+    for lo, hi in zip(vals[:-1], vals[1:]):
+        g = float(np.sqrt(lo * hi))
+        if lo > 0 and hi / lo >= MARGIN ** 2 and g < 1.0:
+            out.setdefault(next(s for s, p in seq if not p > g), []).append((g, lo, hi))
+    return out
+
+
+def test_rank_gate_sites_reachable_from_well_posed_input():
+    """Status 3 site by site: a min_relative_pivot in the geometric middle of two neighbouring recorded pivots >= 30^2 apart, so that both are 30 x
+    clear of it; the site is where the first failing pivot falls.
+
+    Reachable: LinearAlignment's border (nb == 4), on four and five frames at 50 ms -- RANK_SITES.
+    NOT reachable this way, searched over WELL_POSED, vertical_case (F 4 | 11, both signs), tilted_case (1e-7, 1e-2), ragged_case (three seeds)
+    and the STATUS2 seeds:
+      - the bias kernel's 3 x 3: its relative pivots are 1 to three digits (J is -sum_dt I to first order), nothing lies 30 x under 1.  The
+        exactly singular zero_dt_case (below) reaches that site and the alignment kernel's early exit at the default gate;
+      - a band pivot: the band's pivots lie in 0.04 .. 1 (the velocity block is dt^2 I plus a chain), above every border pivot of the same case,
+        and no two neighbours are 900 x apart;
+      - the border of a RefineGravity round (nb == 3, index map 0 1 3): its smallest pivot is always above LinearAlignment's smallest (two
+        gravity directions are eliminated before the scale, not three), so a gate that fails it fails LinearAlignment first.  Before the
+        TangentBasis fix vertical_case(sign = -1) failed exactly there, with A_kk == 0.  The index map itself runs in every aligned case."""
+    found = {}
+    for F, S in WELL_POSED:
+        for site, gs in _gates_by_site(_sites(VC.make_case(7 + F, F, S))).items():
+            found.setdefault(site, []).extend((F, S) + g for g in gs)
+    others = [VC.vertical_case(F, S, sg) for F, S, sg in VERTICAL] + [VC.tilted_case(*t) for t in TILTED] + [VC.ragged_case(k, F) for k, F in enumerate((6, 23, 65))] + \
+        [VC.noise_T_case(seed, F) for seed, F in STATUS2]
+    for c in others:
+        assert not _gates_by_site(_sites(c)), c["name"]
+    for site, gs in found.items():
+        for F, S, g, lo, hi in gs:
+            print("%-14s F %d period %d: gate %.3g between the pivots %.3g and %.3g" % (site, F, S, g, lo, hi))
+    assert set(found) == {"linear border"}
+    assert sorted((F, S) for F, S, _, _, _ in found["linear border"]) == sorted((F, S) for F, S, _, _ in RANK_SITES)
+    for F, S, gate, site in RANK_SITES:
+        g, lo, hi = next(x[2:] for x in found[site] if x[:2] == (F, S))
+        assert abs(gate / g - 1.0) < 0.01 and lo * MARGIN <= gate <= hi / MARGIN
+        c = VC.make_case(7 + F, F, S)
+        del c["period"]
+        for r in _both(c, gate):
+            assert r["status"] == VO.RANK and r["site"] == site and r["delta_bg"].any() and not r["velocity"].any() and r["scale"] == 0
+
+
+@pytest.mark.parametrize("F", SINGULAR_FRAMES)
+def test_exactly_singular_inputs_fail_the_gate_clearly(F):
+    """a camera at rest (T == 0: the scale column is exactly zero, A_kk == 0 at the failing pivot), constant velocity without rotation (scale and a
+    common velocity confounded: |relative pivot| at the failure <= DEFAULT_GATE / MARGIN), and IMU samples with dt == 0 (the bias Jacobians are
+    exactly zero: the bias solve itself fails, on A_00 == 0, and nothing behind it is computed)"""
+    for r in _both(VC.stationary_case(F)):
+        assert r["status"] == VO.RANK and r["site"] == "linear border" and r["fail_a0"] == 0 and len(r["stages"][0][1]) == 3 * F + 4
+        assert r["delta_bg"].any()
+    for r in _both(VC.constant_velocity_case(F)):
+        print("constant velocity F %d: relative pivot at the failure %.3g (%s)" % (F, float(r["pivots"][-1]), r["scale"].dtype))
+        assert r["status"] == VO.RANK and r["site"] == "linear border" and abs(float(r["pivots"][-1])) <= DEFAULT_GATE / MARGIN
+        assert r["min_pivot"] >= MARGIN * DEFAULT_GATE
+    for r in _both(VC.zero_dt_case(F)):
+        assert r["status"] == VO.RANK and r["site"] == "bias" and r["fail_a0"] == 0 and not r["delta_bg"].any() and not r["bg"].any()
+
+
+def test_scaling_T_alone_never_gives_non_finite():
+    """|T| scaled by 10^k: the float64 restatement is OK for k in -150 .. 152 (s = 2.43 x 10^-k, finite), and RANK outside -- below, the squares
+    of the scale column underflow to an A_kk of zero or a denormal; above, they overflow and the pivot test `d > gate * A_kk` is false for Inf
+    and NaN.  The matrix is shielded by the gate; the right-hand side is not (next test)."""
+    c = VC.make_case(18, 11, 20)
+    seen = {}
+    for k in (-320, -300, -200, -160, -150, -100, 0, 100, 152, 156, 200, 300):
+        cc = dict(c, T=c["T"] * 1e-160 * 10.0 ** (k + 160) if k < -160 else c["T"] * 10.0 ** k)
+        del cc["period"]
+        assert np.isfinite(cc["T"]).all()
+        seen[k] = int(VC.run_oracle_imu(cc, gate=DEFAULT_GATE)[0]["status"])
+    print(seen)
+    assert all(seen[k] == VO.OK for k in (-150, -100, 0, 100, 152)) and all(seen[k] == VO.RANK for k in (-320, -300, -200, -160, 156, 200, 300))
+
+
+@pytest.mark.filterwarnings("ignore::RuntimeWarning")      # (the overflows are the point: synth.preintegrate's covariance, the products of the right-hand side)
+def test_non_finite_after_linear_alignment_from_a_huge_accelerometer():
+    """Status 4, site by site.
+
+    After LinearAlignment's s, g -- REACHED: huge_acc_case(k, 100), accelerometer x 10^k on T x 10^100, every input finite.  The matrices do not
+    depend on the accelerometer, so every pivot is that of the plain case; delta_p and delta_v scale with it, and their products with the scale
+    column overflow.  Float64 restatement at the default gate: LINEAR with finite s = 2.46 x 10^(k - 100) and |g| = 9.81 x 10^k for k <= 208,
+    NON_FINITE for k >= 209 up to 300.  Committed: k = 212 (NON_FINITE) and k = 206 (LINEAR), more than two decades on either side.  Long
+    double does not overflow there and says LINEAR: the verdict is one about float64's range, which the device shares.  (With T unscaled the
+    same happens between k = 305 and 306, but at k = 307 the mid-point sum of two samples overflows inside the pre-integration itself.)
+    After the refinement's s, g, x -- NOT reached: it needs LinearAlignment finite with | |g| - G | <= 1 and s >= 0, then an overflow one solve
+    later in a system that differs by g0's terms only; every input with a right-hand side large enough to overflow has |g| large and ends in
+    LINEAR (all of the above), and a gravity_norm large enough to accept it would need |g| to hit it within 1, below float64's spacing there.
+    After the bias solve -- NOT reached: J is -sum_dt I to first order and |r| <= 2, so delta_bg is about r / dt; swept with every dt = 10^k: finite
+    (2.5 x 10^159 at k = -162) down to k = -162, RANK on A_00 == 0 from k = -165, where dt^2 underflows -- measured below."""
+    seen = {}
+    for k in (150, 200, VC.LINEAR_SIDE_K, 207, 208, 209, 210, 211, VC.NON_FINITE_K, 250, 300):
+        c = VC.huge_acc_case(k)
+        assert all(np.isfinite(m[0]).all() and np.isfinite(m[2]).all() for m in c["imu"]) and np.isfinite(c["T"]).all()
+        r = VC.run_oracle_imu(c, gate=DEFAULT_GATE)[0]
+        seen[k] = int(r["status"])
+        if r["status"] == VO.LINEAR:
+            assert np.isfinite(float(r["scale"])) and np.isfinite(np.asarray(r["gravity_c0"], dtype=np.float64)).all() and r["scale"] > 0
+        else:      # the header's zero pattern: the bias and the pre-integrations stay, nothing behind them
+            assert r["delta_bg"].any() and not any(np.asarray(r[f]).any() for f in ("scale", "gravity_c0", "gravity", "rot_diff", "velocity", "Ps", "Rs", "Vs"))
+        assert r["min_pivot"] >= MARGIN * DEFAULT_GATE and len(r["stages"]) == 1      # every pivot passed; nothing ran behind LinearAlignment
+    print(seen)
+    assert all(seen[k] == VO.LINEAR for k in seen if k <= 208) and all(seen[k] == VO.NON_FINITE for k in seen if k >= 209)
+    assert VC.LINEAR_SIDE_K <= 208 - 2 and VC.NON_FINITE_K >= 209 + 2
+    assert VC.run_oracle_imu(VC.huge_acc_case(VC.NON_FINITE_K), dtype=LD, gate=DEFAULT_GATE)[0]["status"] == VO.LINEAR
+    # the bias site under tiny dt
+    c0 = VC.make_case(18, 11, 20)
+    for k, want in ((-100, VO.OK), (-150, VO.OK), (-162, VO.OK), (-165, VO.RANK), (-200, VO.RANK), (-300, VO.RANK)):
+        imu = [(a0, g0, np.concatenate([np.full((len(s), 1), 10.0 ** k), s[:, 1:]], 1)) for a0, g0, s in c0["imu"]]
+        st, x, _, a0 = VO.gyro_bias_verdict(c0["R"], VC.preint_np(imu, c0["ba0"], c0["bg0"]), np.float64, DEFAULT_GATE)
+        print("dt 1e%d: bias status %d, |delta_bg| %.3g" % (k, st, float(np.abs(x).max())))
+        assert st == want and np.isfinite(np.asarray(x, dtype=np.float64)).all() and (st == VO.OK or a0 == 0)
+
+
+def test_negated_T_is_status_1_by_the_sign_of_s():
+    c = VC.negated_T_case()
+    for r in _both(c):
+        assert r["status"] == VO.LINEAR and abs(float(r["scale"]) + c["truth"]["scale"]) < 1e-3 * c["truth"]["scale"]
+        assert abs(float(np.sqrt(r["gravity_c0"] @ r["gravity_c0"])) - 9.81007) < 0.5 and float(_all_pivots(r).min()) >= MARGIN * DEFAULT_GATE
+
+
+def test_ragged_cases_align_and_skip_frame_zero():
+    for k, F in enumerate((6, 23, 65)):
+        c = VC.ragged_case(k, F)
+        counts = [len(m[2]) for m in c["imu"]]
+        assert min(counts) >= 3 and max(counts) <= 40 and len(set(counts)) > 1 and 0 not in c["key_frame"]
+        assert all(len({float(v) for v in m[2][:, 0]}) > 1 for m in c["imu"]) and {float(v) for m in c["imu"] for v in m[2][:, 0]} == {0.0025, 0.005, 0.01}
+        r64, rld = _both(c)
+        assert r64["status"] == rld["status"] == VO.OK and float(_all_pivots(r64).min()) >= MARGIN * DEFAULT_GATE
+        e = _errors(r64, c["truth"])
+        assert e["scale"] < 1e-4 and e["gravity"] < 1e-5 and e["bg"] < 1e-4, (c["name"], e)
+
+
+def test_dense_solve_agrees_with_the_cholesky():
+    """the second float64 solve (numpy.linalg.solve) gives the Cholesky's answer up to rounding: it sizes noise, it is not another algorithm"""
+    for F, S in ((4, 10), (11, 20), (64, 20)):
+        c = VC.make_case(7 + F, F, S)
+        del c["period"]
+        a = VC.run_oracle_imu(c)[0]; b = VC.run_oracle_imu(c, solver="dense")[0]; ld = VC.run_oracle_imu(c, dtype=LD)[0]
+        assert b["status"] == VO.OK
+        for f in ("delta_bg", "scale", "gravity_c0", "velocity", "Ps"):
+            ea, eb = float(np.abs(a[f] - ld[f]).max()), float(np.abs(b[f] - ld[f]).max())
+            print("F %3d %-10s |cholesky - long double| %.2e   |linalg.solve - long double| %.2e" % (F, f, ea, eb))
+            assert eb <= 1e-6 * max(float(np.abs(ld[f]).max()), 1e-3)      # (condition numbers to 9e12 at four frames: 1e-16 x that, 1000 x spare)
+
+
+def test_fuzz_seed_range_is_decided_by_the_restatement_alone():
+    """tests/dev/fuzz_vi_alignment.py, the suite's seeds 0 .. 59 on the CPU's pre-integrations: at most 5 % undecided (measured: 0 of 60; 0 of
+    300 over seeds 0 .. 299)"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "dev"))
+    try:
+        import fuzz_vi_alignment as FZ
+    finally:
+        sys.path.remove(os.path.join(ROOT, "tests", "dev"))
+    left = []
+    for seed in range(60):
+        c = VC.fuzz_case(seed)
+        r64, rld, _ = FZ.reference(c, with_dense=False)
+        why = FZ.undecided(r64, rld)
+        if why:
+            left.append((c["name"], why))
+    print("left out on the CPU: %d of 60 %s" % (len(left), left))
+    assert len(left) <= FZ.MAX_LEFT_OUT * 60
+    assert (FZ.GATE, FZ.MARGIN) == (DEFAULT_GATE, MARGIN)
