@@ -10,7 +10,8 @@
  * sequence is aligned alone or inside any batch.  There is no CPU path.
  *
  * Left to the caller:
- *   - everything visual: relativePose, GlobalSFM::construct, solvePnP (estimator.cpp:1235-1356);
+ *   - the visual half but its bundle adjustment: relativePose, the PnP and triangulation chain of GlobalSFM::construct and the per-frame
+ *     solvePnP (estimator.cpp:1235-1356); the full BA at the end of construct is tcv_sfm_ba (include/tcv_sfm_ba.h);
  *   - f_manager.triangulate on the camera poses and `estimated_depth *= s` (estimator.cpp:1389-1400, :1419-1425);
  *   - re-propagating the window's own key-frame-to-key-frame pre_integrations[] with `bg` (estimator.cpp:1403-1406): tcv_preintegrate_device
  *     at (0, bg) does that;

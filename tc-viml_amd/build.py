@@ -12,8 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libtcv_hip.so")
-SOURCES = ["tcv_runtime.cpp", "tcv_problem.cpp", "tcv_batch_create.cpp", "tcv_batch_run.cpp", "tcv_batch_results.cpp", "tcv_coop_policy.cpp", "tcv_eval_host.cpp", "tcv_cov_host.cpp", "tcv_cov_tables.cpp", "tcv_factor_eval.hip", "tcv_solve.hip", "tcv_marg.hip", "tcv_eval.hip", "tcv_cov.hip", "tcv_preint.hip", "tcv_gauge.hip", "tcv_relo.hip", "tcv_pose_graph.hip", "tcv_align.hip", "tcv_align_host.cpp", "tcv_lines.hip", "tcv_microbench.hip", "tcv_marg_host.cpp", "tcv_pack.cpp", "tcv_hostpool.cpp", "tcv_estimator.cpp", "tcv_est_tracks.cpp", "tcv_est_window.cpp", "tcv_est_lockstep.cpp"]
-HEADERS = ["tcv_math.h", "tcv_gauge.h", "tcv_relo.h", "tcv_pose_graph.h", "tcv_factors.h", "tcv_packed.h", "tcv_host.h", "tcv_batch.h", "tcv_coop_policy.h", "tcv_runtime.h", "tcv_hostpool.h", "tcv_dev.h", "tcv_eval.h", "tcv_cov.h", "tcv_marg.h", "tcv_align.h", "tcv_est.h", os.path.join("..", "..", "include", "tcv.h"), os.path.join("..", "..", "include", "tcv_estimator.h"), os.path.join("..", "..", "include", "tcv_estimator_td.h"), os.path.join("..", "..", "include", "tcv_estimator_relo.h"), os.path.join("..", "..", "include", "tcv_pose_graph.h"), os.path.join("..", "..", "include", "tcv_covariance.h"), os.path.join("..", "..", "include", "tcv_landmark_covariance.h"), os.path.join("..", "..", "include", "tcv_vi_alignment.h")]
+SOURCES = ["tcv_runtime.cpp", "tcv_problem.cpp", "tcv_batch_create.cpp", "tcv_batch_run.cpp", "tcv_batch_results.cpp", "tcv_coop_policy.cpp", "tcv_eval_host.cpp", "tcv_cov_host.cpp", "tcv_cov_tables.cpp", "tcv_factor_eval.hip", "tcv_solve.hip", "tcv_marg.hip", "tcv_eval.hip", "tcv_cov.hip", "tcv_preint.hip", "tcv_gauge.hip", "tcv_relo.hip", "tcv_pose_graph.hip", "tcv_align.hip", "tcv_align_host.cpp", "tcv_sfm_ba.hip", "tcv_sfm_ba_host.cpp", "tcv_lines.hip", "tcv_microbench.hip", "tcv_marg_host.cpp", "tcv_pack.cpp", "tcv_hostpool.cpp", "tcv_estimator.cpp", "tcv_est_tracks.cpp", "tcv_est_window.cpp", "tcv_est_lockstep.cpp"]
+HEADERS = ["tcv_math.h", "tcv_gauge.h", "tcv_relo.h", "tcv_pose_graph.h", "tcv_factors.h", "tcv_packed.h", "tcv_host.h", "tcv_batch.h", "tcv_coop_policy.h", "tcv_runtime.h", "tcv_hostpool.h", "tcv_dev.h", "tcv_eval.h", "tcv_cov.h", "tcv_marg.h", "tcv_align.h", "tcv_sfm_ba.h", "tcv_est.h", os.path.join("..", "..", "include", "tcv.h"), os.path.join("..", "..", "include", "tcv_estimator.h"), os.path.join("..", "..", "include", "tcv_estimator_td.h"), os.path.join("..", "..", "include", "tcv_estimator_relo.h"), os.path.join("..", "..", "include", "tcv_pose_graph.h"), os.path.join("..", "..", "include", "tcv_covariance.h"), os.path.join("..", "..", "include", "tcv_landmark_covariance.h"), os.path.join("..", "..", "include", "tcv_vi_alignment.h"), os.path.join("..", "..", "include", "tcv_sfm_ba.h")]
 
 
 def _stale() -> bool:
