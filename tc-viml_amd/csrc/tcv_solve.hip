@@ -36,7 +36,7 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 // optional per-phase cycle accounting (build with -DTCV_PROFILE): lane 0 adds s_memtime deltas to 32-bit counters in LDS (the
 // spare half of the reduction scratch; a global read-modify-write per mark used to stall wave 0 for ~1 K cycles and inflated
 // densely marked phases); the counters are flushed to the global table once per window
-#ifdef TCV_PROFILE
+#if defined(TCV_PROFILE) && !defined(TCV_PROFILE_CHAIN)
 #define TCV_MARK(C, id)                                                                        \
     do {                                                                                       \
         const long long t_ = clock64();                                                        \
@@ -1755,8 +1755,8 @@ __device__ __noinline__ void back_subst(TCV_CTX_PARAMS, int nc) {
 //   column owners         thread c < npp + 1 owns column c of W for the whole elimination: w_s = L_ss^-1 (b_s - L_s,s-1 w_s-1) with
 //   (waves 0, 1)          w_s-1 in registers -- no cross-lane traffic, L blocks read from LDS as broadcasts; w_s goes to an LDS buffer
 //                         for the matrix cores and to the spill area for the back-substitution;
-//   matrix cores          S -= W_s-1' W_s-1 on v_mfma_f64_16x16x4 over the tile pairs that hold coupled columns (wave 2, which has no
-//                         other duty).
+//   matrix cores          S -= W_s-1' W_s-1 on v_mfma_f64_16x16x4 over the tile pairs that hold coupled columns: wave 2, which has no
+//                         other duty, and behind their own duty the wavefronts a step would otherwise leave waiting (chain_mfma_share).
 // Every quantity is the one the textbook right-looking block Cholesky in this order produces; only the schedule differs.
 // q accumulates u' H u over the original entries of E and B (Cauchy point).
 // LDS pool during the chain: [W buffer 0 | W buffer 1 | per step L_ss, 1/diag, L_next | T workspace | step records]
@@ -1944,23 +1944,48 @@ __device__ __forceinline__ void chain_mfma_pair2(lds_d *tiles, const lds_d *W, c
 #pragma unroll
     for (int i = 0; i < 4; i++) { C0[M.co[i]] = acc0[i]; if (two) C1[M.co[i]] = acc1[i]; }
 }
-// every pair (a, b), a >= b, over the ascending list of active tile rows, two at a time
+// every pair (a, b), a >= b, over the ascending list of active tile rows, two at a time: a TRIP is two consecutive pairs of that list
+// (the last trip of an odd count is the left-over pair alone).  The trips of one update touch disjoint tiles, so they may run on any
+// wavefront in any order: a wavefront runs the trips [lo, hi) of the list (uniform), the others' ranges cover the rest.
+__device__ __forceinline__ int chain_mfma_trips(int tmask) { const int na = __builtin_popcount(tmask); return (na * (na + 1) / 2 + 1) >> 1; }
 template <int NT>
-__device__ __forceinline__ void chain_mfma_update_all(const Ctx<NT> &C, const lds_d *W, const ChainMfmaLane &M, int tmask, int npp) {
+__device__ __forceinline__ void chain_mfma_update_all(const Ctx<NT> &C, const lds_d *W, const ChainMfmaLane &M, int tmask, int npp, int lo, int hi) {
     int act = 0, na = 0;      // 4 bits per entry
     for (int I = 0; I < C.ntd; I++) if ((tmask >> I) & 1) { act |= I << (4 * na); na++; }
     const int npair = na * (na + 1) / 2;
     int a = 0, b = 0, pI = -1, pJ = -1;
-    for (int p = 0; p < npair; p++) {
+    for (int p = 0; p < npair && p < 2 * hi; p++) {
         const int I = (act >> (4 * a)) & 15, J = (act >> (4 * b)) & 15;
-        if (pI < 0) { pI = I; pJ = J; }
-        else { chain_mfma_pair2(C.tiles, W, M, npp, pI, pJ, I, J, true); pI = -1; }
+        if (p >= 2 * lo) {
+            if (pI < 0) { pI = I; pJ = J; }
+            else { chain_mfma_pair2(C.tiles, W, M, npp, pI, pJ, I, J, true); pI = -1; }
+        }
         if (b == a) { a++; b = 0; } else b++;
     }
     if (pI >= 0) chain_mfma_pair2(C.tiles, W, M, npp, pI, pJ, pI, pJ, false);
 }
+// Which trips of the update S -= W_s-1' W_s-1 a wavefront runs in interval s, behind its own duty of that interval.  nt trips; ne steps.
+//   s == ne       the drain: nothing else is left, the trips go over all four wavefronts;
+//   s == ne - 1   no T step is left: waves 2 and 3 halve the trips (the column owners are busy with W_ne-1);
+//   s <  ne - 1   wave 3 factors the panel of step s + 1 first (7.2 K cycles with its fetch, the same in every step: five of wave 2's
+//                 trips at 1.45 K each), then takes (nt - 5) / 2 trips: none up to four active tile rows (nt <= 5), one of the eight
+//                 trips of five rows.  Two there made wave 3 the last to arrive (a trip behind the T step costs it 2.3 - 2.7 K), and a
+//                 trip for wave 1 on top measured nothing (profiles/chain_step_balance.txt).
+// The left-over pair is the last trip of the list, wherever it lands.  Uniform: from the step record's CH_TMASK alone.
+__device__ __forceinline__ void chain_mfma_share(int wave, int s, int ne, int nt, int &lo, int &hi) {
+    lo = hi = 0;
+    if (s == ne) { lo = wave * nt / 4; hi = (wave + 1) * nt / 4; return; }
+    const int n3 = (s == ne - 1) ? nt / 2 : max(0, (nt - 5) / 2);
+    if (wave == 2) hi = nt - n3;
+    else if (wave == 3) { lo = nt - n3; hi = nt; }
+}
 
-#ifdef TCV_PROFILE
+// -DTCV_PROFILE -DTCV_PROFILE_CHAIN=w (w = 0..3, one build per wavefront; tools/dev_chain_steps.py): the 32 accumulators hold the chain's
+// steps as wavefront w sees them instead of the phases -- [s] the cycles from the previous step barrier to w's arrival at the barrier of
+// interval s, [13 + s] how often w was the last of the four to arrive there (ties: the lowest wavefront), [26] the chains run.  The
+// arrival stamps of an interval stand in red[57..60] (two sets of four 32-bit words, by the parity of s, so that an early wavefront's next
+// stamp does not replace one that is still being compared).  Every other mark of the profile build is off in these builds.
+#if defined(TCV_PROFILE) && !defined(TCV_PROFILE_CHAIN)
 #define CH_TIC() const long long t_role = clock64()
 #define CH_TOC(slot, cond) do { if (cond) ((lds_u *)(C.red + 40))[slot] += (unsigned)(clock64() - t_role); } while (0)
 #else
@@ -2032,6 +2057,9 @@ __device__ __noinline__ ChainOut chain_forward(TCV_CTX_PARAMS, double mu) {
         if (*C.flag && !ABL_FORCE(C)) { ChainOut bad; bad.q = 0.0; bad.ok = false; return bad; }
 #else
         if (*C.flag) { ChainOut bad; bad.q = 0.0; bad.ok = false; return bad; }      // uniform: read after a barrier, written before it
+#endif
+#ifdef TCV_PROFILE_CHAIN
+        const long long t_step0 = clock64();
 #endif
         // ---- T pipeline: one step ahead
         CH_TIC();
@@ -2108,20 +2136,42 @@ __device__ __noinline__ ChainOut chain_forward(TCV_CTX_PARAMS, double mu) {
             CH_TOC(PH_CH_B, tid == 0);
         }
         // ---- matrix cores: S -= W_s-1' W_s-1
-        if (s > 0 && wave == 2 && ABL(C, AB_CH_MFMA)) {
-            // wave 2 (no other duty) takes every pair.  Which wavefront a step waits for changes along the chain (timers of the -DTCV_PROFILE
-            // build at the step's barrier): the early steps, with two or three active tile rows, wait for the T pipeline, the late ones for
-            // the W tiles; sharing the pairs out to the W wavefronts (thirds, sevenths, ... measured) never shortened a step
+        if (s > 0 && ABL(C, AB_CH_MFMA)) {
+            // wave 2 (no other duty) takes the trips the others do not.  Which wavefront a step waits for changes along the chain (per-step
+            // table of the -DTCV_PROFILE_CHAIN build, profiles/chain_step_balance.txt): the early steps, with two or three active tile
+            // rows, wait for the T pipeline, the late ones, with 10 or 15 pairs, for wave 2 -- so wave 3 takes trips behind its T step
+            // where the pairs outweigh it, half of them where it has no T step, and the drain goes over all four (chain_mfma_share).
+            // The W buffer of step s - 1 is next written in interval s + 1 and the T-wave writes ltab and ta only: no further barrier.
             const lds_i *hp = L.tab + (s - 1) * CH_STRIDE;
             const lds_d *Wp = L.wbuf + ((s - 1) & 1) * CH_W * wld;
-            if (wave == 2) chain_mfma_update_all<NT>(C, Wp, ML, hp[CH_TMASK], npp);
+            const int tmp = hp[CH_TMASK];
+            int lo, hi;
+            chain_mfma_share(wave, s, ne, chain_mfma_trips(tmp), lo, hi);
+            lo = __builtin_amdgcn_readfirstlane(lo); hi = __builtin_amdgcn_readfirstlane(hi);
+            if (lo < hi) chain_mfma_update_all<NT>(C, Wp, ML, tmp, npp, lo, hi);
             CH_TOC(PH_CH_C, tid == 128);
         }
-#ifdef TCV_PROFILE
+#ifdef TCV_PROFILE_CHAIN
+        const unsigned t_here = (unsigned)clock64();
+        lds_u *stamp = (lds_u *)(C.red + 57) + 4 * (s & 1);
+        if (lane == 0) stamp[wave] = t_here;
+        __syncthreads();
+        if (tid == 64 * (TCV_PROFILE_CHAIN)) {
+            lds_u *cn = (lds_u *)(C.red + 40);
+            const int ss = min(s, 12);
+            bool last = true;
+            for (int w = 0; w < 4; w++) { const int d = (int)(stamp[w] - t_here); if (w != wave && (d > 0 || (d == 0 && w < wave))) last = false; }
+            cn[ss] += t_here - (unsigned)t_step0;
+            cn[13 + ss] += last ? 1u : 0u;
+            if (s == 0) cn[26] += 1u;
+        }
+#elif defined(TCV_PROFILE)
         const long long t_arrive = clock64();
 #endif
+#ifndef TCV_PROFILE_CHAIN
         __syncthreads();
-#ifdef TCV_PROFILE
+#endif
+#if defined(TCV_PROFILE) && !defined(TCV_PROFILE_CHAIN)
         // how long each wavefront waits at the step's barrier: the one that waits least sets the step (slots: chain_bwd's -- unused here -- and 29..31)
         if (lane == 0) ((lds_u *)(C.red + 40))[wave == 0 ? (int)PH_CHAIN_BWD : 28 + wave] += (unsigned)(clock64() - t_arrive);
 #endif
